@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- ERP Mpixels/s enc+dec @512x1024, model-idx 3 (BASELINE.json metric) on N MI355X of one node.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps and K timed steps, writes the last step's outputs if --dump-outputs is given and prints the
+result line (headline, `ms_per_step`).  Everything else below -- calibration, round-trip checks, side figures, kernel rows, roofline,
+CPU baseline -- runs only with --full.
 
 One "step" = one pass of the hot path over one batch of synthetic images per GPU: BOTH bitstreams of every image -- the
 quantised latent (48x64x128 symbols under its importance mask) and the 32x64 importance map, what the reference's
@@ -14,7 +18,7 @@ Launch: with `--gpus N > 1` and no WORLD_SIZE in the environment, this process m
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`
 (lic360_shard.launch_ranks), which is also how the driver launches it; every rank asserts WORLD_SIZE == --gpus.
 
-Rank 0 prints ONE JSON line (contract in the task description) with, besides the headline:
+Rank 0 prints ONE JSON line: the headline and, with --full only:
   roofline      the dominant kernel (the conv kernel class with the most GPU time), measured ALONE on the GPU: one sub-batch,
                 one stream, HIP events around every launch on the launch stream (an instrumented pass outside the timed
                 region; the timed region runs with instrumentation off).  `concurrent` repeats it with all streams running.
@@ -56,6 +60,7 @@ NET_GMAC = 123.42
 IMP_GMAC = 6.22
 F32_MFMA_PEAK_TFLOPS = 157.3            # MI355X_MICROARCH.md: fp32 MFMA dense peak
 HBM_PEAK_GBS = 8000.0                   # MI355X_MICROARCH.md: HBM3E ~8 TB/s
+DUMP_SAMPLE, DUMP_SEED, DUMP_LIMIT = 8, 20261016, 64 * 10 ** 6     # --dump-outputs: images of the sample, its seed, bytes in all
 
 
 def parse_args():
@@ -73,10 +78,19 @@ def parse_args():
     ap.add_argument("--masks", choices=("smooth", "iid"), default="smooth", help="importance maps of the synthetic latents: smooth = SURVEY.md 8d's "
                     "L = clip(round(24 + 12 cos(lat) n)), n smooth noise (tests/util.py:latent_smooth; the workload since round 6); iid = every map cell drawn "
                     "independently (rounds 1-5; the adversarial case of the dead-cone skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (skip latent-only pass, single image, config4, streaming ops)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: calibration, round-trip checks of the timed data, side "
+                    "figures (batch 144, iid masks, latent only, config 4 / 5, single image, streaming ops, transforms), per-kernel-class rows + roofline, "
+                    "CPU baseline.  Off: set-up, warm-up, the timed steps, --dump-outputs, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed (rank 0's images) as DIR/<name>.npy "
+                    "(float32 / float64): bitstream lengths and CRC-32s of every image; decoded latent, decoded mask, decoded importance map and both "
+                    "bitstreams of a fixed seeded sample of %d images" % DUMP_SAMPLE)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only (skip latent-only pass, single image, config4, streaming ops)")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the launch / sharding / reporting path on gloo: no codec work, value 0")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def split_for_streams(n, ns):
@@ -110,6 +124,51 @@ def synth_latents(batch, seed0, h=H, w=W, kind=None):
         masks.append(m)
         levels.append(lv)
     return np.concatenate(codes, 0), np.concatenate(masks, 0), np.concatenate(levels, 0)
+
+
+def dump_outputs(path, codecs, icodecs, mask_bufs, sizes, nbytes, inbytes):
+    """--dump-outputs: what the last timed step handed its caller, as path/<name>.npy.  Every image: both bitstreams' lengths and CRC-32s;
+    a fixed seeded sample of DUMP_SAMPLE images: the decoded latent, the mask the device derived from the decoded importance map, the decoded
+    map and both bitstreams (one byte per float32, zero past a stream's end).  Image i is image i of the per-GPU batch (sub-batches in order)."""
+    import zlib
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    where = [(j, i) for j, sz in enumerate(sizes) for i in range(sz)]         # image -> (sub-batch, index in it)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(len(where), min(DUMP_SAMPLE, len(where)), replace=False))
+
+    def streams(cds, nb):
+        out, k = [], 0
+        for c, sz in zip(cds, sizes):
+            if sz:
+                host = c.bytes[:sz, :int(nb[k:k + sz].max())].cpu().numpy()
+                out += [host[i, :int(nb[k + i])] for i in range(sz)]
+            k += sz
+        return out
+
+    def padded(rows):
+        a = np.zeros((len(rows), max(len(r) for r in rows)), np.float32)
+        for i, r in enumerate(rows):
+            a[i, :len(r)] = r
+        return a
+
+    lat, imp = streams(codecs, nbytes), streams(icodecs, inbytes)
+    sample = lambda t: torch.stack([t(j)[i] for j, i in (where[p] for p in pick)]).cpu().numpy().astype(np.float32)
+    arrays = {
+        "sample_images": pick.astype(np.float64),
+        "latent_nbytes": np.asarray(nbytes, np.float64), "importance_nbytes": np.asarray(inbytes, np.float64),
+        "latent_crc32": np.array([zlib.crc32(s.tobytes()) for s in lat], np.float64),
+        "importance_crc32": np.array([zlib.crc32(s.tobytes()) for s in imp], np.float64),
+        "latent_code": sample(lambda j: codecs[j].code_out), "latent_mask": sample(lambda j: mask_bufs[j]),
+        "importance_levels": sample(lambda j: icodecs[j].levels_out),
+        "latent_bitstream": padded([lat[p] for p in pick]), "importance_bitstream": padded([imp[p] for p in pick]),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes, limit %d" % (total, DUMP_LIMIT)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def cpu_baseline(layers, imp_layers, code, mask, levels, gpu_bytes, gpu_imp_bytes):
@@ -390,23 +449,29 @@ def run_rank(args):
         return ok
 
     say = progress if rank == 0 else (lambda m: None)
-    calib = calibrate(dev) if rank == 0 else {}
+    calib = calibrate(dev) if rank == 0 and args.full else {}
     say("codecs ready; calibration %s; warm-up + %d timed steps of %d images" % (calib, args.steps, B))
     step = lambda: run(codes, masks, levels, True)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    ok = exact(codes, masks, levels)
+    ok = exact(codes, masks, levels) if args.full else None
     dt = shard.timed(step, args.steps, dev)                   # barrier + sync both sides, MAX over ranks; instrumentation off
-    ok = ok and exact(codes, masks, levels)
+    if args.full:
+        ok = ok and exact(codes, masks, levels)
     nbytes = np.concatenate([c.nbytes[:cd.shape[0]].cpu().numpy() for c, cd in zip(codecs, codes)])
     inbytes = np.concatenate([c.nbytes[:cd.shape[0]].cpu().numpy() for c, cd in zip(icodecs, codes)])
-    img0 = (bytes(codecs[0].bytes[0, :int(nbytes[0])].cpu().numpy().tobytes()), bytes(icodecs[0].bytes[0, :int(inbytes[0])].cpu().numpy().tobytes()))
-
+    if args.full:                                                      # image 0's bitstreams, for the CPU baseline's byte comparison
+        img0 = (bytes(codecs[0].bytes[0, :int(nbytes[0])].cpu().numpy().tobytes()), bytes(icodecs[0].bytes[0, :int(inbytes[0])].cpu().numpy().tobytes()))
     say("timed region done: %.1f ms per step" % (dt / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        say("outputs of the last step -> %s" % args.dump_outputs)
+        dump_outputs(args.dump_outputs, codecs, icodecs, [mbufs[i][flip[0]] for i in range(ns)], sizes, nbytes, inbytes)
+
     extras = {}
+    full_extras = args.full and not args.no_extras
     ks = max(1, min(args.steps, 3))                                    # timed steps of the side figures (the headline alone runs args.steps: the default run stays within minutes)
-    if not args.no_extras and B > 144 and all(sz >= 48 for sz in sizes) and ns == 3:
+    if full_extras and B > 144 and all(sz >= 48 for sz in sizes) and ns == 3:
         # the per-GPU batch of rounds 1-5 (144 = 3 x 48 images) through the same codecs: what the larger sub-batches add
         c48, m48, l48 = [c[:48] for c in codes], [m[:48] for m in masks], [l[:48] for l in levels]
         run(c48, m48, l48)
@@ -414,7 +479,7 @@ def run_rank(args):
         ok = ok and exact(c48, m48, l48)
         extras["batch144"] = {"value": world * 144 * ks * PIXELS / dt48 / 1e6, "unit": "Mpixel/s", "ms_per_step": dt48 / ks * 1e3,
                               "note": "144 images per GPU (3 sub-batches of 48), the per-GPU batch of rounds 1-5"}
-    if not args.no_extras and args.masks != "iid":
+    if full_extras and args.masks != "iid":
         # the same step on the masks of rounds 1-5 (every map cell drawn independently): nothing for the dead-cone skip to find -- the adversarial case
         ci, mi, li = synth_latents(B, seed0=1000 * rank, kind="iid")
         o, cdi, mki, lvi = 0, [], [], []
@@ -427,7 +492,7 @@ def run_rank(args):
         extras["iid_masks"] = {"value": world * B * ks * PIXELS / dti / 1e6, "unit": "Mpixel/s", "ms_per_step": dti / ks * 1e3,
                                "note": "the timed step on i.i.d. importance maps (tests/util.py:latent, the workload of rounds 1-5)"}
         del cdi, mki, lvi
-    if not args.no_extras:
+    if full_extras:
         # the latent stream alone (98.6 % of the bytes, 95 % of the MACs): round 1's headline, kept for comparison
         run(codes, masks, levels, False)
         dt_lat = shard.timed(lambda: run(codes, masks, levels, False), ks, dev)
@@ -518,73 +583,79 @@ def run_rank(args):
         del c5, i5, cd5, mk5, lv5
         mb5 = None
         torch.cuda.empty_cache()
-    ok = shard.all_ok(ok, dev)
+    if args.full:
+        ok = shard.all_ok(ok, dev)
 
     if rank == 0:
+        cfg = {"workload": "%d/GPU synthetic 512x1024 ERPs, model-idx 3 --ssim seed, latent+importance bitstreams, entropy enc+dec" % B,
+               "images_per_gpu_per_step": B, "streams": ns}
+        if args.full:
+            cfg.update(roundtrip_exact=ok, bit_exact_against="CPU oracle (arithmetic coder pinned to the reference's ArithmeticCoder.cpp; float kernels unpinnable without CUDA)")
+        cfg.update(mean_latent_bytes=float(nbytes.mean()), mean_importance_bytes=float(inbytes.mean()))
         out = {
             "metric": "ERP Mpixels/s enc+dec @512x1024 model-idx 3; bitstream bit-exact vs ref",
             "value": world * B * args.steps * PIXELS / dt / 1e6, "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%d/GPU synthetic 512x1024 ERPs, model-idx 3 --ssim seed, latent+importance bitstreams, entropy enc+dec" % B,
-                       "images_per_gpu_per_step": B, "streams": ns, "roundtrip_exact": ok,
-                       "bit_exact_against": "CPU oracle (arithmetic coder pinned to the reference's ArithmeticCoder.cpp; float kernels unpinnable without CUDA)",
-                       "mean_latent_bytes": float(nbytes.mean()), "mean_importance_bytes": float(inbytes.mean())},
+            "dtype": "f32", "data": "synthetic", "config": cfg,
         }
         assert len(out["config"]["workload"]) <= 120
-        # the side figures as SCALAR keys of `config` (the driver's record keeps scalars only); the nested forms stay beside them
-        flat = out["config"]
-        flat.update(calib)
-        if calib.get("calib_mfma_tflops"):
-            flat["value_per_calib_mfma_tflop"] = out["value"] / calib["calib_mfma_tflops"]
-        if "iid_masks" in extras:
-            flat["iid_masks_mpixel_s"] = extras["iid_masks"]["value"]
-        if "batch144" in extras:
-            flat["batch144_mpixel_s"] = extras["batch144"]["value"]
-        if "latent_stream_only" in extras:
-            flat["latent_only_mpixel_s"] = extras["latent_stream_only"]["value"]
-        if "config4" in extras:
-            flat["config4_mpixel_s"], flat["config4_ms"] = extras["config4"]["value"], extras["config4"]["ms"]
-        if "config4_per_gpu_share" in extras:
-            sh = extras["config4_per_gpu_share"]
-            flat["config4_share8_ms"] = sh["ms"]
-            flat["config4_pred_8gpu_mpixel_s"] = sh["predicted_8gpu_strong"]["value"]
-            flat["config4_pred_8gpu_x"] = sh["predicted_8gpu_strong"]["vs_this_gpu_on_all_64"]
-        if "value" in extras.get("config5", {}):
-            flat["config5_mpixel_s"], flat["config5_ms"] = extras["config5"]["value"], extras["config5"]["ms"]
-        out["config"].update(extras)
-        say("instrumented passes (per-kernel-class events)")
-        inst = instrumented(args, codecs, icodecs, codes, masks, levels, streams, dev, dt, B)
-        skip = inst.pop("skip")
-        out.update(inst)
-        out["config"]["masks"] = args.masks
-        out["config"]["dead_mac_fraction"] = skip["dead_mac_fraction"]
-        out["config"]["dead_cone_skip"] = skip
-        if world == 1 and not args.no_extras:
-            si = single_image(codecs[0], icodecs[0], codes[0], masks[0], levels[0], streams[0], istreams[0], mbufs[0][0], dev)
-            out["config"]["single_image"] = si
-            out["config"]["single_encode_ms"], out["config"]["single_decode_ms"] = si["encode_ms"], si["decode_ms"]
-            say("single image done; streaming ops")
-            try:
-                import stream_ops_bench
-                rows = stream_ops_bench.measure(batches=(32,), device=local)
-                out["kernels"] += [{"kernel": r["op"], "bound": "hbm", "achieved": r["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                    "frac": r["frac_of_hbm_peak"], "avg_launch_ms": r["us"] * 1e-3, "images_per_launch": 32} for r in rows]
-            except Exception as e:                                     # noqa: BLE001  (never lose the headline to a side table)
-                out["config"]["streaming_ops_error"] = repr(e)
-            try:       # the neighbouring row f1: analysis / synthesis transforms (library convs + native ops) and the one-pass GDN
-                say("transforms + whole codec")
-                import transform_bench
-                out["kernels"] += transform_bench.measure(batch=8, device=local)
-            except Exception as e:                                     # noqa: BLE001
-                out["config"]["transform_bench_error"] = repr(e)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(layers, imp_layers, code_np[0:1], mask_np[0:1], level_np[0:1], img0[0], img0[1])
+        if args.full:
+            # the side figures as SCALAR keys of `config` (the driver's record keeps scalars only); the nested forms stay beside them
+            flat = out["config"]
+            flat.update(calib)
+            if calib.get("calib_mfma_tflops"):
+                flat["value_per_calib_mfma_tflop"] = out["value"] / calib["calib_mfma_tflops"]
+            if "iid_masks" in extras:
+                flat["iid_masks_mpixel_s"] = extras["iid_masks"]["value"]
+            if "batch144" in extras:
+                flat["batch144_mpixel_s"] = extras["batch144"]["value"]
+            if "latent_stream_only" in extras:
+                flat["latent_only_mpixel_s"] = extras["latent_stream_only"]["value"]
+            if "config4" in extras:
+                flat["config4_mpixel_s"], flat["config4_ms"] = extras["config4"]["value"], extras["config4"]["ms"]
+            if "config4_per_gpu_share" in extras:
+                sh = extras["config4_per_gpu_share"]
+                flat["config4_share8_ms"] = sh["ms"]
+                flat["config4_pred_8gpu_mpixel_s"] = sh["predicted_8gpu_strong"]["value"]
+                flat["config4_pred_8gpu_x"] = sh["predicted_8gpu_strong"]["vs_this_gpu_on_all_64"]
+            if "value" in extras.get("config5", {}):
+                flat["config5_mpixel_s"], flat["config5_ms"] = extras["config5"]["value"], extras["config5"]["ms"]
+            out["config"].update(extras)
+            say("instrumented passes (per-kernel-class events)")
+            inst = instrumented(args, codecs, icodecs, codes, masks, levels, streams, dev, dt, B)
+            skip = inst.pop("skip")
+            out.update(inst)
+            out["config"]["masks"] = args.masks
+            out["config"]["dead_mac_fraction"] = skip["dead_mac_fraction"]
+            out["config"]["dead_cone_skip"] = skip
+            if world == 1 and not args.no_extras:
+                si = single_image(codecs[0], icodecs[0], codes[0], masks[0], levels[0], streams[0], istreams[0], mbufs[0][0], dev)
+                out["config"]["single_image"] = si
+                out["config"]["single_encode_ms"], out["config"]["single_decode_ms"] = si["encode_ms"], si["decode_ms"]
+                say("single image done; streaming ops")
+                try:
+                    import stream_ops_bench
+                    rows = stream_ops_bench.measure(batches=(32,), device=local)
+                    out["kernels"] += [{"kernel": r["op"], "bound": "hbm", "achieved": r["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                        "frac": r["frac_of_hbm_peak"], "avg_launch_ms": r["us"] * 1e-3, "images_per_launch": 32} for r in rows]
+                except Exception as e:                                     # noqa: BLE001  (never lose the headline to a side table)
+                    out["config"]["streaming_ops_error"] = repr(e)
+                try:       # the neighbouring row f1: analysis / synthesis transforms (library convs + native ops) and the one-pass GDN
+                    say("transforms + whole codec")
+                    import transform_bench
+                    out["kernels"] += transform_bench.measure(batch=8, device=local)
+                except Exception as e:                                     # noqa: BLE001
+                    out["config"]["transform_bench_error"] = repr(e)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(layers, imp_layers, code_np[0:1], mask_np[0:1], level_np[0:1], img0[0], img0[1])
+        else:
+            out["config"]["masks"] = args.masks
         print(json.dumps(out))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
 
 
 def single_image(c, ic, code, mask, lv, st, ist, mb, dev):

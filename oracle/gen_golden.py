@@ -13,6 +13,9 @@ Cases (SURVEY.md §8c pins (1), §8d config 1):
   rand49        2048 symbols, 49-symbol alphabet (importance-map codec), unmasked
   skew8         4096 symbols, near-degenerate tables (frequencies of 1) -> long underflow runs
   empty         0 symbols -> the bare terminator byte
+
+`gen_golden.py --seeds` writes tests/golden/ac_ref_seeds.npz instead: the reference's bitstreams and decodes of the three
+random cases of test_oracle_ac.py::test_against_compiled_reference.
 """
 import hashlib
 import os
@@ -119,5 +122,41 @@ def main():
     print("wrote", os.path.normpath(dst), os.path.getsize(dst), "bytes; fixed_full nbytes =", int(out["fixed_full_nbytes"][0]))
 
 
+SEED_NCODE = {0: 8, 1: 49, 2: 3}
+
+
+def seed_case(seed):
+    """inputs of tests/test_oracle_ac.py::test_against_compiled_reference[seed] (3000 symbols, 30 % masked; seed 2: skewed tables)"""
+    rng = np.random.default_rng(seed)
+    n, ncode = 3000, SEED_NCODE[seed]
+    tab = rand_tables(rng, n, ncode, skew=(seed == 2))
+    lab = draw_from_tables(rng, tab)
+    mask = (rng.random(n) > 0.3).astype(np.float32)
+    return tab, ncode, lab, mask
+
+
+def case_digest(tab, lab, mask):
+    h = hashlib.sha256()
+    for a in (tab.astype(np.int32), lab.astype(np.int32), mask.astype(np.float32)):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return np.frombuffer(h.digest(), np.uint8)
+
+
+def main_seeds():
+    """tests/golden/ac_ref_seeds.npz: the reference coder's bitstream and decode of each seed_case, and a digest of its inputs"""
+    orc.build(ref=True)
+    assert orc.have_ref(), "reference coder not built"
+    out = {}
+    for seed in SEED_NCODE:
+        tab, ncode, lab, mask = seed_case(seed)
+        data = orc.ref_encode(tab, ncode, lab, mask)
+        out["seed%d_inputs_sha256" % seed] = case_digest(tab, lab, mask)
+        out["seed%d_bytes" % seed] = np.frombuffer(data, np.uint8)
+        out["seed%d_decoded" % seed] = orc.ref_decode(data, tab, ncode, mask, len(lab))
+    dst = os.path.join(HERE, "..", "tests", "golden", "ac_ref_seeds.npz")
+    np.savez_compressed(dst, **out)
+    print("wrote", os.path.normpath(dst), os.path.getsize(dst), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    main_seeds() if sys.argv[1:] == ["--seeds"] else main()
