@@ -29,11 +29,9 @@ LIC360_API int lic360_calib_mfma_f32(void *stream, double *tflops, int *cus_out)
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     if (cus_out) *cus_out = cus;
-    float *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, (size_t)cus * 512 * sizeof(float)));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    DevBuf<float> buf;
+    HipEvent e0, e1;
+    if (buf.alloc((size_t)cus * 512) || e0.create(hipEventDefault) || e1.create(hipEventDefault)) return 1;
     const int iters = 40000;
     hipLaunchKernelGGL(k_calib_mfma, dim3(cus), dim3(512), 0, s, buf, 100);
     LAUNCH_CHECK();
@@ -45,6 +43,5 @@ LIC360_API int lic360_calib_mfma_f32(void *stream, double *tflops, int *cus_out)
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     *tflops = 2048.0 * 8.0 * iters * 8.0 * cus / (ms * 1e-3) / 1e12;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(buf);
     return 0;
 }

@@ -98,20 +98,16 @@ LIC360_API long lic360_conv144_packed_floats(const lic360_conv_plan *p) {
 LIC360_API int lic360_conv144_pack(void *stream, const lic360_conv_plan *p, const float *weight, float *packed) {
     ARG_CHECK(p && conv144_ok(p) && weight && packed);
     const int NQ = conv144_nq(p), NG = ITerms<144, 1>::NG, nint = 4 * NQ + 8 * 4 * NG;
-    int *h = (int *)malloc(sizeof(int) * nint), *d = nullptr;
-    i144_fill_src<1>(h, h + 4 * NQ);
-    hipError_t e = hipMalloc((void **)&d, sizeof(int) * nint);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, h, sizeof(int) * nint, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) {
-        const long total = lic360_conv144_packed_floats(p);
-        hipLaunchKernelGGL(k_conv144_pack, dim3(lic360_blocks(total, 4)), dim3(256), 0, (hipStream_t)stream, weight, d, d + 4 * NQ, packed, p->nout, p->C, NG,
-                           total);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);          // h / d are released below
-    free(h);
-    if (d) (void)hipFree(d);
-    HIP_TRY(e);
+    std::vector<int> h(nint);
+    i144_fill_src<1>(h.data(), h.data() + 4 * NQ);
+    DevBuf<int> d;
+    if (d.alloc(nint)) return 1;
+    HIP_TRY(hipMemcpyAsync(d, h.data(), sizeof(int) * nint, hipMemcpyHostToDevice, (hipStream_t)stream));
+    const long total = lic360_conv144_packed_floats(p);
+    hipLaunchKernelGGL(k_conv144_pack, dim3(lic360_blocks(total, 4)), dim3(256), 0, (hipStream_t)stream, weight, d, d + 4 * NQ, packed, p->nout, p->C, NG,
+                       total);
+    LAUNCH_CHECK();
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));                        // before h / d are released
     return 0;
 }
 

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <thread>
 #include <atomic>
+#include <memory>
 #include <immintrin.h>
 
 struct AcDevState {            // per-image decoder state carried across planes
@@ -29,40 +30,52 @@ struct AcDevState {            // per-image decoder state carried across planes
     unsigned long long acc;
 };
 
+struct PlanDeleter { void operator()(lic360_conv_plan *p) const { lic360_conv_plan_destroy(p); } };
+using PlanPtr = std::unique_ptr<lic360_conv_plan, PlanDeleter>;
+static int make_plan(PlanPtr &out, int channel, int ngroup, int nout, int ksz, int constrain) {
+    lic360_conv_plan *p = nullptr;
+    const int rc = lic360_conv_plan_create(channel, ngroup, nout, ksz, constrain, &p);
+    out.reset(p);
+    return rc;
+}
+
 enum { PROF_EC_FIRST, PROF_EC_HIDDEN, PROF_EC_LAST, PROF_ENC_TABLES, PROF_AC_ENCODE,
        PROF_DC_FIRST, PROF_DC_HIDDEN, PROF_DC_LAST, PROF_DEC_TABLES, PROF_DEC_PLANE, PROF_NCLS };
 static const char *const PROF_NAMES = "ec_first,ec_hidden,ec_last,enc_tables,ac_encode,dc_first,dc_hidden,dc_last,dec_tables,dec_plane";
 
+struct HostLeg;
 struct lic360_codec {
     int G, H, W, maxB, S, P, HW;
     int sk_rows, sk_pitch, sk_row0, sk_col0;
     int e_hp, e_wp, e_off;                     // encode activation planes: [e_hp][e_wp], cell (r, c) at [(r+e_off)*e_wp + c+e_off]
-    lic360_conv_plan *plan[3];                 // first, hidden, last
-    float *packed[12], *bias[12], *act[12];
-    float *packed4[12];                        // leaf-resident (4x4x1 MFMA) weight layout, when the shape allows it
-    float *packed16[12];                       // 16x16x4 MFMA weight layout of the encode-order kernel (csrc/cconv16_kernels.hip)
+    PlanPtr plan[3];                           // first, hidden, last
+    DevBuf<float> packed[12], bias[12], act[12];
+    DevBuf<float> packed4[12];                 // leaf-resident (4x4x1 MFMA) weight layout, when the shape allows it
+    DevBuf<float> packed16[12];                // 16x16x4 MFMA weight layout of the encode-order kernel (csrc/cconv16_kernels.hip)
     bool use4;                                 // the nets' shapes fit the specialised kernels (4x4x1 decode order, 16x16x4 encode order with the last layer
                                                // fused with the CDF tables); otherwise -- or under LIC360_FUSED_CONV=16 -- the generic kernels of cconv_kernels.hip
     int dc_mode = 0;                           // schedule switches of the decode kernel (LIC360_NOPACK, LIC360_DC_GSTEP), read from the environment once, at create
-    int *e_ctr = nullptr;                      // 8 task counters of the encode kernel
+    DevBuf<int> e_ctr;                         // 8 task counters of the encode kernel
     std::vector<int> h_idx, h_pidx, h_plane_start;
-    int *d_idx, *d_pidx, *d_plane_start;
-    float *e_x0, *e_buf[3];
-    uint2 *e_rec;
-    float *d_x0, *d_act[11], *d_y;
-    AcDevState *d_state;
-    uint4 *d_tab = nullptr;                    // per-plane CDF tables [maxB][tab_pitch][2] (k_dec_tables -> k_dec_plane)
+    DevBuf<int> d_idx, d_pidx, d_plane_start;
+    DevBuf<float> e_x0, e_buf[3];
+    DevBuf<uint2> e_rec;
+    DevBuf<float> d_x0, d_act[11], d_y;
+    DevBuf<AcDevState> d_state;
+    DevBuf<uint4> d_tab;                       // per-plane CDF tables [maxB][tab_pitch][2] (k_dec_tables -> k_dec_plane)
     int tab_pitch = 0;
-    bool layer_set[12];
+    bool layer_set[12] = {};
     // Dead-cone skip (round 6, need.h): outputs no coded symbol can observe are not computed -- per-layer need maps from the mask, compacted task lists
     // for the encode-order kernels (layers 1..11), per-plane task records for the decode-order kernel (layers 1..11; batches of >= 16 images with
     // 8 | batch on images of at most 64 rows -- below that a list could only drop whole three-group tasks, which almost never happens, and the decode
     // would have to wait for the whole importance map instead of running behind it).  LIC360_NOSKIP=1 (read at create) turns it off.
     bool skip = false;
-    signed char *need = nullptr, *need_d = nullptr, *tmax = nullptr;
-    lic360_ec_lists ecl;
+    DevBuf<signed char> need, need_d, tmax;
+    lic360_ec_lists ecl;                       // views of ecl_list / ecl_cnt and dcl_list / dcl_cnt for the launchers
     lic360_dc_lists dcl;
-    unsigned long long *stats = nullptr;       // [2][12][NEED_STAT_G]: live tiles per (layer, group block) of the encodes, stored cells per (layer, group) of the decodes
+    DevBuf<int> ecl_list, ecl_cnt, dcl_cnt;
+    DevBuf<uint4> dcl_list;
+    DevBuf<unsigned long long> stats;          // [2][12][NEED_STAT_G]: live tiles per (layer, group block) of the encodes, stored cells per (layer, group) of the decodes
     bool stats_on = false;
     // Host leg of the arithmetic coder (round 6; the reference's own division of labour: extension/coder.cpp:70-113 runs on the CPU).  One wave per image
     // is the slowest possible coder -- 27.6 ms per image to encode, ~170 us per plane to decode -- and only hides behind other images' convolutions; a
@@ -71,21 +84,21 @@ struct lic360_codec {
     // image decodes its symbols, a GPU kernel waits for them on polled flags (no API call, no stream synchronisation per plane).
     int coder_mode = 2;                        // 0 device, 1 host, 2 auto (host when B <= coder_auto_max); LIC360_HOST_CODER=0|1 overrides at create
     int coder_auto_max = 8;                    // (16 images per stream on three streams lose: config 4 as written 52 -> 36 Mpixel/s, config 5 47 -> 18 -- every plane then waits for its slowest host thread while the GPU coder of one stream hides behind the other streams' convolutions)
-    struct HostLeg *hl = nullptr;
     // optional per-kernel-class timing (bench.py's instrumented pass; off in the timed region): HIP event pairs around
     // every launch of a class, recorded on the launch stream
     bool prof = false;
-    std::vector<hipEvent_t> ev[PROF_NCLS];     // start/stop pairs
+    std::vector<HipEvent> ev[PROF_NCLS];       // start/stop pairs
     size_t n_ev[PROF_NCLS] = {};
+    std::unique_ptr<HostLeg> hl;               // last, so destroyed first: it aborts, joins and synchronises the device before the buffers in-flight kernels read go
 };
 
 static int prof_mark(lic360_codec *c, int cls, hipStream_t s) {
     if (!c->prof) return 0;
-    std::vector<hipEvent_t> &pool = c->ev[cls];
+    std::vector<HipEvent> &pool = c->ev[cls];
     if (c->n_ev[cls] >= pool.size()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        pool.push_back(e);
+        HipEvent e;
+        if (e.create(hipEventDefault)) return 1;
+        pool.push_back(std::move(e));
     }
     HIP_TRY(hipEventRecord(pool[c->n_ev[cls]++], s));
     return 0;
@@ -668,70 +681,50 @@ __global__ void k_collect_err(const AcDevState *__restrict__ state, int *__restr
     if (b < B) err[b] = state[b].error;
 }
 
-// ------------------------------------------------------------------------------------------------ host side
-template <class T>
-static int dmalloc(T **p, size_t n) {
-    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------ host leg of the coder (latency regime)
 // Pinned, host-coherent buffers + polled flags between the GPU and one host thread per image; see lic360_codec::coder_mode.
 #define HL_FB 16                               // flags: [0] tables of plane `seq` are in tab_h, [1] bitstreams of decode `gen` are in bytes_h, [2] abort,
 #define HL_MAXB 64                             //        [HL_FB + i] image i's symbols of plane `seq` are in sym_h
 #define HL_SPIN_LIMIT 2000000L                 // polls of a GPU-side wait before it gives up (~4 s: a host thread that lost its core on a busy box gets it back long before): a dead
                                                // host thread is an error, never a hang
+static inline int hl_ld(const int *p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
+static inline void hl_st(int *p, int v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
 struct HostLeg {
     int maxB = 0, tab_pitch = 0;
     long cap = 0, nsym = 0;
-    uint2 *rec_h = nullptr;                    // [maxB][nsym] (cdf[sym], cdf[sym + 1]) records of an encode
-    uint8_t *bytes_h = nullptr;                // [maxB][cap]
-    int *nbytes_h = nullptr, *err_h = nullptr;
-    unsigned short *tab_h = nullptr;           // [maxB][tab_pitch][8]: coded flag, T[1..7] of the current plane's symbols
-    float *sym_h = nullptr;                    // [maxB][tab_pitch]: decoded symbols of the current plane (-1: not coded)
-    int *flags = nullptr;
-    int *d_ctr = nullptr;                      // device: arrival counter of the table kernel's workgroups
+    PinnedBuf<uint2> rec_h;                    // [maxB][nsym] (cdf[sym], cdf[sym + 1]) records of an encode
+    PinnedBuf<uint8_t> bytes_h;                // [maxB][cap]
+    PinnedBuf<int> nbytes_h, err_h;
+    PinnedBuf<unsigned short> tab_h;           // [maxB][tab_pitch][8]: coded flag, T[1..7] of the current plane's symbols
+    PinnedBuf<float> sym_h;                    // [maxB][tab_pitch]: decoded symbols of the current plane (-1: not coded)
+    PinnedBuf<int> flags;
+    DevBuf<int> d_ctr;                         // device: arrival counter of the table kernel's workgroups
     int gen = 0;
     std::vector<std::thread> workers;
+    void join() {
+        for (std::thread &t : workers) if (t.joinable()) t.join();
+        workers.clear();
+    }
+    ~HostLeg() {
+        if (flags) hl_st(flags + 2, 1);                                   // release whoever still polls
+        join();
+        (void)hipDeviceSynchronize();
+    }
 };
-static inline int hl_ld(const int *p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
-static inline void hl_st(int *p, int v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
-static void hl_join(HostLeg *h) {
-    for (std::thread &t : h->workers) if (t.joinable()) t.join();
-    h->workers.clear();
-}
-static void hl_free(HostLeg *h) {
-    if (!h) return;
-    if (h->flags) hl_st(h->flags + 2, 1);                                 // release whoever still polls
-    hl_join(h);
-    (void)hipDeviceSynchronize();
-    (void)hipHostFree(h->rec_h); (void)hipHostFree(h->bytes_h); (void)hipHostFree(h->nbytes_h); (void)hipHostFree(h->err_h);
-    (void)hipHostFree(h->tab_h); (void)hipHostFree(h->sym_h); (void)hipHostFree(h->flags); (void)hipFree(h->d_ctr);
-    delete h;
-}
-template <class T>
-static int hl_alloc(T **p, size_t n) {
-    HIP_TRY(hipHostMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocMapped | hipHostMallocCoherent));
-    return 0;
-}
 // buffers for B images of nsym symbols, bitstream slots of cap bytes, planes of at most tab_pitch symbols (grown on demand; growing synchronises)
 static int hl_get(lic360_codec *c, int B, long cap, HostLeg **out) {
     ARG_CHECK(B > 0 && B <= HL_MAXB);
-    HostLeg *h = c->hl;
-    const long nsym = (long)c->G * c->HW;
-    if (h && (h->maxB < B || h->cap < cap)) { hl_free(h); h = c->hl = nullptr; }
-    if (!h) {
-        h = new HostLeg();
-        c->hl = h;
-        h->maxB = std::max(B, std::min(c->maxB, c->coder_auto_max)); h->cap = cap; h->nsym = nsym; h->tab_pitch = c->tab_pitch;
-        int rc = hl_alloc(&h->rec_h, (size_t)h->maxB * nsym) | hl_alloc(&h->bytes_h, (size_t)h->maxB * cap) | hl_alloc(&h->nbytes_h, h->maxB) |
-                 hl_alloc(&h->err_h, h->maxB) | hl_alloc(&h->tab_h, (size_t)h->maxB * h->tab_pitch * 8) | hl_alloc(&h->sym_h, (size_t)h->maxB * h->tab_pitch) |
-                 hl_alloc(&h->flags, HL_FB + HL_MAXB) | dmalloc(&h->d_ctr, 1);
-        if (rc) return 1;
+    if (!c->hl || c->hl->maxB < B || c->hl->cap < cap) {
+        std::unique_ptr<HostLeg> h(new HostLeg());
+        h->maxB = std::max(B, std::min(c->maxB, c->coder_auto_max)); h->cap = cap; h->nsym = (long)c->G * c->HW; h->tab_pitch = c->tab_pitch;
+        if (h->rec_h.alloc((size_t)h->maxB * h->nsym) || h->bytes_h.alloc((size_t)h->maxB * cap) || h->nbytes_h.alloc(h->maxB) || h->err_h.alloc(h->maxB) ||
+            h->tab_h.alloc((size_t)h->maxB * h->tab_pitch * 8) || h->sym_h.alloc((size_t)h->maxB * h->tab_pitch) || h->flags.alloc(HL_FB + HL_MAXB) ||
+            h->d_ctr.alloc(1)) return 1;
         memset(h->flags, 0, (HL_FB + HL_MAXB) * sizeof(int));
         HIP_TRY(hipMemset(h->d_ctr, 0, sizeof(int)));
+        c->hl = std::move(h);
     }
-    *out = h;
+    *out = c->hl.get();
     return 0;
 }
 
@@ -768,7 +761,9 @@ static int hl_encode(lic360_codec *c, hipStream_t s, int B, uint8_t *bytes, long
     if (hl_get(c, B, cap, &h)) return 1;
     const long n = (long)c->G * c->HW;
     HIP_TRY(hipMemcpyAsync(h->rec_h, c->e_rec, (size_t)B * n * sizeof(uint2), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipLaunchHostFunc(s, hl_encode_all, new HlEncJob{h, B, n, cap}));
+    std::unique_ptr<HlEncJob> job(new HlEncJob{h, B, n, cap});
+    HIP_TRY(hipLaunchHostFunc(s, hl_encode_all, job.get()));
+    job.release();                                                      // (hl_encode_all deletes it)
     HIP_TRY(hipMemcpy2DAsync(bytes, (size_t)cap, h->bytes_h, (size_t)h->cap, (size_t)cap, (size_t)B, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(nbytes, h->nbytes_h, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(err, h->err_h, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
@@ -901,18 +896,13 @@ static void hl_decode_worker(HostLeg *h, int i, long cap, int gen, std::vector<i
 
 LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic360_codec **out) {
     ARG_CHECK(out && ngroup > 0 && ngroup < 128 && h > 0 && w > 0 && h < 4096 && w < 4096 && max_batch > 0);
-    lic360_codec *c = new lic360_codec();
-    memset(c->layer_set, 0, sizeof(c->layer_set));
+    std::unique_ptr<lic360_codec> c(new lic360_codec());
     c->G = ngroup; c->H = h; c->W = w; c->maxB = max_batch; c->S = h + w - 1; c->P = h + w + ngroup - 2; c->HW = h * w;
-    for (int i = 0; i < 12; ++i) c->packed[i] = c->bias[i] = c->act[i] = c->packed4[i] = c->packed16[i] = nullptr;
-    int rc = 0;
-    rc |= lic360_conv_plan_create(ngroup * 1, ngroup, ngroup * 4, 5, 5, &c->plan[0]);
-    rc |= lic360_conv_plan_create(ngroup * 4, ngroup, ngroup * 4, 5, 6, &c->plan[1]);
-    rc |= lic360_conv_plan_create(ngroup * 4, ngroup, ngroup * 3, 5, 6, &c->plan[2]);
-    if (rc) return 1;
+    if (make_plan(c->plan[0], ngroup * 1, ngroup, ngroup * 4, 5, 5) || make_plan(c->plan[1], ngroup * 4, ngroup, ngroup * 4, 5, 6) ||
+        make_plan(c->plan[2], ngroup * 4, ngroup, ngroup * 3, 5, 6)) return 1;
     const char *force = getenv("LIC360_FUSED_CONV");                  // "16" forces the generic 16x16x4 kernels (the fall-back path, kept tested)
-    c->use4 = lic360_conv4_supported(c->plan[0]) && lic360_conv4_supported(c->plan[1]) && lic360_conv4_supported(c->plan[2]) &&
-              lic360_conv16_supported(c->plan[0]) && lic360_conv16_supported(c->plan[1]) && lic360_conv16_supported(c->plan[2]) &&
+    c->use4 = lic360_conv4_supported(c->plan[0].get()) && lic360_conv4_supported(c->plan[1].get()) && lic360_conv4_supported(c->plan[2].get()) &&
+              lic360_conv16_supported(c->plan[0].get()) && lic360_conv16_supported(c->plan[1].get()) && lic360_conv16_supported(c->plan[2].get()) &&
               !(force && force[0] == '1' && force[1] == '6');
     c->h_idx.resize(2 * (size_t)c->HW);
     c->h_pidx.resize(h + w);
@@ -927,10 +917,7 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     }
     c->h_plane_start[c->P] = acc;
     if (acc != ngroup * c->HW) { lic360_set_error("internal: plane schedule does not cover the latent"); return 1; }
-    rc |= dmalloc(&c->d_idx, c->h_idx.size());
-    rc |= dmalloc(&c->d_pidx, c->h_pidx.size());
-    rc |= dmalloc(&c->d_plane_start, c->h_plane_start.size());
-    if (rc) return 1;
+    if (c->d_idx.alloc(c->h_idx.size()) || c->d_pidx.alloc(c->h_pidx.size()) || c->d_plane_start.alloc(c->h_plane_start.size())) return 1;
     HIP_TRY(hipMemcpy(c->d_idx, c->h_idx.data(), c->h_idx.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_pidx, c->h_pidx.data(), c->h_pidx.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_plane_start, c->h_plane_start.data(), c->h_plane_start.size() * 4, hipMemcpyHostToDevice));
@@ -941,79 +928,57 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     // encode order: 16x16x4 MFMA kernels on zero-haloed NCHW planes, or plain NCHW for the generic kernels
     if (c->use4) { if (lic360_ec16_layout(h, w, &c->e_hp, &c->e_wp)) return 1; c->e_off = 2; }
     else { c->e_hp = h; c->e_wp = w; c->e_off = 0; }
-    rc |= dmalloc(&c->e_ctr, 8);
     const size_t EPL = (size_t)c->e_hp * c->e_wp;
-    rc |= dmalloc(&c->e_x0, B * G * EPL + TAIL);
-    for (int i = 0; i < 3; ++i) rc |= dmalloc(&c->e_buf[i], 3 * B * 4 * G * EPL + TAIL);
-    rc |= dmalloc(&c->e_rec, B * G * HW);
-    rc |= dmalloc(&c->d_x0, B * G * SK + TAIL);
-    for (int i = 0; i < 11; ++i) rc |= dmalloc(&c->d_act[i], 3 * B * 4 * G * SK + TAIL);
-    rc |= dmalloc(&c->d_y, 3 * B * 3 * G * SK + TAIL);
-    rc |= dmalloc(&c->d_state, B);
+    if (c->e_ctr.alloc(8) || c->e_x0.alloc(B * G * EPL + TAIL)) return 1;
+    for (DevBuf<float> &b : c->e_buf) if (b.alloc(3 * B * 4 * G * EPL + TAIL)) return 1;
+    if (c->e_rec.alloc(B * G * HW) || c->d_x0.alloc(B * G * SK + TAIL)) return 1;
+    for (DevBuf<float> &b : c->d_act) if (b.alloc(3 * B * 4 * G * SK + TAIL)) return 1;
+    if (c->d_y.alloc(3 * B * 3 * G * SK + TAIL) || c->d_state.alloc(B)) return 1;
     for (int p = 0; p < c->P; ++p) c->tab_pitch = std::max(c->tab_pitch, c->h_plane_start[p + 1] - c->h_plane_start[p]);
     c->tab_pitch = (c->tab_pitch + 63) / 64 * 64;
-    rc |= dmalloc(&c->d_tab, 2 * B * (size_t)c->tab_pitch);                 // two uint4 per symbol (dec_pack8)
+    if (c->d_tab.alloc(2 * B * (size_t)c->tab_pitch)) return 1;                 // two uint4 per symbol (dec_pack8)
     if (const char *hc = getenv("LIC360_HOST_CODER")) c->coder_mode = hc[0] == '0' ? 0 : (hc[0] == '1' ? 1 : 2);
     c->skip = c->use4 && !getenv("LIC360_NOSKIP");
     if (c->skip) {
         const size_t S = c->S, nt = (size_t)((h + 3) / 4) * ((w + 15) / 16);
-        rc |= dmalloc(&c->need, B * NEED_LAYERS * HW);
-        rc |= dmalloc(&c->need_d, B * NEED_LAYERS * S * h);
-        rc |= dmalloc(&c->tmax, B * NEED_LAYERS * nt);
-        rc |= dmalloc(&c->stats, 2 * NEED_LAYERS * NEED_STAT_G);
+        if (c->need.alloc(B * NEED_LAYERS * HW) || c->need_d.alloc(B * NEED_LAYERS * S * h) || c->tmax.alloc(B * NEED_LAYERS * nt) ||
+            c->stats.alloc(2 * NEED_LAYERS * NEED_STAT_G)) return 1;
         c->ecl.cap = (int)(((3 * B + 7) / 8) * ((nt + 3) / 4) * ((G + 3) / 4));          // tasks of an XCD's list, hidden layers (the fused layer's is shorter)
         const size_t cap11 = ((B + 7) / 8) * ((nt + 1) / 2) * ((G + 4) / 5);
         if ((size_t)c->ecl.cap < cap11) c->ecl.cap = (int)cap11;
-        rc |= dmalloc(&c->ecl.list, (size_t)NEED_LAYERS * 8 * c->ecl.cap);
-        rc |= dmalloc(&c->ecl.cnt, (size_t)NEED_LAYERS * 8);
+        if (c->ecl_list.alloc((size_t)NEED_LAYERS * 8 * c->ecl.cap) || c->ecl_cnt.alloc((size_t)NEED_LAYERS * 8)) return 1;
+        c->ecl.list = c->ecl_list; c->ecl.cnt = c->ecl_cnt;
         if (h <= 64 && max_batch % 8 == 0 && max_batch >= 16 && max_batch <= 512 && ngroup <= 72) {
             c->dcl.P = c->P;
             c->dcl.cap = (int)(((G + 2) / 3) * 3 * (B / 8));
-            rc |= dmalloc(&c->dcl.list, (size_t)NEED_LAYERS * c->P * 8 * c->dcl.cap);
-            rc |= dmalloc(&c->dcl.cnt, (size_t)NEED_LAYERS * c->P * 8);
+            if (c->dcl_list.alloc((size_t)NEED_LAYERS * c->P * 8 * c->dcl.cap) || c->dcl_cnt.alloc((size_t)NEED_LAYERS * c->P * 8)) return 1;
+            c->dcl.list = c->dcl_list; c->dcl.cnt = c->dcl_cnt;
         }
-        if (rc) return 1;
         HIP_TRY(hipMemset(c->stats, 0, 2 * NEED_LAYERS * NEED_STAT_G * sizeof(unsigned long long)));
     }
-    if (rc) return 1;
     // decode activations are only ever read where already written or with a zero weight; they must be finite
     HIP_TRY(hipMemset(c->e_x0, 0, (B * G * EPL + TAIL) * 4));
     for (int i = 0; i < 3; ++i) HIP_TRY(hipMemset(c->e_buf[i], 0, (3 * B * 4 * G * EPL + TAIL) * 4));
     HIP_TRY(hipMemset(c->d_x0, 0, (B * G * SK + TAIL) * 4));
     for (int i = 0; i < 11; ++i) HIP_TRY(hipMemset(c->d_act[i], 0, (3 * B * 4 * G * SK + TAIL) * 4));
     HIP_TRY(hipMemset(c->d_y, 0, (3 * B * 3 * G * SK + TAIL) * 4));
-    *out = c;
+    *out = c.release();
     return 0;
 }
 
-LIC360_API void lic360_codec_destroy(lic360_codec *c) {
-    if (!c) return;
-    hl_free(c->hl);
-    for (int i = 0; i < 3; ++i) lic360_conv_plan_destroy(c->plan[i]);
-    for (int i = 0; i < 12; ++i) { (void)hipFree(c->packed[i]); (void)hipFree(c->bias[i]); (void)hipFree(c->act[i]); (void)hipFree(c->packed4[i]); }
-    (void)hipFree(c->d_idx); (void)hipFree(c->d_pidx); (void)hipFree(c->d_plane_start);
-    (void)hipFree(c->e_x0); for (int i = 0; i < 3; ++i) (void)hipFree(c->e_buf[i]);
-    (void)hipFree(c->e_rec); (void)hipFree(c->d_x0); for (int i = 0; i < 11; ++i) (void)hipFree(c->d_act[i]);
-    (void)hipFree(c->d_y); (void)hipFree(c->d_state); (void)hipFree(c->d_tab); (void)hipFree(c->e_ctr);
-    (void)hipFree(c->need); (void)hipFree(c->need_d); (void)hipFree(c->tmax); (void)hipFree(c->stats);
-    (void)hipFree(c->ecl.list); (void)hipFree(c->ecl.cnt); (void)hipFree(c->dcl.list); (void)hipFree(c->dcl.cnt);
-    for (int i = 0; i < 12; ++i) (void)hipFree(c->packed16[i]);
-    for (int k = 0; k < PROF_NCLS; ++k)
-        for (hipEvent_t e : c->ev[k]) (void)hipEventDestroy(e);
-    delete c;
-}
+LIC360_API void lic360_codec_destroy(lic360_codec *c) { delete c; }
 
 LIC360_API int lic360_codec_set_layer(void *stream, lic360_codec *c, int layer, const float *weight, const float *bias, const float *act) {
     ARG_CHECK(c && layer >= 0 && layer < 12 && weight && bias);
     ARG_CHECK((act != nullptr) == (layer != 11));
-    lic360_conv_plan *p = c->plan[plan_of(layer)];
+    lic360_conv_plan *p = c->plan[plan_of(layer)].get();
     long nper = lic360_conv_plan_packed_floats(p);
-    if (!c->packed[layer]) {
-        if (dmalloc(&c->packed[layer], 3 * (size_t)nper)) return 1;
-        if (dmalloc(&c->bias[layer], 3 * (size_t)p->nout)) return 1;
-        if (act && dmalloc(&c->act[layer], 3 * (size_t)p->nout)) return 1;
-        if (c->use4 && dmalloc(&c->packed4[layer], 3 * (size_t)lic360_conv4_packed_floats(p))) return 1;
-        if (c->use4 && dmalloc(&c->packed16[layer], 3 * (size_t)lic360_conv16_packed_floats(p))) return 1;
+    if (!c->packed[layer]) {                                            // (all of the layer's buffers, or none)
+        DevBuf<float> pk, bs, ac, pk4, pk16;
+        if (pk.alloc(3 * (size_t)nper) || bs.alloc(3 * (size_t)p->nout) || (act && ac.alloc(3 * (size_t)p->nout)) ||
+            (c->use4 && (pk4.alloc(3 * (size_t)lic360_conv4_packed_floats(p)) || pk16.alloc(3 * (size_t)lic360_conv16_packed_floats(p))))) return 1;
+        c->packed[layer] = std::move(pk); c->bias[layer] = std::move(bs); c->act[layer] = std::move(ac);
+        c->packed4[layer] = std::move(pk4); c->packed16[layer] = std::move(pk16);
     }
     if (lic360_conv_pack(stream, p, weight, 3, c->packed[layer])) return 1;
     if (c->use4 && lic360_conv4_pack(stream, p, weight, 3, c->packed4[layer])) return 1;
@@ -1058,7 +1023,7 @@ LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *c
         if (lic360_ec_lists_build(stream, c->tmax, B, G, H, W, c->ecl, c->stats_on ? c->stats : nullptr)) return 1;
     }
     auto ec = [&](int layer, const float *xin, const float *res, float *dst, int x_mod) -> int {
-        lic360_conv_plan *p = c->plan[plan_of(layer)];
+        lic360_conv_plan *p = c->plan[plan_of(layer)].get();
         if (c->use4 && c->skip && layer > 0)
             return lic360_cconv16_ec_list(stream, p, xin, c->packed16[layer], c->bias[layer], c->act[layer], res, dst, 3 * B, H, W, 3, x_mod, c->e_ctr,
                                           c->ecl.list + (size_t)layer * 8 * c->ecl.cap, c->ecl.cnt + layer * 8, c->ecl.cap);
@@ -1079,10 +1044,10 @@ LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *c
         if (c->skip) {
             // a skipped (tile, group block) holds masked symbols only: their records are (0, 0) and nobody writes them
             HIP_TRY(hipMemsetAsync(c->e_rec, 0, (size_t)B * G * c->HW * sizeof(uint2), s));
-            PROF(c, PROF_EC_LAST, s, rc |= lic360_cconv16_ec_tables_list(stream, c->plan[2], cur, c->packed16[11], c->bias[11], code, mask, c->d_pidx, c->d_plane_start,
+            PROF(c, PROF_EC_LAST, s, rc |= lic360_cconv16_ec_tables_list(stream, c->plan[2].get(), cur, c->packed16[11], c->bias[11], code, mask, c->d_pidx, c->d_plane_start,
                                                                          c->e_rec, B, H, W, c->e_ctr, c->ecl.list + (size_t)11 * 8 * c->ecl.cap, c->ecl.cnt + 11 * 8, c->ecl.cap));
         } else
-        PROF(c, PROF_EC_LAST, s, rc |= lic360_cconv16_ec_tables(stream, c->plan[2], cur, c->packed16[11], c->bias[11], code, mask, c->d_pidx,
+        PROF(c, PROF_EC_LAST, s, rc |= lic360_cconv16_ec_tables(stream, c->plan[2].get(), cur, c->packed16[11], c->bias[11], code, mask, c->d_pidx,
                                                                 c->d_plane_start, c->e_rec, B, H, W, c->e_ctr));
         if (rc) return 1;
         if (coder_on_host(c, B)) {
@@ -1108,7 +1073,7 @@ LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *c
 }
 
 static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes, long cap, const int *nbytes,
-                             const float *mask, int B, float *code_out, int *err, void *const *gate, int n_gate, int gate_stride) {
+                             const float *mask, int B, float *code_out, int *err, const HipEvent *gate, int n_gate, int gate_stride) {
     if (check_ready(c, B)) return 2;
     ARG_CHECK(bytes && nbytes && mask && code_out && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0);
     hipStream_t s = (hipStream_t)stream;
@@ -1117,11 +1082,17 @@ static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes
     // the serial decoder: one wave per image on the GPU, or one host thread per image fed through pinned memory (few images per call)
     const bool host = coder_on_host(c, B);
     HostLeg *h = nullptr;
+    // Once the workers start, every return that is not the successful end aborts and joins them: they would wait for tables that never come,
+    // and the next decode would block joining them.  On success they outlive the call and the next decode joins them.
+    struct WorkerRelease {
+        HostLeg *h = nullptr;
+        ~WorkerRelease() { if (h) { hl_st(h->flags + 2, 1); h->join(); } }
+    } release;
     int seq0 = 0;
     if (host) {
         ARG_CHECK(c->P < (1 << 13));
         if (hl_get(c, B, cap, &h)) return 1;
-        hl_join(h);                                                     // the previous decode's threads end with its last plane
+        h->join();                                                      // the previous decode's threads end with its last plane
         if (hl_ld(h->flags + 2) || h->gen >= (1 << 17)) {               // an aborted decode, or the sequence numbers run out: nothing polls after a synchronisation
             HIP_TRY(hipDeviceSynchronize());
             memset(h->flags, 0, (HL_FB + HL_MAXB) * sizeof(int));
@@ -1135,11 +1106,10 @@ static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes
         LAUNCH_CHECK();
         std::vector<int> lens(c->P);
         for (int p = 0; p < c->P; ++p) { int st0, ln; lic360_plane_window(p, G, H, W, pih, &st0, &ln); lens[p] = ln; }
+        release.h = h;
         try {
             for (int i = 0; i < B; ++i) h->workers.emplace_back(hl_decode_worker, h, i, cap, gen, lens);
-        } catch (...) {                                                 // (thread creation failed: release the ones that started, report)
-            hl_st(h->flags + 2, 1);
-            hl_join(h);
+        } catch (...) {                                                 // (thread creation failed: the ones that started are released on return)
             lic360_set_error("host leg of the coder: cannot start %d decode threads (lic360_codec_set_coder(codec, 0) keeps the coder on the GPU)", B);
             return 1;
         }
@@ -1150,12 +1120,12 @@ static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes
     // dead-cone skip: the whole mask must be final before the first plane (a gated decode waits for the map's LAST event instead of plane by plane)
     const bool lists = c->skip && c->dcl.list && B % 8 == 0 && B >= 16;
     if (lists) {
-        if (gate) { HIP_TRY(hipStreamWaitEvent(s, (hipEvent_t)gate[n_gate - 1], 0)); gate = nullptr; }
+        if (gate) { HIP_TRY(hipStreamWaitEvent(s, gate[n_gate - 1], 0)); gate = nullptr; }
         if (lic360_need_build(stream, mask, B, G, H, W, c->need, c->need_d, c->tmax)) return 1;
         if (lic360_dc_lists_build(stream, c->need_d, B, G, H, W, c->dcl, c->stats_on ? c->stats + NEED_LAYERS * NEED_STAT_G : nullptr)) return 1;
     }
     auto dc = [&](int layer, const float *xin, const float *res, float *dst, int x_mod, int p) -> int {
-        lic360_conv_plan *pl = c->plan[plan_of(layer)];
+        lic360_conv_plan *pl = c->plan[plan_of(layer)].get();
         if (lists && layer > 0) {
             const size_t li = ((size_t)layer * c->P + p) * 8;
             return lic360_cconv4_dc_plane_list(stream, pl, xin, c->packed4[layer], c->bias[layer], c->act[layer], res, dst, 3 * B, H, W, 3, p, x_mod,
@@ -1183,12 +1153,12 @@ static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes
         if (len <= 0) continue;
         if (gate) {                                                     // the mask of this plane's positions: map planes <= p / stride (see lic360_impcodec_decode_masked)
             const int q = std::min(n_gate - 1, p / gate_stride);
-            if (q != gate_q) { HIP_TRY(hipStreamWaitEvent(s, (hipEvent_t)gate[q], 0)); gate_q = q; }
+            if (q != gate_q) { HIP_TRY(hipStreamWaitEvent(s, gate[q], 0)); gate_q = q; }
         }
         if (host) {
             const int nblk = (len + 63) / 64 * B;
             PROF(c, PROF_DEC_TABLES, s, hipLaunchKernelGGL(k_dec_tables_host, dim3((len + 63) / 64, B), dim3(64), 0, s, DecTablesHostArgs{c->d_y, mask, c->d_idx, start, len, p,
-                                                           (uint4 *)h->tab_h, h->tab_pitch, B, G, H, W, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0, h->d_ctr, h->flags, seq0 + p + 1, nblk}));
+                                                           (uint4 *)(unsigned short *)h->tab_h, h->tab_pitch, B, G, H, W, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0, h->d_ctr, h->flags, seq0 + p + 1, nblk}));
             LAUNCH_CHECK();
             PROF(c, PROF_DEC_PLANE, s, hipLaunchKernelGGL(k_dec_wait_scatter, dim3(1), dim3(1024), 0, s, DecWaitArgs{h->flags, h->sym_h, seq0 + p + 1, B, h->tab_pitch, c->d_idx, start, len, p,
                                                           c->d_x0, code_out, G, H, W, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0}));
@@ -1206,6 +1176,7 @@ static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes
     if (host) hipLaunchKernelGGL(k_hl_err, dim3((B + 63) / 64), dim3(64), 0, s, h->err_h, h->flags, err, B);
     else hipLaunchKernelGGL(k_collect_err, dim3((B + 63) / 64), dim3(64), 0, s, c->d_state, err, B);
     LAUNCH_CHECK();
+    release.h = nullptr;                                                // (enqueued: the workers run on with the planes)
     return 0;
 }
 LIC360_API int lic360_codec_decode(void *stream, lic360_codec *c, const uint8_t *bytes, long cap, const int *nbytes,
@@ -1220,29 +1191,29 @@ LIC360_API int lic360_codec_decode(void *stream, lic360_codec *c, const uint8_t 
 struct lic360_impcodec {
     int H, W, HW, P, cpg, nsym, maxB;
     float sc;
-    lic360_conv_plan *plan[3];
-    float *packed[12], *bias[12], *act[12];
-    bool layer_set[12];
+    PlanPtr plan[3];
+    DevBuf<float> packed[12], bias[12], act[12];
+    bool layer_set[12] = {};
     std::vector<int> h_idx, h_pidx;
-    int *d_idx, *d_pidx;
-    float *e_x0, *e_buf[3];
-    uint2 *e_rec;
-    float *d_x0, *d_act[11], *d_y;
+    DevBuf<int> d_idx, d_pidx;
+    DevBuf<float> e_x0, e_buf[3];
+    DevBuf<uint2> e_rec;
+    DevBuf<float> d_x0, d_act[11], d_y;
     // leaf-resident 16x16x4 kernels for the 144-channel layers (csrc/cconv144_kernels.hip): encode on zero-haloed NCHW planes,
     // decode on zero-padded diagonal-major planes [rows = sk_rows][sk_pitch], cell (th, tw) at (th + tw + sk_row0, th + sk_col0)
     bool use144 = false;
-    float *packed144[12];
+    DevBuf<float> packed144[12];
     int e_hp = 0, e_wp = 0;
-    float *e_pad[3] = {nullptr, nullptr, nullptr}, *e_plain = nullptr;
+    DevBuf<float> e_pad[3], e_plain;
     int sk_rows, sk_pitch, sk_row0, sk_col0;
-    int *d_tab;                                 // [maxB][tab_pitch][IMP_TW] tables of the current plane
+    DevBuf<int> d_tab;                          // [maxB][tab_pitch][IMP_TW] tables of the current plane
     int tab_pitch;
-    AcDevState *d_state;
+    DevBuf<AcDevState> d_state;
     // lic360_impcodec_decode_masked: one event per plane ("the latent mask of every map cell of planes <= p is final").  The events are
     // re-recorded by every masked decode and hipStreamWaitEvent latches whichever record came last, so a gated latent decode is only
     // valid when it is enqueued AFTER the masked decode of the same step: decode_masked bumps gate_gen and arms the gate, decode_gated
     // must present that generation and consumes it (a stale, reused or out-of-order gate is an error, not a silent wrong mask).
-    std::vector<hipEvent_t> plane_ev;
+    std::vector<HipEvent> plane_ev;
     long gate_gen = 0;
     bool gate_armed = false;
     int gate_stride = 0, gate_B = 0;           // gate_B: the batch whose mask rows the armed masked decode fills
@@ -1428,79 +1399,53 @@ __global__ __launch_bounds__(64) void k_imp_dec_plane(const ImpDecPlaneArgs a) {
 
 LIC360_API int lic360_impcodec_create(int h, int w, int hidden_channels, int nsym, int max_batch, lic360_impcodec **out) {
     ARG_CHECK(out && h > 0 && w > 0 && h < 4096 && w < 4096 && hidden_channels > 0 && nsym >= 3 && nsym < IMP_TW && max_batch > 0);
-    lic360_impcodec *c = new lic360_impcodec();
-    memset(c->layer_set, 0, sizeof(c->layer_set));
+    std::unique_ptr<lic360_impcodec> c(new lic360_impcodec());
     c->H = h; c->W = w; c->HW = h * w; c->P = h + w - 1; c->cpg = hidden_channels; c->nsym = nsym; c->maxB = max_batch;
     c->sc = 2.0f / (float)(nsym - 2);
-    for (int i = 0; i < 12; ++i) c->packed[i] = c->bias[i] = c->act[i] = c->packed144[i] = nullptr;
-    int rc = 0;
-    rc |= lic360_conv_plan_create(1, 1, hidden_channels, 5, 5, &c->plan[0]);
-    rc |= lic360_conv_plan_create(hidden_channels, 1, hidden_channels, 5, 6, &c->plan[1]);
-    rc |= lic360_conv_plan_create(hidden_channels, 1, nsym, 5, 6, &c->plan[2]);
-    if (rc) return 1;
+    if (make_plan(c->plan[0], 1, 1, hidden_channels, 5, 5) || make_plan(c->plan[1], hidden_channels, 1, hidden_channels, 5, 6) ||
+        make_plan(c->plan[2], hidden_channels, 1, nsym, 5, 6)) return 1;
     c->h_idx.resize(2 * (size_t)c->HW);
     c->h_pidx.resize(h + w);
     lic360_code_contex(h, w, c->h_idx.data(), c->h_pidx.data());
     c->tab_pitch = ((h < w ? h : w) + 63) / 64 * 64;
     const size_t B = max_batch, HW = c->HW, C = hidden_channels, CE = hidden_channels > nsym ? hidden_channels : nsym;   // the last layer writes nsym planes
-    rc |= dmalloc(&c->d_idx, c->h_idx.size());
-    rc |= dmalloc(&c->d_pidx, c->h_pidx.size());
-    rc |= dmalloc(&c->e_x0, B * HW);
-    for (int i = 0; i < 3; ++i) rc |= dmalloc(&c->e_buf[i], B * CE * HW);
-    rc |= dmalloc(&c->e_rec, B * HW);
+    if (c->d_idx.alloc(c->h_idx.size()) || c->d_pidx.alloc(c->h_pidx.size()) || c->e_x0.alloc(B * HW)) return 1;
+    for (DevBuf<float> &b : c->e_buf) if (b.alloc(B * CE * HW)) return 1;
+    if (c->e_rec.alloc(B * HW)) return 1;
     // 144-channel layers on the leaf-resident 16x16x4 kernels (other widths keep the generic kernels)
-    c->use144 = lic360_conv144_supported(c->plan[1]) && lic360_conv144_supported(c->plan[2]);
+    c->use144 = lic360_conv144_supported(c->plan[1].get()) && lic360_conv144_supported(c->plan[2].get());
     if (c->use144) {
         if (lic360_ec144_layout(h, w, &c->e_hp, &c->e_wp) || lic360_dc144_layout(h, w, &c->sk_rows, &c->sk_pitch)) return 1;
         c->sk_row0 = 4; c->sk_col0 = 2;
-        for (int i = 0; i < 3; ++i) rc |= dmalloc(&c->e_pad[i], B * C * (size_t)c->e_hp * c->e_wp);
-        rc |= dmalloc(&c->e_plain, B * CE * HW);
-        if (rc) return 1;
+        for (DevBuf<float> &b : c->e_pad) if (b.alloc(B * C * (size_t)c->e_hp * c->e_wp)) return 1;
+        if (c->e_plain.alloc(B * CE * HW)) return 1;
         for (int i = 0; i < 3; ++i) HIP_TRY(hipMemset(c->e_pad[i], 0, B * C * (size_t)c->e_hp * c->e_wp * 4));   // the halo stays zero
     } else { c->sk_rows = h + w - 1; c->sk_pitch = h; c->sk_row0 = 0; c->sk_col0 = 0; }
     const size_t SK = (size_t)c->sk_rows * c->sk_pitch;                   // diagonal-major decode planes
-    rc |= dmalloc(&c->d_x0, B * SK);
-    for (int i = 0; i < 11; ++i) rc |= dmalloc(&c->d_act[i], B * C * SK);
-    rc |= dmalloc(&c->d_y, B * (size_t)nsym * SK);
-    rc |= dmalloc(&c->d_tab, B * (size_t)c->tab_pitch * IMP_TW);
-    rc |= dmalloc(&c->d_state, B);
-    if (rc) return 1;
+    if (c->d_x0.alloc(B * SK)) return 1;
+    for (DevBuf<float> &b : c->d_act) if (b.alloc(B * C * SK)) return 1;
+    if (c->d_y.alloc(B * (size_t)nsym * SK) || c->d_tab.alloc(B * (size_t)c->tab_pitch * IMP_TW) || c->d_state.alloc(B)) return 1;
     HIP_TRY(hipMemcpy(c->d_idx, c->h_idx.data(), c->h_idx.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_pidx, c->h_pidx.data(), c->h_pidx.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(c->d_x0, 0, B * SK * 4));
     for (int i = 0; i < 11; ++i) HIP_TRY(hipMemset(c->d_act[i], 0, B * C * SK * 4));
     HIP_TRY(hipMemset(c->d_y, 0, B * (size_t)nsym * SK * 4));
-    *out = c;
+    *out = c.release();
     return 0;
 }
-LIC360_API void lic360_impcodec_destroy(lic360_impcodec *c) {
-    if (!c) return;
-    for (int i = 0; i < 3; ++i) lic360_conv_plan_destroy(c->plan[i]);
-    for (int i = 0; i < 12; ++i) { (void)hipFree(c->packed[i]); (void)hipFree(c->bias[i]); (void)hipFree(c->act[i]); (void)hipFree(c->packed144[i]); }
-    for (int i = 0; i < 3; ++i) (void)hipFree(c->e_pad[i]);
-    (void)hipFree(c->e_plain);
-    (void)hipFree(c->d_idx); (void)hipFree(c->d_pidx); (void)hipFree(c->e_x0);
-    for (int i = 0; i < 3; ++i) (void)hipFree(c->e_buf[i]);
-    (void)hipFree(c->e_rec); (void)hipFree(c->d_x0);
-    for (int i = 0; i < 11; ++i) (void)hipFree(c->d_act[i]);
-    (void)hipFree(c->d_y); (void)hipFree(c->d_tab); (void)hipFree(c->d_state);
-    for (hipEvent_t e : c->plane_ev) (void)hipEventDestroy(e);
-    delete c;
-}
+LIC360_API void lic360_impcodec_destroy(lic360_impcodec *c) { delete c; }
 LIC360_API int lic360_impcodec_set_layer(void *stream, lic360_impcodec *c, int layer, const float *weight, const float *bias, const float *act) {
     ARG_CHECK(c && layer >= 0 && layer < 12 && weight && bias);
     ARG_CHECK((act != nullptr) == (layer != 11));
-    lic360_conv_plan *p = c->plan[plan_of(layer)];
-    if (!c->packed[layer]) {
-        if (dmalloc(&c->packed[layer], (size_t)lic360_conv_plan_packed_floats(p))) return 1;
-        if (dmalloc(&c->bias[layer], (size_t)p->nout)) return 1;
-        if (act && dmalloc(&c->act[layer], (size_t)p->nout)) return 1;
+    lic360_conv_plan *p = c->plan[plan_of(layer)].get();
+    if (!c->packed[layer]) {                                            // (all of the layer's buffers, or none)
+        DevBuf<float> pk, bs, ac, pk144;
+        if (pk.alloc((size_t)lic360_conv_plan_packed_floats(p)) || bs.alloc((size_t)p->nout) || (act && ac.alloc((size_t)p->nout)) ||
+            (c->use144 && layer > 0 && pk144.alloc((size_t)lic360_conv144_packed_floats(p)))) return 1;
+        c->packed[layer] = std::move(pk); c->bias[layer] = std::move(bs); c->act[layer] = std::move(ac); c->packed144[layer] = std::move(pk144);
     }
     if (lic360_conv_pack(stream, p, weight, 1, c->packed[layer])) return 1;
-    if (c->use144 && layer > 0) {
-        if (!c->packed144[layer] && dmalloc(&c->packed144[layer], (size_t)lic360_conv144_packed_floats(p))) return 1;
-        if (lic360_conv144_pack(stream, p, weight, c->packed144[layer])) return 1;
-    }
+    if (c->use144 && layer > 0 && lic360_conv144_pack(stream, p, weight, c->packed144[layer])) return 1;
     HIP_TRY(hipMemcpyAsync(c->bias[layer], bias, (size_t)p->nout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (act) HIP_TRY(hipMemcpyAsync(c->act[layer], act, (size_t)p->nout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     c->layer_set[layer] = true;
@@ -1524,19 +1469,19 @@ LIC360_API int lic360_impcodec_encode(void *stream, lic360_impcodec *c, const fl
         // layer 0 (1 -> 144) on the generic kernel into plain NCHW, copied into the zero-haloed planes; layers 1..10 haloed -> haloed;
         // layer 11 (144 -> nsym) haloed -> plain NCHW for the table kernel
         const long PLh = (long)c->e_hp * c->e_wp;
-        if (lic360_cconv_ec_ex(stream, c->plan[0], c->e_x0, c->packed[0], c->bias[0], c->act[0], nullptr, c->e_plain, B, H, W, 1, B)) return 1;
+        if (lic360_cconv_ec_ex(stream, c->plan[0].get(), c->e_x0, c->packed[0], c->bias[0], c->act[0], nullptr, c->e_plain, B, H, W, 1, B)) return 1;
         hipLaunchKernelGGL(k_imp_halo, dim3(lic360_blocks((long)B * c->cpg * c->HW, 4)), dim3(256), 0, s, c->e_plain, c->e_pad[0], (long)B * c->cpg * c->HW, H, W, c->e_hp, c->e_wp);
         LAUNCH_CHECK();
         float *cur = c->e_pad[0], *t1 = c->e_pad[1], *nxt = c->e_pad[2];
         auto ec = [&](int layer, const float *xin, const float *res, float *dst) -> int {
-            return lic360_cconv144_ec(stream, c->plan[1], xin, c->packed144[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, PLh, c->e_wp, 2);
+            return lic360_cconv144_ec(stream, c->plan[1].get(), xin, c->packed144[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, PLh, c->e_wp, 2);
         };
         for (int blk = 0; blk < 5; ++blk) {
             if (ec(1 + 2 * blk, cur, nullptr, t1)) return 1;
             if (ec(2 + 2 * blk, t1, cur, nxt)) return 1;
             float *tmp = cur; cur = nxt; nxt = tmp;
         }
-        if (lic360_cconv144_ec(stream, c->plan[2], cur, c->packed144[11], c->bias[11], nullptr, nullptr, c->e_plain, B, H, W, (long)c->HW, W, 0)) return 1;
+        if (lic360_cconv144_ec(stream, c->plan[2].get(), cur, c->packed144[11], c->bias[11], nullptr, nullptr, c->e_plain, B, H, W, (long)c->HW, W, 0)) return 1;
         if (c->nsym == IMP_NSYM_FAST) hipLaunchKernelGGL(k_imp_enc_tables<true>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, c->e_plain, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
         else hipLaunchKernelGGL(k_imp_enc_tables<false>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, c->e_plain, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
         LAUNCH_CHECK();
@@ -1546,7 +1491,7 @@ LIC360_API int lic360_impcodec_encode(void *stream, lic360_impcodec *c, const fl
     }
     float *cur = c->e_buf[0], *t1 = c->e_buf[1], *nxt = c->e_buf[2];
     auto ec = [&](int layer, const float *xin, const float *res, float *dst) -> int {
-        return lic360_cconv_ec_ex(stream, c->plan[plan_of(layer)], xin, c->packed[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, 1, B);
+        return lic360_cconv_ec_ex(stream, c->plan[plan_of(layer)].get(), xin, c->packed[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, 1, B);
     };
     if (ec(0, c->e_x0, nullptr, cur)) return 1;
     for (int blk = 0; blk < 5; ++blk) {
@@ -1615,9 +1560,9 @@ static int impcodec_decode_impl(void *stream, lic360_impcodec *c, const uint8_t 
     const long SK = (long)c->sk_rows * c->sk_pitch, off0 = (long)c->sk_row0 * c->sk_pitch + c->sk_col0;
     auto dc = [&](int layer, const float *xin, const float *res, float *dst, int p) -> int {
         if (c->use144 && layer > 0)
-            return lic360_cconv144_dc_plane(stream, c->plan[plan_of(layer)], xin, c->packed144[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, p);
+            return lic360_cconv144_dc_plane(stream, c->plan[plan_of(layer)].get(), xin, c->packed144[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, p);
         // generic kernel on the diagonal-major planes: cell (th, tw) at th * (pitch + 1) + tw * pitch from the layout's origin
-        return lic360_cconv_dc_plane_strided(stream, c->plan[plan_of(layer)], xin + off0, c->packed[layer], c->bias[layer], c->act[layer],
+        return lic360_cconv_dc_plane_strided(stream, c->plan[plan_of(layer)].get(), xin + off0, c->packed[layer], c->bias[layer], c->act[layer],
                                              res ? res + off0 : nullptr, dst + off0, B, H, W, 1, c->d_idx, c->d_pidx, pih, p, B,
                                              SK, c->sk_pitch + 1, c->sk_pitch, SK, c->sk_pitch + 1, c->sk_pitch);
     };
@@ -1671,9 +1616,9 @@ LIC360_API int lic360_impcodec_decode_masked(void *stream, lic360_impcodec *c, c
     ARG_CHECK(c && mask_out && generation_out && mask_c > 0 && stride > 0 && mask_c % (stride * stride) == 0 && c->nsym > 1 &&
               mask_c % (c->nsym - 1) == 0 && B > 0 && B <= c->maxB);
     while ((int)c->plane_ev.size() < c->P) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));   // (same-device consumers only: no system-scope cache writeback per plane)
-        c->plane_ev.push_back(e);
+        HipEvent e;
+        if (e.create(hipEventDisableTiming | hipEventDisableSystemFence)) return 1;   // (same-device consumers only: no system-scope cache writeback per plane)
+        c->plane_ev.push_back(std::move(e));
     }
     const int rc = impcodec_decode_impl(stream, c, bytes, cap, nbytes, B, levels_out, err, mask_out, mask_c, stride);
     c->gate_armed = rc == 0;                                            // (a failed enqueue arms nothing)
@@ -1710,7 +1655,7 @@ LIC360_API int lic360_codec_decode_gated(void *stream, lic360_codec *c, const ui
     if (check_ready(c, B)) return 2;
     ARG_CHECK(bytes && nbytes && mask && code_out && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0);
     map_codec->gate_armed = false;
-    return codec_decode_impl(stream, c, bytes, cap, nbytes, mask, B, code_out, err, (void *const *)map_codec->plane_ev.data(), map_codec->P,
+    return codec_decode_impl(stream, c, bytes, cap, nbytes, mask, B, code_out, err, map_codec->plane_ev.data(), map_codec->P,
                              map_codec->gate_stride);
 }
 
@@ -1756,8 +1701,8 @@ LIC360_API int lic360_devcoder_encode(void *stream, const int *tables, int ncode
     ARG_CHECK(ncode >= 1 && n >= 0 && bytes && nbytes && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0 &&
               (n == 0 || (tables && labels)));
     hipStream_t s = (hipStream_t)stream;
-    uint2 *rec = nullptr;
-    if (dmalloc(&rec, (size_t)n)) return 1;
+    DevBuf<uint2> rec;
+    if (rec.alloc((size_t)n)) return 1;
     if (n) {
         hipLaunchKernelGGL(k_test_records, dim3(lic360_blocks(n, 1)), dim3(256), 0, s, tables, ncode, labels, mask, n, rec);
         LAUNCH_CHECK();
@@ -1765,7 +1710,6 @@ LIC360_API int lic360_devcoder_encode(void *stream, const int *tables, int ncode
     hipLaunchKernelGGL(k_ac_encode, dim3(1), dim3(128), 0, s, rec, n, bytes, cap, nbytes, err);
     LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize(s));
-    (void)hipFree(rec);
     return 0;
 }
 
@@ -1777,10 +1721,10 @@ LIC360_API int lic360_devcoder_decode(void *stream, const int *tables, int ncode
     ARG_CHECK(ncode >= 1 && ncode < IMP_TW && n >= 0 && chunk > 0 && bytes && nbytes && out && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 &&
               ((uintptr_t)bytes & 3) == 0 && (n == 0 || tables) && (ncode == 8 || !mask));
     hipStream_t s = (hipStream_t)stream;
-    AcDevState *st = nullptr;
-    uint4 *tab8 = nullptr;
-    int *tabn = nullptr;
-    if (dmalloc(&st, 1) || dmalloc(&tab8, 2 * (size_t)chunk) || dmalloc(&tabn, (size_t)chunk * IMP_TW)) return 1;
+    DevBuf<AcDevState> st;
+    DevBuf<uint4> tab8;
+    DevBuf<int> tabn;
+    if (st.alloc(1) || tab8.alloc(2 * (size_t)chunk) || tabn.alloc((size_t)chunk * IMP_TW)) return 1;
     hipLaunchKernelGGL(k_dec_init, dim3(1), dim3(64), 0, s, bytes, cap, nbytes, st, 1);
     LAUNCH_CHECK();
     for (long start = 0; start < n; start += chunk) {
@@ -1801,7 +1745,6 @@ LIC360_API int lic360_devcoder_decode(void *stream, const int *tables, int ncode
     hipLaunchKernelGGL(k_collect_err, dim3(1), dim3(64), 0, s, st, err, 1);
     LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize(s));
-    (void)hipFree(st); (void)hipFree(tab8); (void)hipFree(tabn);
     return 0;
 }
 

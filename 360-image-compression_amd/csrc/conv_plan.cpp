@@ -13,6 +13,7 @@
 #include "common.h"
 #include "conv_plan.h"
 #include <algorithm>
+#include <memory>
 
 static int bitrev7(int r) {
     int l = 0;
@@ -29,10 +30,9 @@ static int nchannel_for_group(const lic360_conv_plan &p, int g, int kh, int kw) 
 }
 
 template <class T>
-static int upload(const std::vector<T> &v, T **dst) {
-    size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    HIP_TRY(hipMalloc((void **)dst, bytes));
-    if (!v.empty()) HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+static int upload(const std::vector<T> &v, DevBuf<T> &dst) {
+    if (dst.alloc(v.size())) return 1;
+    if (!v.empty()) HIP_TRY(hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -40,7 +40,7 @@ LIC360_API int lic360_conv_plan_create(int channel, int ngroup, int nout, int ks
     ARG_CHECK(out && channel > 0 && ngroup > 0 && nout > 0 && ksz > 0 && (ksz & 1));
     ARG_CHECK(channel % ngroup == 0 && nout % ngroup == 0 && (constrain == 5 || constrain == 6));
     ARG_CHECK(channel < 65536 && ksz < 256);
-    lic360_conv_plan *p = new lic360_conv_plan();
+    std::unique_ptr<lic360_conv_plan> p(new lic360_conv_plan());
     p->C = channel; p->ngroup = ngroup; p->nout = nout; p->ksz = ksz; p->constrain = constrain;
     p->cin = channel / ngroup; p->cout = nout / ngroup; p->half = ksz / 2;
     p->n_mtiles = (nout + 15) / 16;
@@ -92,24 +92,13 @@ LIC360_API int lic360_conv_plan_create(int channel, int ngroup, int nout, int ks
     p->total_rec = rec;
     // wsrc was pushed as [rec][k][i] = slot k*16+i : matches the A-fragment lane map of 16x16x4 (lane = k*16 + i)
     for (int i = 0; i < LIC360_REC_PAD * 4; ++i) p->term.push_back(0 | (p->half << 16) | (p->half << 24));
-    int rc = 0;
-    rc |= upload(p->mt_rec_start, &p->d_mt_rec_start);
-    rc |= upload(p->leaf_cnt, &p->d_leaf_cnt);
-    rc |= upload(p->term, &p->d_term);
-    rc |= upload(p->wsrc, &p->d_wsrc);
-    rc |= upload(p->mt_glo, &p->d_mt_glo);
-    rc |= upload(p->mt_ghi, &p->d_mt_ghi);
-    if (rc) { lic360_conv_plan_destroy(p); return 1; }
-    *out = p;
+    if (upload(p->mt_rec_start, p->d_mt_rec_start) || upload(p->leaf_cnt, p->d_leaf_cnt) || upload(p->term, p->d_term) ||
+        upload(p->wsrc, p->d_wsrc) || upload(p->mt_glo, p->d_mt_glo) || upload(p->mt_ghi, p->d_mt_ghi)) return 1;
+    *out = p.release();
     return 0;
 }
 
-LIC360_API void lic360_conv_plan_destroy(lic360_conv_plan *p) {
-    if (!p) return;
-    (void)hipFree(p->d_mt_rec_start); (void)hipFree(p->d_leaf_cnt); (void)hipFree(p->d_term); (void)hipFree(p->d_wsrc);
-    (void)hipFree(p->d_mt_glo); (void)hipFree(p->d_mt_ghi);
-    delete p;
-}
+LIC360_API void lic360_conv_plan_destroy(lic360_conv_plan *p) { delete p; }
 
 LIC360_API long lic360_conv_plan_packed_floats(const lic360_conv_plan *p) {
     return p ? (p->total_rec + LIC360_REC_PAD) * 64 : 0;

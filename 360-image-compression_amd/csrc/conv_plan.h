@@ -1,5 +1,6 @@
 // conv_plan.h -- weight-independent schedule of one group-causal masked conv layer shape.
 #pragma once
+#include "common.h"
 #include <vector>
 #include <cstdint>
 
@@ -14,8 +15,7 @@ struct lic360_conv_plan {
     std::vector<int> term;                // [total_rec+PAD][4]  ti | kh<<16 | kw<<24
     std::vector<int> wsrc;                // [total_rec][64]     flat index into weight[nout][C][k][k], -1 = zero
     std::vector<int> mt_glo, mt_ghi;      // group range covered by each output tile
-    int *d_mt_rec_start = nullptr, *d_leaf_cnt = nullptr, *d_term = nullptr, *d_wsrc = nullptr;
-    int *d_mt_glo = nullptr, *d_mt_ghi = nullptr;
+    DevBuf<int> d_mt_rec_start, d_leaf_cnt, d_term, d_wsrc, d_mt_glo, d_mt_ghi;    // device copies of the arrays above
 };
 static const int LIC360_REC_PAD = 4;       // records readable past the end (software prefetch)
 

@@ -378,13 +378,11 @@ int lic360_dc_lists_build(void *stream, const signed char *need_d, int B, int G,
 // reachability statement of the dead cone
 LIC360_API int lic360_need_maps(void *stream, const float *mask, int B, int G, int H, int W, signed char *need_out) {
     ARG_CHECK(mask && need_out && B > 0 && G > 0 && G <= 127 && H > 0 && W > 0);
-    signed char *dd = nullptr, *tm = nullptr;
     const long S = H + W - 1, nt = (long)((H + 3) / 4) * ((W + 15) / 16);
-    HIP_TRY(hipMalloc((void **)&dd, (size_t)B * NEED_LAYERS * S * H));
-    HIP_TRY(hipMalloc((void **)&tm, (size_t)B * NEED_LAYERS * nt));
+    DevBuf<signed char> dd, tm;
+    if (dd.alloc((size_t)B * NEED_LAYERS * S * H) || tm.alloc((size_t)B * NEED_LAYERS * nt)) return 1;
     const int rc = lic360_need_build(stream, mask, B, G, H, W, need_out, dd, tm);
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    (void)hipFree(dd); (void)hipFree(tm);
     return rc;
 }
 

@@ -195,7 +195,7 @@ def test_sconv3x3_matches_the_oracle_conv(lic, case):
     assert np.all(got[frame] == 7.0)
 
 
-def test_sconv3x3_with_the_pixel_shuffle_as_its_store_pattern(lic):
+def test_sconv3x3_fuses_the_pixel_shuffle(lic):
     """the unpadded 3x3 conv -> PReLU -> Dtow(2) chain of ResidualBlockUp (test/model_zoo.py:160-162) in one launch: the shuffled window equals the
     oracle's sphere pad -> conv2d -> PReLU -> dtow; cells of the shuffled map outside the window are not touched"""
     import oracle as orc
