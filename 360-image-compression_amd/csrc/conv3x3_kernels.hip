@@ -309,3 +309,5 @@ LIC360_API int lic360_sconv1x1(void *stream, const float *x, const float *packed
                                int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
     return s3_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
 }
+
+#include "sconv_bf16x3.inc"          // the split-bf16 form of these convolutions (lic360_sconv3x3_bf16x3 / lic360_sconv1x1_bf16x3)

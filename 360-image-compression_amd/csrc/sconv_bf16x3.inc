@@ -1,0 +1,306 @@
+// sconv_bf16x3.inc -- the split-bf16 ("bf16x3") form of the transforms' sphere convolutions (csrc/conv3x3_kernels.hip): the same
+// operation -- sphere apron read by index, output window (ring, ring_w), tall last tile row, crop, x2 pixel-shuffle store, bias + PReLU +
+// residual in the epilogue, cells outside the window untouched -- on bf16 MFMAs, opt-in (lic360_models.set_conv_precision).
+//
+// Arithmetic.  Every fp32 operand v becomes hi = bf16(v) and lo = bf16(v - hi) (both round to nearest even; v - hi is exact in fp32); each
+// product is w_hi x_hi + w_hi x_lo + w_lo x_hi on v_mfma_f32_16x16x32_bf16, accumulated in fp32.  hi + lo holds v to 2^-17 relative, the
+// dropped w_lo x_lo is below 2^-16 of the product: about 2^-16 relative per product (fp32: 2^-24), i.e. 1e-4 parity with a library convolution
+// on the transforms' data.  Three 16x16x32 bf16 MFMAs (16 cycles each) do the K = 32 that eight 16x16x4 fp32 MFMAs (32 cycles each) do:
+// 3/16 of the matrix time.  Inference only; NaN / infinity and values within 2^-8 of FLT_MAX are outside the contract.
+//
+// Mapping.  As the fp32 body: M = output channels, N = positions, K = (input channel, tap); a workgroup (8 waves, two per SIMD) owns a 16 x 16
+// tile (or the tall last tile row) of one image and NQ * 48 output channels, wave (mq, nh) 3 row tiles x RW rows in 12 RW accumulator registers.
+// K step = 32 input channels of one tap (kw, kh): lane (kq, i) of the A operand holds W[co = 48 mq + 16 mt + i][ci = 32 cg + 8 kq + j][kh][kw],
+// j < 8, lane (kq, col) of the B operand x[ci = 32 cg + 8 kq + j] at (row + kh, col + kw).  Input channels arrive in chunks of 32: their halo
+// tiles go by the fp32 body's per-lane LDS-DMA (sphere rule by index) to a double-buffered fp32 staging image, one chunk ahead.
+//
+// Where the split happens: ONCE per chunk, in a conversion pass over the LDS halo tile (not at fragment-read time, where each of the NQ waves
+// that share a row group would split the same values again, from 8 strided ds_read_b32 per operand).  Each lane of the pass reads 8 channels of
+// one halo cell (ds_read_b32, conflict-free: consecutive lanes, consecutive cells), converts them (8 v_cvt to bf16 + 8 subtractions + 8 more
+// conversions) and writes one 16-byte hi cell and one 16-byte lo cell; a B operand is then one ds_read_b128 for hi and one for lo.  Split image:
+// [hl][kq < 4][PS cells] x 16 bytes, PS = halo cells rounded up to 16 (a plane = 0 mod 64 banks: the four kq planes of a ds_read_b128 fall
+// on disjoint banks, the 16 columns of a lane group on all 64).  Cost: 3 pass iterations per lane and chunk and a second barrier per chunk
+// against 648 MFMAs per wave (192 channels, 3x3); measurements: DESIGN 7c'.
+// Included at the end of conv3x3_kernels.hip (one translation unit: S3Args, the LDS-DMA helpers and the sphere rule are that file's; the tests
+// that check every M0-writing translation unit compile it).  s3_cell_offsets / s3_epilogue restate the fp32 body's inline code for this body;
+// the fp32 body keeps its own copy, so its code is unchanged.
+#include <type_traits>
+
+// this lane's cells of a chunk's LDS image: LDS float q = (i * 8 + wave) * 64 + lane <-> (channel q / PL, halo row, halo column) of the CK
+// channels of a chunk, a channel's (tile rows + KS - 1) x XC halo cells at pitch PL.  voff[i] = byte offset of the cell's source in the
+// chunk's first input plane (sphere rule applied).
+template <int NDMA, int CK, int PL, int XR, int XC, int KS>
+__device__ __forceinline__ void s3_cell_offsets(const S3Args &a, int tr0, int tc0, int wave, int lane, long PLg, unsigned (&voff)[NDMA]) {
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) {
+        const int q = (i * 8 + wave) * 64 + lane;
+        int ch = q / PL, rem = q - ch * PL;
+        if (ch >= CK || rem >= XR * XC) { ch = 0; rem = 0; }      // pitch padding and the slack behind the last plane: any valid cell
+        const int r = rem / XC, c = rem - r * XC;
+        int ph = tr0 - KS / 2 + r, pw = tc0 - KS / 2 + c;
+        ph = ph < 0 ? 0 : (ph > a.hp - 1 ? a.hp - 1 : ph);                  // (only cells of outputs outside the window reach past the map)
+        pw = pw < 0 ? 0 : (pw > a.wp - 1 ? a.wp - 1 : pw);
+        if (a.sphere == 1) s3_sphere(ph, pw, a.hp, a.wp, a.pad);
+        else if (a.sphere == 2) { const int W = a.wp - 2 * a.pad; pw = pw < a.pad ? pw + W : (pw >= a.pad + W ? pw - W : pw); }
+        voff[i] = (unsigned)(((long)ch * PLg + (long)ph * a.wp + pw) * 4);
+    }
+}
+
+// bias, PReLU, residual, store.  Accumulator m, row r, register v: channel co0 + 16 m + 4 kq + v (co0 = the wave's first output channel),
+// position (tr0 + nh * RW + r, tc0 + col) of the input grid (col = lane & 15, kq = lane >> 4, PLg = hp * wp); cells outside the window are not written
+template <int RW>
+__device__ __forceinline__ void s3_epilogue(const S3Args &a, const s3_f4 (&acc)[3][RW], int img, int tr0, int tc0, int co0, int nh, int col, int kq,
+                                            long PLg) {
+    const int pw = tc0 + col;
+    const long oPL = (long)a.ohp * a.owp;
+    const float *__restrict__ resp = a.res;
+    float *__restrict__ outp = a.out;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int co = co0 + 16 * m + 4 * kq;
+        const s3_f4 bs = *(const s3_f4 *)(a.bias + co);
+        s3_f4 sl = {1.f, 1.f, 1.f, 1.f};
+        if (a.slope) sl = *(const s3_f4 *)(a.slope + co);
+        s3_f4 rv[RW];
+        if (resp) {                                                         // all residual loads of the row tile in flight before its first store
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                const int ph = tr0 + nh * RW + r;
+                const bool ok = ph < a.hp - a.ring && pw < a.wp - a.ringw;
+                const int rh = ok ? ph : a.ring, rw_ = ok ? pw : a.ringw;
+                if (a.shuffle) {                                           // the residual has the OUTPUT's (shuffled) geometry
+                    typedef float s3_f2 __attribute__((ext_vector_type(2)));
+                    const long ri = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (rh - a.ooff)) * (2 * a.owp) + 2 * (rw_ - a.ooff);
+                    const s3_f2 lo = *(const s3_f2 *)(resp + ri), hi = *(const s3_f2 *)(resp + ri + 2 * a.owp);
+                    rv[r] = (s3_f4){lo[0], lo[1], hi[0], hi[1]};
+                } else {
+                    const long ri = ((long)img * a.cout + co) * PLg + (long)rh * a.wp + rw_;
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) rv[r][v] = resp[ri + v * PLg];
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            const int ph = tr0 + nh * RW + r;
+            if (ph < a.hp - a.ring && pw < a.wp - a.ringw) {
+                float y[4];
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    y[v] = acc[m][r][v] + bs[v];
+                    if (a.slope) y[v] = y[v] > 0.f ? y[v] : y[v] * sl[v];
+                    if (resp) y[v] = y[v] + rv[r][v];
+                }
+                if (a.shuffle) {                                           // two 8-byte stores per lane: 16 lanes write 128 contiguous bytes of each of two rows
+                    typedef float s3_f2 __attribute__((ext_vector_type(2)));
+                    const long o = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (ph - a.ooff)) * (2 * a.owp) + 2 * (pw - a.ooff);
+                    *(s3_f2 *)(outp + o) = (s3_f2){y[0], y[1]};
+                    *(s3_f2 *)(outp + o + 2 * a.owp) = (s3_f2){y[2], y[3]};
+                } else {
+                    const long o = ((long)img * a.cout + co) * oPL + (long)(ph - a.ooff) * a.owp + (pw - a.ooff);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) outp[o + v * oPL] = y[v];
+                }
+            }
+        }
+    }
+}
+
+typedef __bf16 b3_bf8 __attribute__((ext_vector_type(8)));
+typedef unsigned b3_u4 __attribute__((ext_vector_type(4)));
+
+#define B3_THREADS 512
+#define B3_CK 32                                                            // input channels per chunk (= the K of one MFMA)
+constexpr int b3_ndma(int ncell) { return (B3_CK * ncell + 511) / 512; }   // DMA instructions per wave and chunk (fp32 staging pitch = halo cells)
+constexpr int b3_ps(int ncell) { return (ncell + 15) / 16 * 16; }          // split-image plane pitch in 16-byte cells
+// LDS floats of a body: two fp32 staging buffers + the split image (2 x 4 planes of PS 16-byte cells)
+constexpr int b3_lds(int tr, int ks) { return 2 * 8 * b3_ndma((tr + ks - 1) * (S3_T + ks - 1)) * 64 + 32 * b3_ps((tr + ks - 1) * (S3_T + ks - 1)); }
+
+__device__ __forceinline__ b3_u4 b3_split(const float (&v)[8], bool lo) {  // 8 values -> their bf16 hi (lo = false) or lo parts, packed
+    b3_bf8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const __bf16 h = (__bf16)v[j];
+        r[j] = lo ? (__bf16)(v[j] - (float)h) : h;
+    }
+    return __builtin_bit_cast(b3_u4, r);
+}
+
+// weights: [cout block of NQ * 48][it = (cg * ks + kw) * ks + kh < cin / 32 * ks * ks][mq][mt < 3][hl < 2][lane] x 8 bf16; lane l = 16 kq + i,
+// element j: the hi (hl = 0) or lo (hl = 1) part of W[co = 48 mq + 16 mt + i][ci = 32 cg + 8 kq + j][kh][kw] -- the A operand of the K step
+// (cg, kw, kh) for row tile mt; a wave reads its six operands of a step as one 6 KiB block.  One thread per 16-byte cell.
+__global__ void k_sconv_b3_pack(const float *__restrict__ w, b3_u4 *__restrict__ packed, int cin, int cout, int nq, int ks, long total) {
+    const int nit = cin / B3_CK * ks * ks;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int lane = (int)(idx & 63);
+        long r = idx >> 6;
+        const int hl = (int)(r & 1); r >>= 1;
+        const int mt = (int)(r % 3); r /= 3;
+        const int mq = (int)(r % nq); r /= nq;
+        const int it = (int)(r % nit), blk = (int)(r / nit);
+        const int kh = it % ks, kw = it / ks % ks, cg = it / (ks * ks);
+        const int co = blk * nq * 48 + 48 * mq + 16 * mt + (lane & 15), ci0 = B3_CK * cg + 8 * (lane >> 4);
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = w[(((long)co * cin + ci0 + j) * ks + kh) * ks + kw];
+        packed[idx] = b3_split(v, hl != 0);
+    }
+}
+
+template <int NQ, int RW, int KS>                                           // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps
+__device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int tx, int img) {
+    constexpr int NR = 8 / NQ, TR = NR * RW, XR = TR + KS - 1, XC = S3_T + KS - 1, NCELL = XR * XC;
+    constexpr int NDMA = b3_ndma(NCELL), BUF = 8 * NDMA * 64, PS = b3_ps(NCELL), NSTEP = KS * KS;
+    float (*xs)[BUF] = (float (*)[BUF])lds;
+    b3_u4 *sp = (b3_u4 *)(lds + 2 * BUF);                                   // split image [hl][kq][PS]
+    const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, kq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), mq = wave % NQ, nh = wave / NQ;
+    const int tr0 = a.ring + ty * (NR * a.rw), tc0 = a.ringw + tx * S3_T;
+    const int blk = blockIdx.y;
+    const long PLg = (long)a.hp * a.wp;
+    unsigned voff[NDMA];
+    s3_cell_offsets<NDMA, B3_CK, NCELL, XR, XC, KS>(a, tr0, tc0, wave, lane, PLg, voff);
+    const float *xb = a.x + (long)img * a.cin * PLg;
+    const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) const float *)&xs[0][0];
+    auto issue_dma = [&](const float *sb0, int buf) __attribute__((always_inline)) {
+        const float *sb = s3_uniform(sb0);
+        const unsigned lb = lds0 + (unsigned)(buf * BUF + wave * 64) * 4u;
+#pragma unroll
+        for (int i = 0; i < NDMA; ++i) s3_dma(voff[i], sb, lb + (unsigned)(i * 8 * 64 * 4));
+    };
+    const int nck = a.cin / B3_CK, niter = nck * NSTEP;
+    // A operands: six 16-byte loads per lane and K step (two address registers: the offset field stops at 4 KiB), one step ahead, waited for by
+    // counted vmcnt as in the fp32 body: the chunk's DMAs are issued behind the loads of its second step, so the wait at step 1 skips them
+    const char *wl = (const char *)a.w + (((long)blk * niter * NQ + mq) * 6 * 64 + lane) * 16;   // + it * NQ * 6 KiB per K step
+    auto load_a = [&](int it, b3_u4 (&A)[6]) __attribute__((always_inline)) {
+        const char *p = wl + (long)it * (NQ * 6 * 1024), *q = p + 3072;
+        asm volatile("global_load_dwordx4 %0, %6, off\n\tglobal_load_dwordx4 %1, %6, off offset:1024\n\tglobal_load_dwordx4 %2, %6, off offset:2048\n\t"
+                     "global_load_dwordx4 %3, %7, off\n\tglobal_load_dwordx4 %4, %7, off offset:1024\n\tglobal_load_dwordx4 %5, %7, off offset:2048"
+                     : "=&v"(A[0]), "=&v"(A[1]), "=&v"(A[2]), "=&v"(A[3]), "=&v"(A[4]), "=&v"(A[5]) : "v"(p), "v"(q));
+    };
+#define B3_WAIT_A(N, A_) asm volatile("s_waitcnt vmcnt(%6)" : "+v"(A_[0]), "+v"(A_[1]), "+v"(A_[2]), "+v"(A_[3]), "+v"(A_[4]), "+v"(A_[5]) : "n"(N))
+    s3_f4 acc[3][RW];
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+#pragma unroll
+        for (int r = 0; r < RW; ++r) acc[m][r] = (s3_f4){0.f, 0.f, 0.f, 0.f};
+    b3_u4 A[2][6];                                                          // operand ring: K step `it` in set it & 1
+    issue_dma(xb, 0);
+    load_a(0, A[0]);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // one chunk; P = ck & 1 makes the operand set of every step static (NSTEP is odd)
+    auto chunk = [&](int ck, auto par) __attribute__((always_inline)) {
+        constexpr int P = decltype(par)::value;
+        // the split pass: fp32 staging buffer ck & 1 -> the split image (its last readers passed the barrier that ended the previous chunk)
+        const float *xf = xs[ck & 1];
+#pragma unroll
+        for (int c0 = 0; c0 < 4 * NCELL; c0 += B3_THREADS) {
+            const int c = c0 + tid;
+            if (c0 + B3_THREADS <= 4 * NCELL || c < 4 * NCELL) {
+                const int g = c / NCELL, pos = c - g * NCELL;
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = xf[(8 * g + j) * NCELL + pos];
+                sp[g * PS + pos] = b3_split(v, false);
+                sp[(4 + g) * PS + pos] = b3_split(v, true);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < NSTEP; ++p) {
+            const int kw = p / KS, kh = p - KS * kw, sa = (P * NSTEP + p) & 1;
+            // in-order counter: behind step 1's operands come only the chunk's DMAs (issued at step 0); at step 0 the end-of-chunk wait covered it
+            if (p == 1) B3_WAIT_A(NDMA, A[sa]);
+            else if (p > 1) B3_WAIT_A(0, A[sa]);
+            const int itn = ck * NSTEP + p + 1;
+            load_a(itn < niter ? itn : niter - 1, A[sa ^ 1]);
+            if (p == 0) issue_dma(ck + 1 < nck ? xb + (long)(ck + 1) * B3_CK * PLg : xb, (ck + 1) & 1);   // the last chunk's are harmless loads into the idle buffer
+            const b3_u4 *bl = sp + kq * PS + (nh * RW + kh) * XC + col + kw;
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                const b3_bf8 bh = __builtin_bit_cast(b3_bf8, bl[r * XC]), blo = __builtin_bit_cast(b3_bf8, bl[4 * PS + r * XC]);
+#pragma unroll
+                for (int m = 0; m < 3; ++m) {
+                    const b3_bf8 ah = __builtin_bit_cast(b3_bf8, A[sa][2 * m]), alo = __builtin_bit_cast(b3_bf8, A[sa][2 * m + 1]);
+                    acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bh, acc[m][r], 0, 0, 0);
+                    acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, blo, acc[m][r], 0, 0, 0);
+                    acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[m][r], 0, 0, 0);
+                }
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the next chunk's DMAs have landed (and its first operands)
+        __syncthreads();
+    };
+    for (int ck = 0; ck < nck; ck += 2) {
+        chunk(ck, std::integral_constant<int, 0>{});
+        if (ck + 1 < nck) chunk(ck + 1, std::integral_constant<int, 1>{});
+    }
+#undef B3_WAIT_A
+    s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
+}
+
+template <int NQ, int RW, int KS>
+__global__ __launch_bounds__(B3_THREADS) void k_sconv_b3(S3Args a) {
+    constexpr int NR = 8 / NQ;
+    __shared__ __attribute__((aligned(16))) float lds[b3_lds(NR * (RW + (KS == 3 ? 1 : 0)), KS)];
+    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
+    const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
+    if constexpr (KS == 3) {
+        if (a.tall_last && ty == a.tiles_y - 1) { b3_body<NQ, RW + 1, 3>(a, lds, ty, tx, img); return; }
+    }
+    b3_body<NQ, RW, KS>(a, lds, ty, tx, img);
+}
+
+static inline bool b3_ok(int cin, int cout, int ks) { return (ks == 3 || ks == 1) && cin >= B3_CK && cin % B3_CK == 0 && cout >= 96 && (cout % 192 == 0 || cout == 96); }
+static inline long b3_packed_bytes(int cin, int cout, int ks) { return b3_ok(cin, cout, ks) ? (long)cout * cin * ks * ks * 4 : 0; }   // hi + lo bf16 per weight
+static int b3_pack(void *stream, const float *weight, void *packed, int cin, int cout, int ks) {
+    ARG_CHECK(weight && packed && b3_ok(cin, cout, ks) && ((uintptr_t)packed & 15) == 0);
+    const long total = b3_packed_bytes(cin, cout, ks) / 16;
+    hipLaunchKernelGGL(k_sconv_b3_pack, dim3(lic360_blocks(total)), dim3(256), 0, (hipStream_t)stream, weight, (b3_u4 *)packed, cin, cout,
+                       cout % 192 == 0 ? 4 : 2, ks, total);
+    LAUNCH_CHECK();
+    return 0;
+}
+static int b3_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                     int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle) {
+    // the fp32 launch's argument contract (csrc/conv3x3_kernels.hip, s3_launch), with the 32-channel chunk of this body
+    ARG_CHECK(x && packed && bias && out && n > 0 && b3_ok(cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w && out_crop >= 0 &&
+              out_crop <= ring && sphere >= 0 && sphere <= 2);
+    ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));
+    ARG_CHECK((double)B3_CK * hp * wp * 4.0 < 4294967296.0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)bias & 15) == 0 && (!slope || ((uintptr_t)slope & 15) == 0));
+    ARG_CHECK(!residual || out_crop == 0 || shuffle);
+    ARG_CHECK(!shuffle || (((uintptr_t)out & 7) == 0 && ((uintptr_t)residual & 7) == 0));
+    S3Args a;
+    a.x = x; a.w = (const float *)packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
+    a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = ring; a.ringw = ring_w;
+    a.ooff = out_crop; a.ohp = hp - 2 * out_crop; a.owp = wp - 2 * out_crop; a.shuffle = shuffle;
+    a.tiles_x = (wp - 2 * ring_w + S3_T - 1) / S3_T;
+    const int nq = cout % 192 == 0 ? 4 : 2, nrg = 8 / nq, nr = hp - 2 * ring, full = nr / S3_T, rem = nr - full * S3_T;
+    a.rw = S3_T / nrg;
+    a.tall_last = ks == 3 && rem > 0 && rem <= nrg && full > 0;
+    a.tiles_y = a.tall_last ? full : (nr + S3_T - 1) / S3_T;
+    const long tiles = (long)n * a.tiles_x * a.tiles_y;
+    ARG_CHECK(tiles < (1L << 31));
+    const dim3 grid((unsigned)tiles, nq == 4 ? cout / 192 : 1);
+    if (ks == 3 && nq == 4) hipLaunchKernelGGL((k_sconv_b3<4, 8, 3>), grid, dim3(B3_THREADS), 0, (hipStream_t)stream, a);
+    else if (ks == 3) hipLaunchKernelGGL((k_sconv_b3<2, 4, 3>), grid, dim3(B3_THREADS), 0, (hipStream_t)stream, a);
+    else if (nq == 4) hipLaunchKernelGGL((k_sconv_b3<4, 8, 1>), grid, dim3(B3_THREADS), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_sconv_b3<2, 4, 1>), grid, dim3(B3_THREADS), 0, (hipStream_t)stream, a);
+    LAUNCH_CHECK();
+    return 0;
+}
+LIC360_API int lic360_sconv3x3_bf16x3_supported(int cin, int cout) { return b3_ok(cin, cout, 3) ? 1 : 0; }
+LIC360_API long lic360_sconv3x3_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(cin, cout, 3); }
+LIC360_API int lic360_sconv3x3_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(stream, weight, packed, cin, cout, 3); }
+LIC360_API int lic360_sconv3x3_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
+    return b3_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+}
+LIC360_API int lic360_sconv1x1_bf16x3_supported(int cin, int cout) { return b3_ok(cin, cout, 1) ? 1 : 0; }
+LIC360_API long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(cin, cout, 1); }
+LIC360_API int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(stream, weight, packed, cin, cout, 1); }
+LIC360_API int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                      int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
+    return b3_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+}

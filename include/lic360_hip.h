@@ -349,6 +349,24 @@ long lic360_sconv1x1_packed_floats(int cin, int cout);
 int lic360_sconv1x1_pack(void *stream, const float *weight, float *packed, int cin, int cout);
 int lic360_sconv1x1(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                     int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle);
+/* ---- the split-bf16 ("bf16x3") form of lic360_sconv3x3 / lic360_sconv1x1 (csrc/sconv_bf16x3.inc), opt-in: the same operation and the same
+ * argument lists (sphere apron by index, window, crop, shuffle, bias + PReLU + residual; cells outside the window not touched), replacing the
+ * same reference layers as its fp32 sibling.  Every fp32 operand is split into hi = bf16(v) and lo = bf16(v - hi); each product is
+ * w_hi x_hi + w_hi x_lo + w_lo x_hi on v_mfma_f32_16x16x32_bf16 with fp32 accumulation: about 2^-16 relative error per product (fp32: 2^-24), this
+ * kernel's own summation order -- 1e-4 against a library convolution on the transforms' data, at least 16x closer than single-pass bf16.
+ * Inference only.  cin % 32 == 0, cout in {96} or a multiple of 192; packed = lic360_sconv3x3_bf16x3_pack (packed_bytes bytes, 16-byte aligned:
+ * hi and lo bf16 planes in the waves' operand order) -- NOT the fp32 pack. */
+int lic360_sconv3x3_bf16x3_supported(int cin, int cout);
+long lic360_sconv3x3_bf16x3_packed_bytes(int cin, int cout);
+int lic360_sconv3x3_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout);
+int lic360_sconv3x3_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                           int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int crop, int shuffle);
+/* the 1x1 layers in the same form (replaces what lic360_sconv1x1 replaces; same accuracy statement; cin % 32 == 0, cout = 96 or a multiple of 192) */
+int lic360_sconv1x1_bf16x3_supported(int cin, int cout);
+long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout);
+int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout);
+int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                           int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle);
 /* apron of dst <- sphere-wrapped interior of src (src == dst: lic360_sphere_pad_inplace); [nc][hp][wp] planes      sphere_pad_cuda.cu:48-65 */
 int lic360_sphere_apron_from(void *stream, const float *src, float *dst, int nc, int hp, int wp, int pad);
 

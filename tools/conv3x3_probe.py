@@ -1,7 +1,8 @@
 """lic360_sconv3x3 (csrc/conv3x3_kernels.hip) next to torch.nn.functional.conv2d (MIOpen) on the transforms' 3x3 stride-1 shapes, batch 8:
 correctness (max |diff| against conv2d over the sphere-padded map, fp32) and time per launch -- the library form timed WITH the launches the
-fused kernel absorbs (in-place apron refresh, PReLU, trim) and without.  VERDICT r4 next #2."""
-import os, sys
+fused kernel absorbs (in-place apron refresh, PReLU, trim) and without.  VERDICT r4 next #2.
+--precision bf16x3: "ours" is the split-bf16 form (lic360_sconv3x3_bf16x3 / sconv1x1_bf16x3), timed in the same run next to the fp32 kernel."""
+import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "360-image-compression_amd"))
 import torch
@@ -9,6 +10,9 @@ import torch.nn.functional as F
 import lic360
 
 dev = "cuda:0"
+ap = argparse.ArgumentParser()
+ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32")
+B3 = ap.parse_args().precision == "bf16x3"
 
 
 def timed(fn, reps=10):
@@ -32,7 +36,7 @@ for (n, cin, cout, hp, wp, ring, crop) in shapes:
     w = torch.randn(cout, cin, 3, 3, device=dev) * 0.05
     b, sl = torch.randn(cout, device=dev), torch.rand(cout, device=dev) * 0.5
     res = torch.randn(n, cout, hp, wp, device=dev) if crop == 0 else None
-    pk = lic360.sconv3x3_pack(w)
+    pk, pk3 = lic360.sconv3x3_pack(w), (lic360.sconv3x3_bf16x3_pack(w) if B3 else None)
     out = torch.zeros(n, cout, hp - 2 * crop, wp - 2 * crop, device=dev)
     pad_op, trim_op = lic360.SpherePadOp(2, True, 0, False), lic360.SphereTrimOp(ring, 0, False)
 
@@ -46,8 +50,13 @@ for (n, cin, cout, hp, wp, ring, crop) in shapes:
                 y = y + res
         return y
 
-    def ours():
+    def fp32():
         return lic360.sconv3x3(x, pk, b, sl, res, out, pad=2, sphere=True, ring=ring, crop=crop, ring_w=max(ring, 2 - 2 * crop))
+
+    def ours():
+        if not B3:
+            return fp32()
+        return lic360.sconv3x3_bf16x3(x, pk3, b, sl, res, out, pad=2, sphere=True, ring=ring, crop=crop, ring_w=max(ring, 2 - 2 * crop))
 
     want = lib(True)                                                    # (refreshes x's apron in place: the fused kernel ignores it anyway)
     got = ours()
@@ -65,6 +74,13 @@ for (n, cin, cout, hp, wp, ring, crop) in shapes:
           "(%.1f TF on its %dx%d window, %.1f TF nominal) | ours / library-with-epilogue = %.2f" % (
               cin, cout, hp, wp, n, ring, crop, err, t_conv, fl_lib / t_conv / 1e9, t_full, t_ours, fl_win / t_ours / 1e9, hp - 2 * ring, wp - 2 * rw_,
               fl_lib / t_ours / 1e9, t_ours / t_full), flush=True)
+    if B3:
+        t32, t3 = [], []
+        for _ in range(5):
+            t32.append(timed(fp32))
+            t3.append(timed(ours))
+        print("    bf16x3 vs fp32 sconv3x3, 5 alternating repeats: fp32 %.3f ms (min %.3f max %.3f), bf16x3 %.3f ms (min %.3f max %.3f), speedup %.2f" % (
+            sorted(t32)[2], min(t32), max(t32), sorted(t3)[2], min(t3), max(t3), sorted(t32)[2] / sorted(t3)[2]), flush=True)
 
 # ---- the 1x1 layers of ResidualBlock on the same kernel body, against the library GEMM (+ the elementwise launch each one absorbs)
 for (n, cin, cout, hp, wp, what) in [(8, 192, 96, 132, 260, "prelu"), (8, 96, 192, 132, 260, "add"), (8, 192, 192, 132, 260, "prelu")]:
@@ -74,12 +90,23 @@ for (n, cin, cout, hp, wp, what) in [(8, 192, 96, 132, 260, "prelu"), (8, 96, 19
     b, sl = torch.randn(cout, device=dev), torch.rand(cout, device=dev) * 0.5
     res = torch.randn(n, cout, hp, wp, device=dev)
     pk = lic360.sconv1x1_pack(w)
+    conv1, pk1 = lic360.sconv1x1, pk
+    if B3:
+        conv1, pk1 = lic360.sconv1x1_bf16x3, lic360.sconv1x1_bf16x3_pack(w)
     out = torch.zeros(n, cout, hp, wp, device=dev)
     lib = (lambda: F.prelu(F.conv2d(x, w, b), sl)) if what == "prelu" else (lambda: F.conv2d(x, w, b) + res)
-    ours = (lambda: lic360.sconv1x1(x, pk, b, sl, None, out, ring=2)) if what == "prelu" else (lambda: lic360.sconv1x1(x, pk, b, None, res, out, ring=2))
+    ours = (lambda: conv1(x, pk1, b, sl, None, out, ring=2)) if what == "prelu" else (lambda: conv1(x, pk1, b, None, res, out, ring=2))
+    fp32 = (lambda: lic360.sconv1x1(x, pk, b, sl, None, out, ring=2)) if what == "prelu" else (lambda: lic360.sconv1x1(x, pk, b, None, res, out, ring=2))
     win = (slice(None), slice(None), slice(2, hp - 2), slice(2, wp - 2))
     err = (ours()[win] - lib()[win]).abs().max().item()
     t_conv, t_lib, t_ours = timed(lambda: F.conv2d(x, w, b)), timed(lib), timed(ours)
     fl = 2.0 * n * cout * cin * (hp - 4) * (wp - 4)
     print("1x1 %d->%d @%dx%d x%d + %s: max|diff| %.2e | library conv alone %.3f ms, with the %s %.3f ms | sconv1x1 %.3f ms (%.1f TF on its window) | ours / library = %.2f" % (
         cin, cout, hp, wp, n, what, err, t_conv, what, t_lib, t_ours, fl / t_ours / 1e9, t_ours / t_lib), flush=True)
+    if B3:
+        t32, t3 = [], []
+        for _ in range(5):
+            t32.append(timed(fp32))
+            t3.append(timed(ours))
+        print("    bf16x3 vs fp32 sconv1x1, 5 alternating repeats: fp32 %.3f ms (min %.3f max %.3f), bf16x3 %.3f ms (min %.3f max %.3f), speedup %.2f" % (
+            sorted(t32)[2], min(t32), max(t32), sorted(t3)[2], min(t3), max(t3), sorted(t32)[2] / sorted(t3)[2]), flush=True)

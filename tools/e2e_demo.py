@@ -33,6 +33,7 @@ def main():
     ap.add_argument("--images", nargs="*", default=[])
     ap.add_argument("--checkpoint")
     ap.add_argument("--imp-checkpoint")
+    ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32", help="arithmetic of the transforms' fused convolutions")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     import lic360_container as box
@@ -62,6 +63,8 @@ def main():
         dec.quant.weight.data.copy_(enc.quant.weight.data)
         fc.load_layers(make_main_params(1003, 48))
         ic.load_layers(make_imp_params(1003))
+    lm.set_conv_precision(enc, args.precision)                             # the latent's bitstream is exact in either mode; only the pixels depend on it
+    lm.set_conv_precision(dec, args.precision)
     with torch.no_grad():
         torch.cuda.synchronize()
         t0 = time.time()

@@ -1,6 +1,8 @@
 """Analysis / synthesis transforms (lic360_models.py) at the reference's width (192 channels, 512x1024 ERPs): ms per image and nominal
 TFLOP/s (library convolutions through MIOpen + this package's sphere / shuffle / quantiser / GDN kernels), and the one-pass GDN against
-its four-kernel torch form.  Seeded random weights.  Writes one JSON document to stdout."""
+its four-kernel torch form.  Seeded random weights.  Writes one JSON document to stdout.
+--precision {fp32,bf16x3}: the mode of the fused convolutions (lic360_models.set_conv_precision) for every row; --ab: only the analysis and
+synthesis transforms, ms per image in both modes, alternating in one run (one JSON line per repeat and a summary)."""
 import json
 import os
 import sys
@@ -25,12 +27,14 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps * 1e-3
 
 
-def measure(batch=8, device=0, reps=3):
+def measure(batch=8, device=0, reps=3, precision="fp32"):
     import lic360
     import lic360_models as lm
     dev = "cuda:%d" % device
     torch.manual_seed(0)
     enc, dec = lm.CMP_Encoder(gpu_id=device).to(dev).eval(), lm.CMP_Decoder(gpu_id=device).to(dev).eval()
+    lm.set_conv_precision(enc, precision)
+    lm.set_conv_precision(dec, precision)
     ge, gd = lm.transform_gflops()
     rows = []
     with torch.no_grad():
@@ -61,11 +65,16 @@ def measure(batch=8, device=0, reps=3):
             ww, bb, sl = torch.randn((c, c, 3, 3), device=dev) * 0.05, torch.randn((c,), device=dev), torch.rand((c,), device=dev) * 0.5
             res, oo, pk = torch.randn_like(xx), torch.zeros_like(xx), lic360.sconv3x3_pack(ww)
             pad_op, trim_op = lic360.SpherePadOp(2, True, device, False), lic360.SphereTrimOp(2, device, False)
-            t_o = timed(lambda: lic360.sconv3x3(xx, pk, bb, sl, res, oo, pad=2, sphere=True, ring=2), 5)
+            if precision == "bf16x3":
+                pk3 = lic360.sconv3x3_bf16x3_pack(ww)
+                t_o = timed(lambda: lic360.sconv3x3_bf16x3(xx, pk3, bb, sl, res, oo, pad=2, sphere=True, ring=2), 5)
+            else:
+                t_o = timed(lambda: lic360.sconv3x3(xx, pk, bb, sl, res, oo, pad=2, sphere=True, ring=2), 5)
             t_c = timed(lambda: F.conv2d(xx, ww, bb, padding=1), 5)
             t_l = timed(lambda: trim_op.forward(F.prelu(F.conv2d(pad_op.forward(xx)[0], ww, bb, padding=1), sl))[0] + res, 5)
             fl = 2.0 * batch * c * c * 9 * (hp - 4) * (wp - 4)
             rows.append({"kernel": "sconv3x3 192->192 on %dx%d maps (%dx%d window): apron by index + conv + bias + PReLU + trim + residual" % (hp, wp, hp - 4, wp - 4),
+                         "precision": precision,
                          "bound": "mfma", "images_per_launch": batch, "avg_launch_ms": t_o * 1e3, "achieved": fl / t_o / 1e12, "peak": F32_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": fl / t_o / 1e12 / F32_PEAK_TFLOPS, "algorithmic_flops_per_launch": fl,
                          "miopen_conv_alone_ms": t_c * 1e3, "miopen_conv_with_pad_prelu_trim_add_ms": t_l * 1e3,
@@ -188,7 +197,37 @@ def whole_codec_streams(enc, dec, device, batch=48, reps=2, nstreams=2):
             "peak": None, "frac": None, "roundtrip_exact": exact, "mean_latent_bytes": float(np.mean([float(L["fc"].nbytes[:per].float().mean().item()) for L in lanes]))}
 
 
+def ab_transforms(batch=8, device=0, reps=3, repeats=5):
+    """analysis and synthesis ms per image, fp32 and bf16x3 modes alternating on the same networks and inputs"""
+    import lic360_models as lm
+    dev = "cuda:%d" % device
+    torch.manual_seed(0)
+    enc, dec = lm.CMP_Encoder(gpu_id=device).to(dev).eval(), lm.CMP_Decoder(gpu_id=device).to(dev).eval()
+    t = {(p, k): [] for p in ("fp32", "bf16x3") for k in ("analysis", "synthesis")}
+    with torch.no_grad():
+        img = torch.rand((batch, 3, 512, 1024), device=dev)
+        code, mask, _ = enc(img)
+        for i in range(repeats):
+            for p in ("fp32", "bf16x3"):
+                lm.set_conv_precision(enc, p)
+                lm.set_conv_precision(dec, p)
+                row = {"repeat": i, "precision": p, "batch": batch}
+                for k, fn in (("analysis", lambda: enc(img)), ("synthesis", lambda: dec(code, mask))):
+                    row[k + "_ms_per_image"] = timed(fn, reps) / batch * 1e3
+                    t[(p, k)].append(row[k + "_ms_per_image"])
+                print(json.dumps(row), flush=True)
+    med = {"%s_%s_ms_per_image" % (k, p): sorted(v)[len(v) // 2] for (p, k), v in t.items()}
+    spread = {"%s_%s_min_max" % (k, p): [min(v), max(v)] for (p, k), v in t.items()}
+    print(json.dumps({"summary": "median of %d alternating repeats" % repeats, **med, **spread}))
+
+
 if __name__ == "__main__":
+    if "--ab" in sys.argv:
+        ab_transforms()
+        sys.exit(0)
+    precision = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp32"
+    if precision not in ("fp32", "bf16x3"):
+        sys.exit("--precision must be fp32 or bf16x3")
     if len(sys.argv) > 1 and sys.argv[1] == "streams":                      # the whole codec as N sub-batches on N streams (experiment: N = 2, 3)
         import lic360_models as lm
         torch.manual_seed(0)
@@ -197,4 +236,4 @@ if __name__ == "__main__":
         for ns in (int(v) for v in sys.argv[2:]):
             print(json.dumps(whole_codec_streams(e, d, 0, batch=per * ns if per else 48, nstreams=ns)))
     else:
-        print(json.dumps({"rows": measure()}, indent=1))
+        print(json.dumps({"rows": measure(precision=precision)}, indent=1))
