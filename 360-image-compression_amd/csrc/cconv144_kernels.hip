@@ -121,8 +121,6 @@ struct ILay {
     static constexpr int ROWS = DC ? 5 : NT + 4, COLS = DC ? 16 * NT + 4 : 20, QPR = COLS / 4, PLANE = ROWS * COLS, TOFF = DC ? 16 : COLS;
     static constexpr int tap_off(int kh, int kw) { return DC ? (kh + kw) * COLS + kh : kh * COLS + kw; }
 };
-#define I144_R0 4                               // DC layout: zero diagonals before s = 0
-#define I144_C0 2                               // DC layout: zero columns before th = 0
 
 struct I144Args {
     const float *x, *packed, *bias, *act, *residual;

@@ -38,6 +38,77 @@ static int make_plan(PlanPtr &out, int channel, int ngroup, int nout, int ksz, i
     out.reset(p);
     return rc;
 }
+static int plan_of(int layer) { return layer == 0 ? 0 : (layer == 11 ? 2 : 1); }
+
+// The weights of a codec's 12-layer net, `nets` stacked copies of it: the plans, the generic kernels' packing, bias, PReLU slopes (every
+// layer but the last) and up to two packings of the codec's specialised kernels (xpack, see each codec).
+struct NetWeights {
+    const char *what, *setter;                 // (the error of an encode / decode before every layer has weights)
+    int nets;
+    PlanPtr plan[3];                           // first, hidden, last
+    DevBuf<float> packed[12], bias[12], act[12], xpack[2][12];
+    bool layer_set[12] = {};
+    int create(int ngroup, int cin, int hidden, int nout) {
+        return make_plan(plan[0], cin, ngroup, hidden, 5, 5) || make_plan(plan[1], hidden, ngroup, hidden, 5, 6) ||
+               make_plan(plan[2], hidden, ngroup, nout, 5, 6);
+    }
+    lic360_conv_plan *at(int layer) const { return plan[plan_of(layer)].get(); }
+    // Installs one layer: its buffers all or none (xfloats(p, k): floats per net of extra packing k, 0: none), the generic packing, the
+    // extra packings (xpack_fn(p)), bias and PReLU slopes.
+    template <class Floats, class Pack>
+    int set(void *stream, int layer, const float *weight, const float *b, const float *a, Floats xfloats, Pack xpack_fn) {
+        ARG_CHECK(layer >= 0 && layer < 12 && weight && b);
+        ARG_CHECK((a != nullptr) == (layer != 11));
+        lic360_conv_plan *p = at(layer);
+        const size_t nout = (size_t)nets * p->nout;
+        if (!packed[layer]) {
+            DevBuf<float> pk, bs, ac, x[2];
+            if (pk.alloc(nets * (size_t)lic360_conv_plan_packed_floats(p)) || bs.alloc(nout) || (a && ac.alloc(nout))) return 1;
+            for (int k = 0; k < 2; ++k)
+                if (const long n = xfloats(p, k)) { if (x[k].alloc(nets * (size_t)n)) return 1; }
+            packed[layer] = std::move(pk); bias[layer] = std::move(bs); act[layer] = std::move(ac);
+            for (int k = 0; k < 2; ++k) xpack[k][layer] = std::move(x[k]);
+        }
+        if (lic360_conv_pack(stream, p, weight, nets, packed[layer]) || xpack_fn(p)) return 1;
+        HIP_TRY(hipMemcpyAsync(bias[layer], b, nout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        if (a) HIP_TRY(hipMemcpyAsync(act[layer], a, nout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        layer_set[layer] = true;
+        return 0;
+    }
+};
+// the check every encode and decode of a codec starts with
+template <class Codec>
+static int check_ready(const Codec *c, int B) {
+    ARG_CHECK(c && B > 0 && B <= c->maxB);
+    for (int i = 0; i < 12; ++i)
+        if (!c->w.layer_set[i]) { lic360_set_error("%s layer %d has no weights (call %s)", c->w.what, i, c->w.setter); return 2; }
+    return 0;
+}
+// The 12 layers of a net in order: the first, five residual pairs (layer a = 1 + 2 blk reads the output of a - 1, a + 1 adds it back), the
+// last.  layer(l, in, residual, out) enqueues layer l; the walk stops at the first that fails.  buf: the encode order's three ping-pong
+// buffers (nbuf = 3) or the decode order's per-layer buffers (nbuf = 11); the last layer writes `last`.
+template <class F>
+static int net_walk(const float *x0, DevBuf<float> *buf, int nbuf, float *last, F layer) {
+    auto out = [&](int l) -> float * { return l == 11 ? last : buf[nbuf == 3 ? (l % 2 ? 1 : l % 4 ? 2 : 0) : l]; };
+    for (int l = 0; l < 12; ++l)
+        if (layer(l, l ? out(l - 1) : x0, l % 2 == 0 && l > 0 ? out(l - 2) : nullptr, out(l))) return 1;
+    return 0;
+}
+// the coding order (lic360_code_contex): idx [2][h * w] (row, column) per position, pidx [h + w] plane starts; both on the host and the device
+static int scan_order(int h, int w, std::vector<int> &h_idx, std::vector<int> &h_pidx, DevBuf<int> &d_idx, DevBuf<int> &d_pidx) {
+    h_idx.resize(2 * (size_t)h * w);
+    h_pidx.resize(h + w);
+    lic360_code_contex(h, w, h_idx.data(), h_pidx.data());
+    if (d_idx.alloc(h_idx.size()) || d_pidx.alloc(h_pidx.size())) return 1;
+    HIP_TRY(hipMemcpy(d_idx, h_idx.data(), h_idx.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pidx, h_pidx.data(), h_pidx.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+// a bitstream slot of `cap` bytes per image at `bytes`: DevBitSink and DevBits move whole dwords at bytes + b * cap
+static int check_slot(const uint8_t *bytes, long cap) {
+    ARG_CHECK(bytes && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0);
+    return 0;
+}
 
 enum { PROF_EC_FIRST, PROF_EC_HIDDEN, PROF_EC_LAST, PROF_ENC_TABLES, PROF_AC_ENCODE,
        PROF_DC_FIRST, PROF_DC_HIDDEN, PROF_DC_LAST, PROF_DEC_TABLES, PROF_DEC_PLANE, PROF_NCLS };
@@ -48,10 +119,8 @@ struct lic360_codec {
     int G, H, W, maxB, S, P, HW;
     int sk_rows, sk_pitch, sk_row0, sk_col0;
     int e_hp, e_wp, e_off;                     // encode activation planes: [e_hp][e_wp], cell (r, c) at [(r+e_off)*e_wp + c+e_off]
-    PlanPtr plan[3];                           // first, hidden, last
-    DevBuf<float> packed[12], bias[12], act[12];
-    DevBuf<float> packed4[12];                 // leaf-resident (4x4x1 MFMA) weight layout, when the shape allows it
-    DevBuf<float> packed16[12];                // 16x16x4 MFMA weight layout of the encode-order kernel (csrc/cconv16_kernels.hip)
+    NetWeights w{"codec", "lic360_codec_set_layer", 3};   // the GMM's weight, delta and mean nets; with use4, xpack[0]: the leaf-resident
+                                               // (4x4x1 MFMA) decode-order packing, xpack[1]: the 16x16x4 encode-order one (csrc/cconv16_kernels.hip)
     bool use4;                                 // the nets' shapes fit the specialised kernels (4x4x1 decode order, 16x16x4 encode order with the last layer
                                                // fused with the CDF tables); otherwise -- or under LIC360_FUSED_CONV=16 -- the generic kernels of cconv_kernels.hip
     int dc_mode = 0;                           // schedule switches of the decode kernel (LIC360_NOPACK, LIC360_DC_GSTEP), read from the environment once, at create
@@ -64,7 +133,6 @@ struct lic360_codec {
     DevBuf<AcDevState> d_state;
     DevBuf<uint4> d_tab;                       // per-plane CDF tables [maxB][tab_pitch][2] (k_dec_tables -> k_dec_plane)
     int tab_pitch = 0;
-    bool layer_set[12] = {};
     // Dead-cone skip (round 6, need.h): outputs no coded symbol can observe are not computed -- per-layer need maps from the mask, compacted task lists
     // for the encode-order kernels (layers 1..11), per-plane task records for the decode-order kernel (layers 1..11; batches of >= 16 images with
     // 8 | batch on images of at most 64 rows -- below that a list could only drop whole three-group tasks, which almost never happens, and the decode
@@ -105,8 +173,6 @@ static int prof_mark(lic360_codec *c, int cls, hipStream_t s) {
 }
 // brackets one launch (or launch group) of class CLS
 #define PROF(c, CLS, s, ...) do { prof_mark(c, CLS, s); __VA_ARGS__; prof_mark(c, CLS, s); } while (0)
-
-static int plan_of(int layer) { return layer == 0 ? 0 : (layer == 11 ? 2 : 1); }
 
 #define GRID_STRIDE(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
@@ -898,15 +964,11 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     ARG_CHECK(out && ngroup > 0 && ngroup < 128 && h > 0 && w > 0 && h < 4096 && w < 4096 && max_batch > 0);
     std::unique_ptr<lic360_codec> c(new lic360_codec());
     c->G = ngroup; c->H = h; c->W = w; c->maxB = max_batch; c->S = h + w - 1; c->P = h + w + ngroup - 2; c->HW = h * w;
-    if (make_plan(c->plan[0], ngroup * 1, ngroup, ngroup * 4, 5, 5) || make_plan(c->plan[1], ngroup * 4, ngroup, ngroup * 4, 5, 6) ||
-        make_plan(c->plan[2], ngroup * 4, ngroup, ngroup * 3, 5, 6)) return 1;
+    if (c->w.create(ngroup, ngroup, ngroup * 4, ngroup * 3)) return 1;
     const char *force = getenv("LIC360_FUSED_CONV");                  // "16" forces the generic 16x16x4 kernels (the fall-back path, kept tested)
-    c->use4 = lic360_conv4_supported(c->plan[0].get()) && lic360_conv4_supported(c->plan[1].get()) && lic360_conv4_supported(c->plan[2].get()) &&
-              lic360_conv16_supported(c->plan[0].get()) && lic360_conv16_supported(c->plan[1].get()) && lic360_conv16_supported(c->plan[2].get()) &&
-              !(force && force[0] == '1' && force[1] == '6');
-    c->h_idx.resize(2 * (size_t)c->HW);
-    c->h_pidx.resize(h + w);
-    lic360_code_contex(h, w, c->h_idx.data(), c->h_pidx.data());
+    c->use4 = !(force && force[0] == '1' && force[1] == '6');
+    for (const PlanPtr &p : c->w.plan) c->use4 = c->use4 && lic360_conv4_supported(p.get()) && lic360_conv16_supported(p.get());
+    if (scan_order(h, w, c->h_idx, c->h_pidx, c->d_idx, c->d_pidx)) return 1;
     c->h_plane_start.resize(c->P + 1);
     int acc = 0;
     for (int p = 0; p < c->P; ++p) {
@@ -917,9 +979,7 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     }
     c->h_plane_start[c->P] = acc;
     if (acc != ngroup * c->HW) { lic360_set_error("internal: plane schedule does not cover the latent"); return 1; }
-    if (c->d_idx.alloc(c->h_idx.size()) || c->d_pidx.alloc(c->h_pidx.size()) || c->d_plane_start.alloc(c->h_plane_start.size())) return 1;
-    HIP_TRY(hipMemcpy(c->d_idx, c->h_idx.data(), c->h_idx.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_pidx, c->h_pidx.data(), c->h_pidx.size() * 4, hipMemcpyHostToDevice));
+    if (c->d_plane_start.alloc(c->h_plane_start.size())) return 1;
     HIP_TRY(hipMemcpy(c->d_plane_start, c->h_plane_start.data(), c->h_plane_start.size() * 4, hipMemcpyHostToDevice));
     if (c->use4) { if (lic360_dc4_layout(h, w, &c->sk_rows, &c->sk_pitch, &c->sk_row0, &c->sk_col0)) return 1; }
     else { c->sk_rows = c->S; c->sk_pitch = h; c->sk_row0 = 0; c->sk_col0 = 0; }
@@ -969,26 +1029,15 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
 LIC360_API void lic360_codec_destroy(lic360_codec *c) { delete c; }
 
 LIC360_API int lic360_codec_set_layer(void *stream, lic360_codec *c, int layer, const float *weight, const float *bias, const float *act) {
-    ARG_CHECK(c && layer >= 0 && layer < 12 && weight && bias);
-    ARG_CHECK((act != nullptr) == (layer != 11));
-    lic360_conv_plan *p = c->plan[plan_of(layer)].get();
-    long nper = lic360_conv_plan_packed_floats(p);
-    if (!c->packed[layer]) {                                            // (all of the layer's buffers, or none)
-        DevBuf<float> pk, bs, ac, pk4, pk16;
-        if (pk.alloc(3 * (size_t)nper) || bs.alloc(3 * (size_t)p->nout) || (act && ac.alloc(3 * (size_t)p->nout)) ||
-            (c->use4 && (pk4.alloc(3 * (size_t)lic360_conv4_packed_floats(p)) || pk16.alloc(3 * (size_t)lic360_conv16_packed_floats(p))))) return 1;
-        c->packed[layer] = std::move(pk); c->bias[layer] = std::move(bs); c->act[layer] = std::move(ac);
-        c->packed4[layer] = std::move(pk4); c->packed16[layer] = std::move(pk16);
-    }
-    if (lic360_conv_pack(stream, p, weight, 3, c->packed[layer])) return 1;
-    if (c->use4 && lic360_conv4_pack(stream, p, weight, 3, c->packed4[layer])) return 1;
-    // (the fused last layer + CDF tables reads a packing of its own: five groups per block)
-    if (c->use4 && (layer == 11 ? lic360_conv16_pack_tables(stream, p, weight, 3, c->packed16[layer])
-                                : lic360_conv16_pack(stream, p, weight, 3, c->packed16[layer]))) return 1;
-    HIP_TRY(hipMemcpyAsync(c->bias[layer], bias, 3 * (size_t)p->nout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (act) HIP_TRY(hipMemcpyAsync(c->act[layer], act, 3 * (size_t)p->nout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    c->layer_set[layer] = true;
-    return 0;
+    ARG_CHECK(c);
+    return c->w.set(stream, layer, weight, bias, act,
+                    [&](const lic360_conv_plan *p, int k) { return !c->use4 ? 0 : k == 0 ? lic360_conv4_packed_floats(p) : lic360_conv16_packed_floats(p); },
+                    [&](lic360_conv_plan *p) {
+                        // (the fused last layer + CDF tables reads a packing of its own: five groups per block)
+                        return c->use4 && (lic360_conv4_pack(stream, p, weight, 3, c->w.xpack[0][layer]) ||
+                                           (layer == 11 ? lic360_conv16_pack_tables(stream, p, weight, 3, c->w.xpack[1][layer])
+                                                        : lic360_conv16_pack(stream, p, weight, 3, c->w.xpack[1][layer])));
+                    });
 }
 
 static bool coder_on_host(const lic360_codec *c, int B) {
@@ -1001,81 +1050,72 @@ LIC360_API int lic360_codec_set_coder(lic360_codec *c, int mode) {
     c->coder_mode = mode;
     return 0;
 }
-static int check_ready(const lic360_codec *c, int B) {
-    ARG_CHECK(c && B > 0 && B <= c->maxB);
-    for (int i = 0; i < 12; ++i)
-        if (!c->layer_set[i]) { lic360_set_error("codec layer %d has no weights (call lic360_codec_set_layer)", i); return 2; }
-    return 0;
-}
 
 LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *code, const float *mask, int B,
                                    uint8_t *bytes, long cap, int *nbytes, int *err) {
     if (check_ready(c, B)) return 2;
-    ARG_CHECK(code && mask && bytes && nbytes && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0);   // DevBitSink: dword stores at bytes + b*cap
+    ARG_CHECK(code && mask && nbytes && err);
+    if (check_slot(bytes, cap)) return 2;
     hipStream_t s = (hipStream_t)stream;
     const int G = c->G, H = c->H, W = c->W;
     const long total = (long)B * G * c->HW;
     hipLaunchKernelGGL(k_enc_prep, dim3(lic360_blocks(total, 4)), dim3(256), 0, s, code, mask, c->e_x0, total, H, W, c->e_hp, c->e_wp, c->e_off);
     LAUNCH_CHECK();
-    float *cur = c->e_buf[0], *t1 = c->e_buf[1], *nxt = c->e_buf[2];
     if (c->skip) {                                                      // need maps of this batch's masks, the live tasks of layers 1..11
         if (lic360_need_build(stream, mask, B, G, H, W, c->need, c->need_d, c->tmax)) return 1;
         if (lic360_ec_lists_build(stream, c->tmax, B, G, H, W, c->ecl, c->stats_on ? c->stats : nullptr)) return 1;
     }
-    auto ec = [&](int layer, const float *xin, const float *res, float *dst, int x_mod) -> int {
-        lic360_conv_plan *p = c->plan[plan_of(layer)].get();
-        if (c->use4 && c->skip && layer > 0)
-            return lic360_cconv16_ec_list(stream, p, xin, c->packed16[layer], c->bias[layer], c->act[layer], res, dst, 3 * B, H, W, 3, x_mod, c->e_ctr,
-                                          c->ecl.list + (size_t)layer * 8 * c->ecl.cap, c->ecl.cnt + layer * 8, c->ecl.cap);
-        if (c->use4) return lic360_cconv16_ec(stream, p, xin, c->packed16[layer], c->bias[layer], c->act[layer], res, dst, 3 * B, H, W, 3, x_mod, c->e_ctr);
-        return lic360_cconv_ec_ex(stream, p, xin, c->packed[layer], c->bias[layer], c->act[layer], res, dst, 3 * B, H, W, 3, x_mod);
-    };
-    int rc = 0;
-    PROF(c, PROF_EC_FIRST, s, rc |= ec(0, c->e_x0, nullptr, cur, B));
-    for (int blk = 0; blk < 5 && !rc; ++blk) {
-        int a = 1 + 2 * blk, b2 = 2 + 2 * blk;
-        PROF(c, PROF_EC_HIDDEN, s, rc |= ec(a, cur, nullptr, t1, 3 * B));
-        PROF(c, PROF_EC_HIDDEN, s, rc |= ec(b2, t1, cur, nxt, 3 * B));
-        float *tmp = cur; cur = nxt; nxt = tmp;
-    }
-    if (rc) return 1;
-    if (c->use4) {
-        // last layer + CDF tables in one kernel: the nets' outputs never reach HBM (no y buffer, no k_enc_tables)
-        if (c->skip) {
-            // a skipped (tile, group block) holds masked symbols only: their records are (0, 0) and nobody writes them
-            HIP_TRY(hipMemsetAsync(c->e_rec, 0, (size_t)B * G * c->HW * sizeof(uint2), s));
-            PROF(c, PROF_EC_LAST, s, rc |= lic360_cconv16_ec_tables_list(stream, c->plan[2].get(), cur, c->packed16[11], c->bias[11], code, mask, c->d_pidx, c->d_plane_start,
-                                                                         c->e_rec, B, H, W, c->e_ctr, c->ecl.list + (size_t)11 * 8 * c->ecl.cap, c->ecl.cnt + 11 * 8, c->ecl.cap));
-        } else
-        PROF(c, PROF_EC_LAST, s, rc |= lic360_cconv16_ec_tables(stream, c->plan[2].get(), cur, c->packed16[11], c->bias[11], code, mask, c->d_pidx,
-                                                                c->d_plane_start, c->e_rec, B, H, W, c->e_ctr));
-        if (rc) return 1;
-        if (coder_on_host(c, B)) {
-            PROF(c, PROF_AC_ENCODE, s, rc |= hl_encode(c, s, B, bytes, cap, nbytes, err));
-            return rc ? 1 : 0;
+    const NetWeights &nw = c->w;
+    auto conv = [&](int layer, const float *xin, const float *res, float *dst) -> int {
+        lic360_conv_plan *p = nw.at(layer);
+        const int x_mod = layer ? 3 * B : B;
+        const bool fused = c->use4 && layer == 11;        // last layer + CDF tables in one kernel: the nets' outputs never reach HBM (no y buffer, no k_enc_tables)
+        if (c->use4 && c->skip && layer > 0) {
+            const int *list = c->ecl.list + (size_t)layer * 8 * c->ecl.cap, *cnt = c->ecl.cnt + layer * 8;
+            if (fused)
+                return lic360_cconv16_ec_tables_list(stream, p, xin, nw.xpack[1][11], nw.bias[11], code, mask, c->d_pidx, c->d_plane_start, c->e_rec, B, H, W,
+                                                     c->e_ctr, list, cnt, c->ecl.cap);
+            return lic360_cconv16_ec_list(stream, p, xin, nw.xpack[1][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, x_mod, c->e_ctr,
+                                          list, cnt, c->ecl.cap);
         }
-        PROF(c, PROF_AC_ENCODE, s, hipLaunchKernelGGL(k_ac_encode, dim3(B), dim3(128), 0, s, c->e_rec, (long)G * c->HW, bytes, cap, nbytes, err));
+        if (fused) return lic360_cconv16_ec_tables(stream, p, xin, nw.xpack[1][11], nw.bias[11], code, mask, c->d_pidx, c->d_plane_start, c->e_rec, B, H, W, c->e_ctr);
+        if (c->use4) return lic360_cconv16_ec(stream, p, xin, nw.xpack[1][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, x_mod, c->e_ctr);
+        return lic360_cconv_ec_ex(stream, p, xin, nw.packed[layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, x_mod);
+    };
+    auto ec = [&](int layer, const float *xin, const float *res, float *dst) -> int {
+        // a skipped (tile, group block) of the fused last layer holds masked symbols only: their records are (0, 0) and nobody writes them
+        if (layer == 11 && c->use4 && c->skip) HIP_TRY(hipMemsetAsync(c->e_rec, 0, (size_t)B * G * c->HW * sizeof(uint2), s));
+        int rc = 0;
+        PROF(c, PROF_EC_FIRST + plan_of(layer), s, rc = conv(layer, xin, res, dst));
+        return rc;
+    };
+    if (net_walk(c->e_x0, c->e_buf, 3, c->e_buf[1], ec)) return 1;
+    if (!c->use4) {
+        PROF(c, PROF_ENC_TABLES, s, hipLaunchKernelGGL(k_enc_tables, dim3(lic360_blocks(total, 1)), dim3(256), 0, s, c->e_buf[1], code, mask, c->d_pidx,
+                                                       c->d_plane_start, c->e_rec, B, G, H, W, c->e_hp, c->e_wp, c->e_off));
         LAUNCH_CHECK();
-        return 0;
     }
-    PROF(c, PROF_EC_LAST, s, rc |= ec(11, cur, nullptr, t1, 3 * B));
-    if (rc) return 1;
-    PROF(c, PROF_ENC_TABLES, s, hipLaunchKernelGGL(k_enc_tables, dim3(lic360_blocks(total, 1)), dim3(256), 0, s, t1, code, mask, c->d_pidx,
-                                                   c->d_plane_start, c->e_rec, B, G, H, W, c->e_hp, c->e_wp, c->e_off));
-    LAUNCH_CHECK();
+    // the serial coder: host threads, or one wave per image
     if (coder_on_host(c, B)) {
-        PROF(c, PROF_AC_ENCODE, s, rc |= hl_encode(c, s, B, bytes, cap, nbytes, err));
-        return rc ? 1 : 0;
+        int rc = 0;
+        PROF(c, PROF_AC_ENCODE, s, rc = hl_encode(c, s, B, bytes, cap, nbytes, err));
+        return rc;
     }
     PROF(c, PROF_AC_ENCODE, s, hipLaunchKernelGGL(k_ac_encode, dim3(B), dim3(128), 0, s, c->e_rec, (long)G * c->HW, bytes, cap, nbytes, err));
     LAUNCH_CHECK();
     return 0;
 }
 
+// the checks a latent decode starts with (lic360_codec_decode_gated runs them before it consumes its ticket)
+static int check_decode(const lic360_codec *c, const uint8_t *bytes, long cap, const int *nbytes, const float *mask, int B, const float *code_out,
+                        const int *err) {
+    if (check_ready(c, B)) return 2;
+    ARG_CHECK(nbytes && mask && code_out && err);
+    return check_slot(bytes, cap);
+}
 static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes, long cap, const int *nbytes,
                              const float *mask, int B, float *code_out, int *err, const HipEvent *gate, int n_gate, int gate_stride) {
-    if (check_ready(c, B)) return 2;
-    ARG_CHECK(bytes && nbytes && mask && code_out && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0);
+    if (const int rc = check_decode(c, bytes, cap, nbytes, mask, B, code_out, err)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int G = c->G, H = c->H, W = c->W;
     const int *pih = c->h_pidx.data();
@@ -1124,30 +1164,27 @@ static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes
         if (lic360_need_build(stream, mask, B, G, H, W, c->need, c->need_d, c->tmax)) return 1;
         if (lic360_dc_lists_build(stream, c->need_d, B, G, H, W, c->dcl, c->stats_on ? c->stats + NEED_LAYERS * NEED_STAT_G : nullptr)) return 1;
     }
-    auto dc = [&](int layer, const float *xin, const float *res, float *dst, int x_mod, int p) -> int {
-        lic360_conv_plan *pl = c->plan[plan_of(layer)].get();
+    const NetWeights &nw = c->w;
+    auto conv = [&](int layer, const float *xin, const float *res, float *dst, int p) -> int {
+        lic360_conv_plan *pl = nw.at(layer);
+        const int x_mod = layer ? 3 * B : B;
         if (lists && layer > 0) {
             const size_t li = ((size_t)layer * c->P + p) * 8;
-            return lic360_cconv4_dc_plane_list(stream, pl, xin, c->packed4[layer], c->bias[layer], c->act[layer], res, dst, 3 * B, H, W, 3, p, x_mod,
+            return lic360_cconv4_dc_plane_list(stream, pl, xin, nw.xpack[0][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, p, x_mod,
                                                c->dcl.list + li * c->dcl.cap, c->dcl.cnt + li, c->dcl.cap);
         }
-        if (c->use4) return lic360_cconv4_dc_plane_mode(stream, pl, xin, c->packed4[layer], c->bias[layer], c->act[layer], res, dst, 3 * B, H, W, 3, p, x_mod, c->dc_mode);
-        return lic360_cconv_dc_plane_ex(stream, pl, xin, c->packed[layer], c->bias[layer], c->act[layer], res, dst, 3 * B, H, W, 3,
+        if (c->use4) return lic360_cconv4_dc_plane_mode(stream, pl, xin, nw.xpack[0][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, p, x_mod, c->dc_mode);
+        return lic360_cconv_dc_plane_ex(stream, pl, xin, nw.packed[layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3,
                                         c->d_idx, c->d_pidx, pih, p, x_mod, 1);
     };
     int gate_q = -1;
     for (int p = 0; p < c->P; ++p) {
         // plane p of all 12 layers (x0 already holds planes < p)
-        int rc = 0;
-        PROF(c, PROF_DC_FIRST, s, rc |= dc(0, c->d_x0, nullptr, c->d_act[0], B, p));
-        for (int blk = 0; blk < 5 && !rc; ++blk) {
-            int a = 1 + 2 * blk, b2 = 2 + 2 * blk;
-            PROF(c, PROF_DC_HIDDEN, s, rc |= dc(a, c->d_act[a - 1], nullptr, c->d_act[a], 3 * B, p));
-            PROF(c, PROF_DC_HIDDEN, s, rc |= dc(b2, c->d_act[a], c->d_act[a - 1], c->d_act[b2], 3 * B, p));
-        }
-        if (rc) return 1;
-        PROF(c, PROF_DC_LAST, s, rc |= dc(11, c->d_act[10], nullptr, c->d_y, 3 * B, p));
-        if (rc) return 1;
+        if (net_walk(c->d_x0, c->d_act, 11, c->d_y, [&](int layer, const float *xin, const float *res, float *dst) {
+                int rc = 0;
+                PROF(c, PROF_DC_FIRST + plan_of(layer), s, rc = conv(layer, xin, res, dst, p));
+                return rc;
+            })) return 1;
         int start, len;
         lic360_plane_window(p, G, H, W, pih, &start, &len);
         if (len <= 0) continue;
@@ -1191,9 +1228,7 @@ LIC360_API int lic360_codec_decode(void *stream, lic360_codec *c, const uint8_t 
 struct lic360_impcodec {
     int H, W, HW, P, cpg, nsym, maxB;
     float sc;
-    PlanPtr plan[3];
-    DevBuf<float> packed[12], bias[12], act[12];
-    bool layer_set[12] = {};
+    NetWeights w{"importance codec", "lic360_impcodec_set_layer", 1};   // with use144, xpack[0]: the 144-channel packing of layers 1..11
     std::vector<int> h_idx, h_pidx;
     DevBuf<int> d_idx, d_pidx;
     DevBuf<float> e_x0, e_buf[3];
@@ -1202,7 +1237,6 @@ struct lic360_impcodec {
     // leaf-resident 16x16x4 kernels for the 144-channel layers (csrc/cconv144_kernels.hip): encode on zero-haloed NCHW planes,
     // decode on zero-padded diagonal-major planes [rows = sk_rows][sk_pitch], cell (th, tw) at (th + tw + sk_row0, th + sk_col0)
     bool use144 = false;
-    DevBuf<float> packed144[12];
     int e_hp = 0, e_wp = 0;
     DevBuf<float> e_pad[3], e_plain;
     int sk_rows, sk_pitch, sk_row0, sk_col0;
@@ -1402,21 +1436,17 @@ LIC360_API int lic360_impcodec_create(int h, int w, int hidden_channels, int nsy
     std::unique_ptr<lic360_impcodec> c(new lic360_impcodec());
     c->H = h; c->W = w; c->HW = h * w; c->P = h + w - 1; c->cpg = hidden_channels; c->nsym = nsym; c->maxB = max_batch;
     c->sc = 2.0f / (float)(nsym - 2);
-    if (make_plan(c->plan[0], 1, 1, hidden_channels, 5, 5) || make_plan(c->plan[1], hidden_channels, 1, hidden_channels, 5, 6) ||
-        make_plan(c->plan[2], hidden_channels, 1, nsym, 5, 6)) return 1;
-    c->h_idx.resize(2 * (size_t)c->HW);
-    c->h_pidx.resize(h + w);
-    lic360_code_contex(h, w, c->h_idx.data(), c->h_pidx.data());
+    if (c->w.create(1, 1, hidden_channels, nsym) || scan_order(h, w, c->h_idx, c->h_pidx, c->d_idx, c->d_pidx)) return 1;
     c->tab_pitch = ((h < w ? h : w) + 63) / 64 * 64;
     const size_t B = max_batch, HW = c->HW, C = hidden_channels, CE = hidden_channels > nsym ? hidden_channels : nsym;   // the last layer writes nsym planes
-    if (c->d_idx.alloc(c->h_idx.size()) || c->d_pidx.alloc(c->h_pidx.size()) || c->e_x0.alloc(B * HW)) return 1;
+    if (c->e_x0.alloc(B * HW)) return 1;
     for (DevBuf<float> &b : c->e_buf) if (b.alloc(B * CE * HW)) return 1;
     if (c->e_rec.alloc(B * HW)) return 1;
     // 144-channel layers on the leaf-resident 16x16x4 kernels (other widths keep the generic kernels)
-    c->use144 = lic360_conv144_supported(c->plan[1].get()) && lic360_conv144_supported(c->plan[2].get());
+    c->use144 = lic360_conv144_supported(c->w.plan[1].get()) && lic360_conv144_supported(c->w.plan[2].get());
     if (c->use144) {
         if (lic360_ec144_layout(h, w, &c->e_hp, &c->e_wp) || lic360_dc144_layout(h, w, &c->sk_rows, &c->sk_pitch)) return 1;
-        c->sk_row0 = 4; c->sk_col0 = 2;
+        c->sk_row0 = I144_R0; c->sk_col0 = I144_C0;
         for (DevBuf<float> &b : c->e_pad) if (b.alloc(B * C * (size_t)c->e_hp * c->e_wp)) return 1;
         if (c->e_plain.alloc(B * CE * HW)) return 1;
         for (int i = 0; i < 3; ++i) HIP_TRY(hipMemset(c->e_pad[i], 0, B * C * (size_t)c->e_hp * c->e_wp * 4));   // the halo stays zero
@@ -1425,8 +1455,6 @@ LIC360_API int lic360_impcodec_create(int h, int w, int hidden_channels, int nsy
     if (c->d_x0.alloc(B * SK)) return 1;
     for (DevBuf<float> &b : c->d_act) if (b.alloc(B * C * SK)) return 1;
     if (c->d_y.alloc(B * (size_t)nsym * SK) || c->d_tab.alloc(B * (size_t)c->tab_pitch * IMP_TW) || c->d_state.alloc(B)) return 1;
-    HIP_TRY(hipMemcpy(c->d_idx, c->h_idx.data(), c->h_idx.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_pidx, c->h_pidx.data(), c->h_pidx.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(c->d_x0, 0, B * SK * 4));
     for (int i = 0; i < 11; ++i) HIP_TRY(hipMemset(c->d_act[i], 0, B * C * SK * 4));
     HIP_TRY(hipMemset(c->d_y, 0, B * (size_t)nsym * SK * 4));
@@ -1435,73 +1463,38 @@ LIC360_API int lic360_impcodec_create(int h, int w, int hidden_channels, int nsy
 }
 LIC360_API void lic360_impcodec_destroy(lic360_impcodec *c) { delete c; }
 LIC360_API int lic360_impcodec_set_layer(void *stream, lic360_impcodec *c, int layer, const float *weight, const float *bias, const float *act) {
-    ARG_CHECK(c && layer >= 0 && layer < 12 && weight && bias);
-    ARG_CHECK((act != nullptr) == (layer != 11));
-    lic360_conv_plan *p = c->plan[plan_of(layer)].get();
-    if (!c->packed[layer]) {                                            // (all of the layer's buffers, or none)
-        DevBuf<float> pk, bs, ac, pk144;
-        if (pk.alloc((size_t)lic360_conv_plan_packed_floats(p)) || bs.alloc((size_t)p->nout) || (act && ac.alloc((size_t)p->nout)) ||
-            (c->use144 && layer > 0 && pk144.alloc((size_t)lic360_conv144_packed_floats(p)))) return 1;
-        c->packed[layer] = std::move(pk); c->bias[layer] = std::move(bs); c->act[layer] = std::move(ac); c->packed144[layer] = std::move(pk144);
-    }
-    if (lic360_conv_pack(stream, p, weight, 1, c->packed[layer])) return 1;
-    if (c->use144 && layer > 0 && lic360_conv144_pack(stream, p, weight, c->packed144[layer])) return 1;
-    HIP_TRY(hipMemcpyAsync(c->bias[layer], bias, (size_t)p->nout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (act) HIP_TRY(hipMemcpyAsync(c->act[layer], act, (size_t)p->nout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    c->layer_set[layer] = true;
-    return 0;
-}
-static int imp_ready(const lic360_impcodec *c, int B) {
-    ARG_CHECK(c && B > 0 && B <= c->maxB);
-    for (int i = 0; i < 12; ++i)
-        if (!c->layer_set[i]) { lic360_set_error("importance codec layer %d has no weights (call lic360_impcodec_set_layer)", i); return 2; }
-    return 0;
+    ARG_CHECK(c);
+    const bool x144 = c->use144 && layer > 0;
+    return c->w.set(stream, layer, weight, bias, act, [&](const lic360_conv_plan *p, int k) { return x144 && k == 0 ? lic360_conv144_packed_floats(p) : 0; },
+                    [&](lic360_conv_plan *p) { return x144 && lic360_conv144_pack(stream, p, weight, c->w.xpack[0][layer]); });
 }
 LIC360_API int lic360_impcodec_encode(void *stream, lic360_impcodec *c, const float *levels, int B, uint8_t *bytes, long cap, int *nbytes, int *err) {
-    if (imp_ready(c, B)) return 2;
-    ARG_CHECK(levels && bytes && nbytes && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0);
+    if (check_ready(c, B)) return 2;
+    ARG_CHECK(levels && nbytes && err);
+    if (check_slot(bytes, cap)) return 2;
     hipStream_t s = (hipStream_t)stream;
     const int H = c->H, W = c->W;
     const long total = (long)B * c->HW;
     hipLaunchKernelGGL(k_imp_prep, dim3(lic360_blocks(total, 4)), dim3(256), 0, s, levels, c->e_x0, total, c->sc);
     LAUNCH_CHECK();
-    if (c->use144) {
-        // layer 0 (1 -> 144) on the generic kernel into plain NCHW, copied into the zero-haloed planes; layers 1..10 haloed -> haloed;
-        // layer 11 (144 -> nsym) haloed -> plain NCHW for the table kernel
-        const long PLh = (long)c->e_hp * c->e_wp;
-        if (lic360_cconv_ec_ex(stream, c->plan[0].get(), c->e_x0, c->packed[0], c->bias[0], c->act[0], nullptr, c->e_plain, B, H, W, 1, B)) return 1;
-        hipLaunchKernelGGL(k_imp_halo, dim3(lic360_blocks((long)B * c->cpg * c->HW, 4)), dim3(256), 0, s, c->e_plain, c->e_pad[0], (long)B * c->cpg * c->HW, H, W, c->e_hp, c->e_wp);
-        LAUNCH_CHECK();
-        float *cur = c->e_pad[0], *t1 = c->e_pad[1], *nxt = c->e_pad[2];
-        auto ec = [&](int layer, const float *xin, const float *res, float *dst) -> int {
-            return lic360_cconv144_ec(stream, c->plan[1].get(), xin, c->packed144[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, PLh, c->e_wp, 2);
-        };
-        for (int blk = 0; blk < 5; ++blk) {
-            if (ec(1 + 2 * blk, cur, nullptr, t1)) return 1;
-            if (ec(2 + 2 * blk, t1, cur, nxt)) return 1;
-            float *tmp = cur; cur = nxt; nxt = tmp;
-        }
-        if (lic360_cconv144_ec(stream, c->plan[2].get(), cur, c->packed144[11], c->bias[11], nullptr, nullptr, c->e_plain, B, H, W, (long)c->HW, W, 0)) return 1;
-        if (c->nsym == IMP_NSYM_FAST) hipLaunchKernelGGL(k_imp_enc_tables<true>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, c->e_plain, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
-        else hipLaunchKernelGGL(k_imp_enc_tables<false>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, c->e_plain, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_ac_encode, dim3(B), dim3(128), 0, s, c->e_rec, (long)c->HW, bytes, cap, nbytes, err);
-        LAUNCH_CHECK();
-        return 0;
-    }
-    float *cur = c->e_buf[0], *t1 = c->e_buf[1], *nxt = c->e_buf[2];
+    const NetWeights &nw = c->w;
     auto ec = [&](int layer, const float *xin, const float *res, float *dst) -> int {
-        return lic360_cconv_ec_ex(stream, c->plan[plan_of(layer)].get(), xin, c->packed[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, 1, B);
+        if (!c->use144) return lic360_cconv_ec_ex(stream, nw.at(layer), xin, nw.packed[layer], nw.bias[layer], nw.act[layer], res, dst, B, H, W, 1, B);
+        // 144 channels: layer 0 (1 -> 144) on the generic kernel into plain NCHW, copied into the zero-haloed planes; layers 1..10 haloed -> haloed;
+        // layer 11 (144 -> nsym) haloed -> plain NCHW for the table kernel
+        if (layer == 0) {
+            if (lic360_cconv_ec_ex(stream, nw.at(0), xin, nw.packed[0], nw.bias[0], nw.act[0], nullptr, c->e_plain, B, H, W, 1, B)) return 1;
+            hipLaunchKernelGGL(k_imp_halo, dim3(lic360_blocks((long)B * c->cpg * c->HW, 4)), dim3(256), 0, s, c->e_plain, dst, (long)B * c->cpg * c->HW, H, W, c->e_hp, c->e_wp);
+            LAUNCH_CHECK();
+            return 0;
+        }
+        if (layer == 11) return lic360_cconv144_ec(stream, nw.at(11), xin, nw.xpack[0][11], nw.bias[11], nullptr, nullptr, dst, B, H, W, (long)c->HW, W, 0);
+        return lic360_cconv144_ec(stream, nw.at(layer), xin, nw.xpack[0][layer], nw.bias[layer], nw.act[layer], res, dst, B, H, W, (long)c->e_hp * c->e_wp, c->e_wp, 2);
     };
-    if (ec(0, c->e_x0, nullptr, cur)) return 1;
-    for (int blk = 0; blk < 5; ++blk) {
-        if (ec(1 + 2 * blk, cur, nullptr, t1)) return 1;
-        if (ec(2 + 2 * blk, t1, cur, nxt)) return 1;
-        float *tmp = cur; cur = nxt; nxt = tmp;
-    }
-    if (ec(11, cur, nullptr, t1)) return 1;                                         // [B, nsym, H, W] (uses the first nsym planes of the buffer)
-    if (c->nsym == IMP_NSYM_FAST) hipLaunchKernelGGL(k_imp_enc_tables<true>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, t1, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
-    else hipLaunchKernelGGL(k_imp_enc_tables<false>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, t1, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
+    float *y = c->use144 ? c->e_plain : c->e_buf[1];                               // [B, nsym, H, W] (the generic path uses the first nsym planes of the buffer)
+    if (net_walk(c->e_x0, c->use144 ? c->e_pad : c->e_buf, 3, y, ec)) return 1;
+    if (c->nsym == IMP_NSYM_FAST) hipLaunchKernelGGL(k_imp_enc_tables<true>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, y, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
+    else hipLaunchKernelGGL(k_imp_enc_tables<false>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, y, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_ac_encode, dim3(B), dim3(128), 0, s, c->e_rec, (long)c->HW, bytes, cap, nbytes, err);
     LAUNCH_CHECK();
@@ -1550,30 +1543,25 @@ __global__ void k_imp_mask_plane(const ImpMaskPlaneArgs a) {
 }
 static int impcodec_decode_impl(void *stream, lic360_impcodec *c, const uint8_t *bytes, long cap, const int *nbytes, int B,
                                 float *levels_out, int *err, float *mask_out, int mask_c, int stride) {
-    if (imp_ready(c, B)) return 2;
-    ARG_CHECK(bytes && nbytes && levels_out && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0);
+    if (check_ready(c, B)) return 2;
+    ARG_CHECK(nbytes && levels_out && err);
+    if (check_slot(bytes, cap)) return 2;
     hipStream_t s = (hipStream_t)stream;
     const int H = c->H, W = c->W;
     hipLaunchKernelGGL(k_dec_init, dim3((B + 63) / 64), dim3(64), 0, s, bytes, cap, nbytes, c->d_state, B);
     LAUNCH_CHECK();
     const int *pih = c->h_pidx.data();
     const long SK = (long)c->sk_rows * c->sk_pitch, off0 = (long)c->sk_row0 * c->sk_pitch + c->sk_col0;
-    auto dc = [&](int layer, const float *xin, const float *res, float *dst, int p) -> int {
-        if (c->use144 && layer > 0)
-            return lic360_cconv144_dc_plane(stream, c->plan[plan_of(layer)].get(), xin, c->packed144[layer], c->bias[layer], c->act[layer], res, dst, B, H, W, p);
-        // generic kernel on the diagonal-major planes: cell (th, tw) at th * (pitch + 1) + tw * pitch from the layout's origin
-        return lic360_cconv_dc_plane_strided(stream, c->plan[plan_of(layer)].get(), xin + off0, c->packed[layer], c->bias[layer], c->act[layer],
-                                             res ? res + off0 : nullptr, dst + off0, B, H, W, 1, c->d_idx, c->d_pidx, pih, p, B,
-                                             SK, c->sk_pitch + 1, c->sk_pitch, SK, c->sk_pitch + 1, c->sk_pitch);
-    };
+    const NetWeights &nw = c->w;
     for (int p = 0; p < c->P; ++p) {
-        if (dc(0, c->d_x0, nullptr, c->d_act[0], p)) return 1;
-        for (int blk = 0; blk < 5; ++blk) {
-            const int a = 1 + 2 * blk, b2 = 2 + 2 * blk;
-            if (dc(a, c->d_act[a - 1], nullptr, c->d_act[a], p)) return 1;
-            if (dc(b2, c->d_act[a], c->d_act[a - 1], c->d_act[b2], p)) return 1;
-        }
-        if (dc(11, c->d_act[10], nullptr, c->d_y, p)) return 1;
+        if (net_walk(c->d_x0, c->d_act, 11, c->d_y, [&](int layer, const float *xin, const float *res, float *dst) -> int {
+                if (c->use144 && layer > 0)
+                    return lic360_cconv144_dc_plane(stream, nw.at(layer), xin, nw.xpack[0][layer], nw.bias[layer], nw.act[layer], res, dst, B, H, W, p);
+                // generic kernel on the diagonal-major planes: cell (th, tw) at th * (pitch + 1) + tw * pitch from the layout's origin
+                return lic360_cconv_dc_plane_strided(stream, nw.at(layer), xin + off0, nw.packed[layer], nw.bias[layer], nw.act[layer],
+                                                     res ? res + off0 : nullptr, dst + off0, B, H, W, 1, c->d_idx, c->d_pidx, pih, p, B,
+                                                     SK, c->sk_pitch + 1, c->sk_pitch, SK, c->sk_pitch + 1, c->sk_pitch);
+            })) return 1;
         const int start = pih[p], len = pih[p + 1] - pih[p];
         if (len <= 0) continue;
         if (c->nsym == IMP_NSYM_FAST)
@@ -1652,8 +1640,7 @@ LIC360_API int lic360_codec_decode_gated(void *stream, lic360_codec *c, const ui
         return 2;
     }
     // a call that is rejected for its own arguments must not burn the ticket: the checks codec_decode_impl starts with, first
-    if (check_ready(c, B)) return 2;
-    ARG_CHECK(bytes && nbytes && mask && code_out && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0);
+    if (const int rc = check_decode(c, bytes, cap, nbytes, mask, B, code_out, err)) return rc;
     map_codec->gate_armed = false;
     return codec_decode_impl(stream, c, bytes, cap, nbytes, mask, B, code_out, err, map_codec->plane_ev.data(), map_codec->P,
                              map_codec->gate_stride);
@@ -1698,8 +1685,8 @@ __global__ void k_test_tabn(const int *__restrict__ tables, int ncode, long star
 
 LIC360_API int lic360_devcoder_encode(void *stream, const int *tables, int ncode, const int *labels, const float *mask, long n,
                                       uint8_t *bytes, long cap, int *nbytes, int *err) {
-    ARG_CHECK(ncode >= 1 && n >= 0 && bytes && nbytes && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 && ((uintptr_t)bytes & 3) == 0 &&
-              (n == 0 || (tables && labels)));
+    ARG_CHECK(ncode >= 1 && n >= 0 && nbytes && err && (n == 0 || (tables && labels)));
+    if (check_slot(bytes, cap)) return 2;
     hipStream_t s = (hipStream_t)stream;
     DevBuf<uint2> rec;
     if (rec.alloc((size_t)n)) return 1;
@@ -1718,8 +1705,8 @@ LIC360_API int lic360_devcoder_encode(void *stream, const int *tables, int ncode
 // uint4 + coded flag), any other alphabet (< 64) k_imp_dec_plane (one table entry per lane).  out[i] = symbol, 0 where masked.
 LIC360_API int lic360_devcoder_decode(void *stream, const int *tables, int ncode, const float *mask, long n, int chunk,
                                       const uint8_t *bytes, long cap, const int *nbytes, float *out, int *err) {
-    ARG_CHECK(ncode >= 1 && ncode < IMP_TW && n >= 0 && chunk > 0 && bytes && nbytes && out && err && cap > 0 && cap < (1L << 31) && cap % 4 == 0 &&
-              ((uintptr_t)bytes & 3) == 0 && (n == 0 || tables) && (ncode == 8 || !mask));
+    ARG_CHECK(ncode >= 1 && ncode < IMP_TW && n >= 0 && chunk > 0 && nbytes && out && err && (n == 0 || tables) && (ncode == 8 || !mask));
+    if (check_slot(bytes, cap)) return 2;
     hipStream_t s = (hipStream_t)stream;
     DevBuf<AcDevState> st;
     DevBuf<uint4> tab8;

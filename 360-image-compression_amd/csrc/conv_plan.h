@@ -18,6 +18,9 @@ struct lic360_conv_plan {
     DevBuf<int> d_mt_rec_start, d_leaf_cnt, d_term, d_wsrc, d_mt_glo, d_mt_ghi;    // device copies of the arrays above
 };
 static const int LIC360_REC_PAD = 4;       // records readable past the end (software prefetch)
+// origin of the 144-channel kernels' decode-order layout (lic360_dc144_layout): cell (th, tw) at row th + tw + I144_R0, column th + I144_C0
+#define I144_R0 4                               // zero diagonals before s = 0
+#define I144_C0 2                               // zero columns before th = 0
 
 // internal entries shared between translation units (hidden visibility; not part of include/lic360_hip.h)
 int lic360_cconv4_dc_plane_mode(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,

@@ -13,30 +13,72 @@ import lic360
 from lic360 import _lib, _chk, _p, _stream, Lic360Error
 
 
+def _net_modules(drv):
+    """The 12 layers of a driver's net (state_dict keys net.N.*) in order: net.0, conv1 and conv2 of the residual blocks net.1..5, net.6."""
+    return [drv.net[0]] + [m for i in range(1, 6) for m in (drv.net[i].conv1, drv.net[i].conv2)] + [drv.net[6]]
 
-class FusedCodec(object):
-    def __init__(self, ngroup, h, w, max_batch, device=0, cap_bytes=None):
-        self.G, self.H, self.W, self.maxB, self.device = int(ngroup), int(h), int(w), int(max_batch), int(device)
-        # worst case of this coder is < 2.1 bytes/symbol (16-bit CDF, frequency >= 1); 1 byte/symbol is ample for
-        # any real table and overflow is reported through err[] rather than written out of bounds
-        self.cap = int(cap_bytes) if cap_bytes else max(4096, self.G * self.H * self.W)
-        self.cap = (self.cap + 3) // 4 * 4              # streams start word-aligned (the device bit reader fetches words)
+
+class _FusedBase(object):
+    """The host half both codecs share: the C handle and the device bitstream slots bytes / nbytes / err."""
+
+    def _open(self, create, args, cap):
+        self.cap = (int(cap) + 3) // 4 * 4              # streams start word-aligned (the device bit reader fetches words)
         self._h = C.c_void_p(0)
         with torch.cuda.device(self.device):
-            _chk(_lib.lic360_codec_create(self.G, self.H, self.W, self.maxB, C.byref(self._h)))
+            _chk(create(*args, C.byref(self._h)))
         dev = "cuda:%d" % self.device
         self.bytes = torch.zeros((self.maxB, self.cap), dtype=torch.uint8, device=dev)
         self.nbytes = torch.zeros((self.maxB,), dtype=torch.int32, device=dev)
         self.err = torch.zeros((self.maxB,), dtype=torch.int32, device=dev)
-        self.code_out = torch.zeros((self.maxB, self.G, self.H, self.W), dtype=torch.float32, device=dev)
+        return dev
 
     def __del__(self):
         try:
             if self._h:
-                _lib.lic360_codec_destroy(self._h)
+                self._destroy(self._h)
                 self._h = None
         except Exception:
             pass
+
+    def _read_streams(self, b):
+        """the bitstreams of the encode of b images just queued, as a list of `bytes`"""
+        nb = self.nbytes[:b].cpu().tolist()
+        er = self.err[:b].cpu().tolist()
+        if any(er):
+            raise Lic360Error("arithmetic encoder fault / capacity overflow: %s" % er)
+        host = self.bytes[:b].cpu()
+        return [bytes(host[i, :nb[i]].numpy().tobytes()) for i in range(b)]
+
+    def _stage_streams(self, streams):
+        """host bitstreams -> the device slots; returns their number"""
+        host = torch.zeros((self.maxB, self.cap), dtype=torch.uint8)
+        nb = torch.zeros((self.maxB,), dtype=torch.int32)
+        for i, s in enumerate(streams):
+            if len(s) > self.cap:
+                raise Lic360Error("bitstream %d longer than the codec capacity" % i)
+            host[i, :len(s)] = torch.frombuffer(bytearray(s), dtype=torch.uint8)
+            nb[i] = len(s)
+        self.bytes.copy_(host)
+        self.nbytes.copy_(nb)
+        return len(streams)
+
+    def _decoded(self, out, b):
+        """a copy of the decode `out` of b images, once err[] reports no fault"""
+        out = out.clone()
+        if int(self.err[:b].abs().sum().item()):
+            raise Lic360Error("arithmetic decoder fault (corrupt stream?): %s" % self.err[:b].cpu().tolist())
+        return out
+
+
+class FusedCodec(_FusedBase):
+    _destroy = staticmethod(_lib.lic360_codec_destroy)
+
+    def __init__(self, ngroup, h, w, max_batch, device=0, cap_bytes=None):
+        self.G, self.H, self.W, self.maxB, self.device = int(ngroup), int(h), int(w), int(max_batch), int(device)
+        # worst case of this coder is < 2.1 bytes/symbol (16-bit CDF, frequency >= 1); 1 byte/symbol is ample for
+        # any real table and overflow is reported through err[] rather than written out of bounds
+        dev = self._open(_lib.lic360_codec_create, (self.G, self.H, self.W, self.maxB), cap_bytes or max(4096, self.G * self.H * self.W))
+        self.code_out = torch.zeros((self.maxB, self.G, self.H, self.W), dtype=torch.float32, device=dev)
 
     # ---- parameters -------------------------------------------------------------------------------
     def set_layer(self, layer, weight, bias, act=None):
@@ -47,11 +89,7 @@ class FusedCodec(object):
 
     def load_from_driver(self, drv):
         """Take the 12 batched layers of an EntEncoderFast / EntDecoder (state_dict keys net.N.*)."""
-        mods = [drv.net[0]]
-        for i in range(1, 6):
-            mods += [drv.net[i].conv1, drv.net[i].conv2]
-        mods.append(drv.net[6])
-        for i, m in enumerate(mods):
+        for i, m in enumerate(_net_modules(drv)):
             self.set_layer(i, m.weight.data.contiguous(), m.bias.data.contiguous(), None if m.relu is None else m.relu.data.contiguous())
 
     def load_layers(self, layers):
@@ -97,29 +135,11 @@ class FusedCodec(object):
 
     def encode(self, code, mask):
         """-> list of `bytes`, one bitstream per image (what the reference writes to `<code>`)."""
-        b = self.encode_async(code, mask)
-        nb = self.nbytes[:b].cpu().tolist()
-        er = self.err[:b].cpu().tolist()
-        if any(er):
-            raise Lic360Error("arithmetic encoder fault / capacity overflow: %s" % er)
-        host = self.bytes[:b].cpu()
-        return [bytes(host[i, :nb[i]].numpy().tobytes()) for i in range(b)]
+        return self._read_streams(self.encode_async(code, mask))
 
     def decode(self, streams, mask):
-        b = len(streams)
-        host = torch.zeros((self.maxB, self.cap), dtype=torch.uint8)
-        nb = torch.zeros((self.maxB,), dtype=torch.int32)
-        for i, s in enumerate(streams):
-            if len(s) > self.cap:
-                raise Lic360Error("bitstream %d longer than the codec capacity" % i)
-            host[i, :len(s)] = torch.frombuffer(bytearray(s), dtype=torch.uint8)
-            nb[i] = len(s)
-        self.bytes.copy_(host)
-        self.nbytes.copy_(nb)
-        out = self.decode_async(mask, b).clone()
-        if int(self.err[:b].abs().sum().item()):
-            raise Lic360Error("arithmetic decoder fault (corrupt stream?): %s" % self.err[:b].cpu().tolist())
-        return out
+        b = self._stage_streams(streams)
+        return self._decoded(self.decode_async(mask, b), b)
 
     def set_coder(self, mode):
         """where the serial coder phases run: "device" (one wave per image), "host" (one host thread per image, <= 64 images per call), "auto"
@@ -170,31 +190,17 @@ class FusedCodec(object):
         return {n: (ms[i], cnt[i]) for i, n in enumerate(names)}
 
 
-class FusedImpCodec(object):
+class FusedImpCodec(_FusedBase):
     """Device-resident importance-map stream: ImpEntEncoderFast + ImpEntDecoder (test/lic360_demo.py:143-189, 241-290) for a
     batch of maps.  levels: float32 [b,1,h,w] with values in {0..nsym-1}; bitstreams == the reference's `<code>_imp` files."""
+
+    _destroy = staticmethod(_lib.lic360_impcodec_destroy)
 
     def __init__(self, h, w, max_batch, hidden_channels=144, nsym=49, device=0, cap_bytes=None):
         self.H, self.W, self.maxB, self.device = int(h), int(w), int(max_batch), int(device)
         self.cpg, self.nsym = int(hidden_channels), int(nsym)
-        self.cap = int(cap_bytes) if cap_bytes else max(4096, 2 * self.H * self.W)
-        self.cap = (self.cap + 3) // 4 * 4
-        self._h = C.c_void_p(0)
-        with torch.cuda.device(self.device):
-            _chk(_lib.lic360_impcodec_create(self.H, self.W, self.cpg, self.nsym, self.maxB, C.byref(self._h)))
-        dev = "cuda:%d" % self.device
-        self.bytes = torch.zeros((self.maxB, self.cap), dtype=torch.uint8, device=dev)
-        self.nbytes = torch.zeros((self.maxB,), dtype=torch.int32, device=dev)
-        self.err = torch.zeros((self.maxB,), dtype=torch.int32, device=dev)
+        dev = self._open(_lib.lic360_impcodec_create, (self.H, self.W, self.cpg, self.nsym, self.maxB), cap_bytes or max(4096, 2 * self.H * self.W))
         self.levels_out = torch.zeros((self.maxB, 1, self.H, self.W), dtype=torch.float32, device=dev)
-
-    def __del__(self):
-        try:
-            if self._h:
-                _lib.lic360_impcodec_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     def load_layers(self, layers):
         """layers: 12 dicts with numpy/torch 'w' [nout,C,5,5], 'b' [nout], 'a' [nout] or None."""
@@ -209,11 +215,7 @@ class FusedImpCodec(object):
 
     def load_from_driver(self, drv):
         """drv: an ImpEntEncoderFast / ImpEntDecoder whose net.* parameters were filled by cast_imp_entropy_parameter."""
-        mods = [drv.net[0]]
-        for i in range(1, 6):
-            mods += [drv.net[i].conv1, drv.net[i].conv2]
-        mods.append(drv.net[6])
-        self.load_layers([dict(w=m.weight.data, b=m.bias.data, a=None if m.relu is None else m.relu.data) for m in mods])
+        self.load_layers([dict(w=m.weight.data, b=m.bias.data, a=None if m.relu is None else m.relu.data) for m in _net_modules(drv)])
 
     def _check(self, t):
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape[1:]) == (1, self.H, self.W) and 0 < t.shape[0] <= self.maxB):
@@ -245,26 +247,8 @@ class FusedImpCodec(object):
         return (self, gen.value)
 
     def encode(self, levels):
-        b = self.encode_async(levels)
-        nb = self.nbytes[:b].cpu().tolist()
-        er = self.err[:b].cpu().tolist()
-        if any(er):
-            raise Lic360Error("arithmetic encoder fault / capacity overflow: %s" % er)
-        host = self.bytes[:b].cpu()
-        return [bytes(host[i, :nb[i]].numpy().tobytes()) for i in range(b)]
+        return self._read_streams(self.encode_async(levels))
 
     def decode(self, streams):
-        b = len(streams)
-        host = torch.zeros((self.maxB, self.cap), dtype=torch.uint8)
-        nb = torch.zeros((self.maxB,), dtype=torch.int32)
-        for i, s in enumerate(streams):
-            if len(s) > self.cap:
-                raise Lic360Error("bitstream %d longer than the codec capacity" % i)
-            host[i, :len(s)] = torch.frombuffer(bytearray(s), dtype=torch.uint8)
-            nb[i] = len(s)
-        self.bytes.copy_(host)
-        self.nbytes.copy_(nb)
-        out = self.decode_async(b).clone()
-        if int(self.err[:b].abs().sum().item()):
-            raise Lic360Error("arithmetic decoder fault (corrupt stream?): %s" % self.err[:b].cpu().tolist())
-        return out
+        b = self._stage_streams(streams)
+        return self._decoded(self.decode_async(b), b)

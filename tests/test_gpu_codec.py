@@ -168,6 +168,49 @@ def test_fused_importance_codec_matches_oracle(cpg, nsym, H, W, B, seed):
     assert np.array_equal(rc.decode_imp(streams[0], layers, H, W, nsym), levels[0:1])
 
 
+@pytest.mark.parametrize("kind", ["latent", "importance"])
+def test_fused_codec_needs_every_layer(kind):
+    """Both codecs' weight store: encode and decode before all 12 layers have weights raise "has no weights"; set_layer rejects a layer
+    index out of range, PReLU slopes given for the last layer and slopes missing for any other, and a rejected call sets nothing."""
+    import lic360
+    from lic360 import _lib, _p, _stream
+    from lic360_fused import FusedCodec, FusedImpCodec
+    rng = np.random.default_rng(81)
+    if kind == "latent":
+        G, H, W = 6, 8, 12
+        layers = rc.make_main_params(2081, G)
+        fc = FusedCodec(G, H, W, max_batch=2)
+        code, mask, _ = latent(rng, G, H, W)
+        args = (dev(code), dev(mask))
+        set_layer, decode_args, ref = _lib.lic360_codec_set_layer, (dev(mask),), lambda: rc.encode_main(code, mask, layers, G)
+    else:
+        H, W, nsym = 6, 9, 13
+        layers = rc.make_imp_params(4081, 8, nsym)
+        fc = FusedImpCodec(H, W, max_batch=2, hidden_channels=8, nsym=nsym)
+        levels = rng.integers(0, nsym, (1, 1, H, W)).astype(np.float32)
+        args = (dev(levels),)
+        set_layer, decode_args, ref = _lib.lic360_impcodec_set_layer, (), lambda: rc.encode_imp(levels, layers, nsym)
+    t = [{k: None if v is None else dev(v) for k, v in l.items()} for l in layers]
+
+    def put(i, l, a):
+        lic360._chk(set_layer(_stream(0), fc._h, i, _p(t[l]["w"]), _p(t[l]["b"]), _p(a)))
+
+    fc.load_layers(layers[:11])
+    for bad in [lambda: put(12, 0, t[0]["a"]), lambda: put(-1, 0, t[0]["a"]),
+                lambda: put(11, 11, t[10]["a"]), lambda: put(5, 5, None)]:
+        with pytest.raises(lic360.Lic360Error, match="bad argument"):
+            bad()
+    with pytest.raises(lic360.Lic360Error, match="layer 11 has no weights"):
+        fc.encode(*args)
+    with pytest.raises(lic360.Lic360Error, match="layer 11 has no weights"):
+        fc.decode([b"\x80"], *decode_args)
+    put(11, 11, None)
+    torch.cuda.synchronize()
+    streams = fc.encode(*args)
+    assert streams == [ref()]
+    assert np.array_equal(fc.decode(streams, *decode_args).cpu().numpy(), code * mask if kind == "latent" else levels)
+
+
 @pytest.mark.parametrize("G,MH,MW,B,seed", [(12, 8, 12, 1, 71), (12, 8, 12, 3, 72), (24, 6, 10, 2, 73)])
 def test_latent_decode_gated_behind_the_map_decode(G, MH, MW, B, seed):
     """lic360_impcodec_decode_masked + lic360_codec_decode_gated: the importance map decodes on one stream and refreshes the latent
