@@ -17,6 +17,11 @@
 // output row r at tap row kh reads input row r + kh) and 9 A operands (3 kh x 3 row tiles, three 16-byte loads per lane from a stream
 // packed in exactly this order, one pair ahead) for 9 RW MFMAs: 0.26 operand fetches per MFMA.  LDS plane pitch 336 = 16 (mod 64)
 // banks: the four k-planes of a B read fall on disjoint bank quarters.
+//
+// Two arithmetic forms, one of everything else.  s3_body (here) is the fp32 form, b3_body (sconv_bf16x3.inc, opt-in) the split-bf16 form; they
+// differ in their chunk loop, LDS layout and weight pack.  What decides which cells a convolution reads and writes exists once and serves both:
+// s3_cell_offset (the source cell of a loader's LDS cell), s3_epilogue (bias, PReLU, residual, window test, store), the kernel wrapper sconv_workgroup<B3, ..>
+// (tile decode, tall last tile row) and the host's sconv_launch<B3> (shape predicate, argument contract, tile geometry, grid).
 #include "common.h"
 #include <cstdint>
 
@@ -30,6 +35,7 @@ constexpr int s3_pitch(int tr, int ks) { int p = (tr + ks - 1) * (S3_T + ks - 1)
 constexpr int s3_ck(int ks) { return ks == 3 ? 16 : 32; }
 constexpr int s3_ndma(int tr, int ks) { return (s3_ck(ks) * s3_pitch(tr, ks) + 511) / 512; }       // DMA instructions per wave and chunk (8 waves x 64 lanes)
 constexpr int s3_na4(int ks) { return (3 * ks + 3) / 4; }                                          // 16-byte A loads per lane and (channel group, kw) pair: 3 ks row-tile operands
+constexpr int s3_lds(int tr, int ks) { return 2 * 8 * s3_ndma(tr, ks) * 64; }                      // LDS floats of a body: two chunk images
 
 struct S3Args {
     const float *x, *w, *bias, *slope, *res;
@@ -64,6 +70,91 @@ __device__ __forceinline__ void s3_sphere(int &ph, int &pw, int hp, int wp, int 
     ph = th + pad; pw = tw + pad;
 }
 
+// float q of a chunk's LDS image <-> (channel q / PL, halo row, halo column) of the CK channels of a chunk, a channel's XR x XC halo cells at
+// pitch PL; returns the byte offset of the cell's source in the chunk's first input plane (sphere rule applied).
+template <int CK, int PL, int XR, int XC, int KS>
+__device__ __forceinline__ unsigned s3_cell_offset(const S3Args &a, int tr0, int tc0, int q, long PLg) {
+    int ch = q / PL, rem = q - ch * PL;
+    if (ch >= CK || rem >= XR * XC) { ch = 0; rem = 0; }                    // pitch padding and the slack behind the last plane: any valid cell
+    const int r = rem / XC, c = rem - r * XC;
+    int ph = tr0 - KS / 2 + r, pw = tc0 - KS / 2 + c;
+    ph = ph < 0 ? 0 : (ph > a.hp - 1 ? a.hp - 1 : ph);                      // (only cells of outputs outside the window reach past the map)
+    pw = pw < 0 ? 0 : (pw > a.wp - 1 ? a.wp - 1 : pw);
+    if (a.sphere == 1) s3_sphere(ph, pw, a.hp, a.wp, a.pad);
+    else if (a.sphere == 2) { const int W = a.wp - 2 * a.pad; pw = pw < a.pad ? pw + W : (pw >= a.pad + W ? pw - W : pw); }
+    return (unsigned)(((long)ch * PLg + (long)ph * a.wp + pw) * 4);
+}
+
+// this lane's cells of a chunk: LDS float q = (i * 8 + wave) * 64 + lane, i < NDMA.  b3_body takes them through this loop.  s3_body spells the
+// same loop out in place: inlined from here, its kernels recompute the map's extents for every cell (1 - 3 % more instructions, all ahead of
+// the first DMA, 0.2 - 0.6 % of the run time of the large shapes), written in place they hoist them as they always did.  b3_body's kernels
+// are the other way round: through this call they keep the code they had, with the loop in place their register allocation moves.
+template <int NDMA, int CK, int PL, int XR, int XC, int KS>
+__device__ __forceinline__ void s3_cell_offsets(const S3Args &a, int tr0, int tc0, int wave, int lane, long PLg, unsigned (&voff)[NDMA]) {
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) voff[i] = s3_cell_offset<CK, PL, XR, XC, KS>(a, tr0, tc0, (i * 8 + wave) * 64 + lane, PLg);
+}
+
+// bias, PReLU, residual, store.  Accumulator m, row r, register v: channel co0 + 16 m + 4 kq + v (co0 = the wave's first output channel),
+// position (tr0 + nh * RW + r, tc0 + col) of the input grid (col = lane & 15, kq = lane >> 4, PLg = hp * wp); cells outside the window are not written
+template <int RW>
+__device__ __forceinline__ void s3_epilogue(const S3Args &a, const s3_f4 (&acc)[3][RW], int img, int tr0, int tc0, int co0, int nh, int col, int kq,
+                                            long PLg) {
+    const int pw = tc0 + col;
+    const long oPL = (long)a.ohp * a.owp;
+    const float *__restrict__ resp = a.res;
+    float *__restrict__ outp = a.out;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int co = co0 + 16 * m + 4 * kq;
+        const s3_f4 bs = *(const s3_f4 *)(a.bias + co);
+        s3_f4 sl = {1.f, 1.f, 1.f, 1.f};
+        if (a.slope) sl = *(const s3_f4 *)(a.slope + co);
+        s3_f4 rv[RW];
+        if (resp) {                                                         // all residual loads of the row tile in flight before its first store
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                const int ph = tr0 + nh * RW + r;
+                const bool ok = ph < a.hp - a.ring && pw < a.wp - a.ringw;
+                const int rh = ok ? ph : a.ring, rw_ = ok ? pw : a.ringw;
+                if (a.shuffle) {                                           // the residual has the OUTPUT's (shuffled) geometry
+                    typedef float s3_f2 __attribute__((ext_vector_type(2)));
+                    const long ri = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (rh - a.ooff)) * (2 * a.owp) + 2 * (rw_ - a.ooff);
+                    const s3_f2 lo = *(const s3_f2 *)(resp + ri), hi = *(const s3_f2 *)(resp + ri + 2 * a.owp);
+                    rv[r] = (s3_f4){lo[0], lo[1], hi[0], hi[1]};
+                } else {
+                    const long ri = ((long)img * a.cout + co) * PLg + (long)rh * a.wp + rw_;
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) rv[r][v] = resp[ri + v * PLg];
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            const int ph = tr0 + nh * RW + r;
+            if (ph < a.hp - a.ring && pw < a.wp - a.ringw) {
+                float y[4];
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    y[v] = acc[m][r][v] + bs[v];
+                    if (a.slope) y[v] = y[v] > 0.f ? y[v] : y[v] * sl[v];
+                    if (resp) y[v] = y[v] + rv[r][v];
+                }
+                if (a.shuffle) {                                           // two 8-byte stores per lane: 16 lanes write 128 contiguous bytes of each of two rows
+                    typedef float s3_f2 __attribute__((ext_vector_type(2)));
+                    const long o = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (ph - a.ooff)) * (2 * a.owp) + 2 * (pw - a.ooff);
+                    *(s3_f2 *)(outp + o) = (s3_f2){y[0], y[1]};
+                    *(s3_f2 *)(outp + o + 2 * a.owp) = (s3_f2){y[2], y[3]};
+                } else {
+                    const long o = ((long)img * a.cout + co) * oPL + (long)(ph - a.ooff) * a.owp + (pw - a.ooff);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) outp[o + v * oPL] = y[v];
+                }
+            }
+        }
+    }
+}
+
 // weights: [cout block of NQ * 48][cin / 4][kw < ks][mq][j < na4][lane] x 4 floats; lane l = 16 k + i, element e = 4 j + t = 3 kh + mt (e < 3 ks):
 // W[co = 48 mq + 16 mt + i][ci = 4 cg + k][kh][kw] -- the A operand of the MFMA for (kh, row tile mt)
 __global__ void k_sconv3x3_pack(const float *__restrict__ w, float *__restrict__ packed, int cin, int cout, int nq, int ks, long total) {
@@ -85,8 +176,9 @@ __global__ void k_sconv3x3_pack(const float *__restrict__ w, float *__restrict__
     }
 }
 
-template <int NQ, int RW, int PD, int KS>                                   // NQ * 48 output channels per workgroup, RW rows per wave, A operands PD pairs ahead, KS x KS taps
+template <int NQ, int RW, int KS>                                           // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps
 __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int tx, int img) {
+    constexpr int PD = KS == 3 ? 1 : 3;                                     // A operands PD pairs ahead: a 1x1 pair is 24 MFMAs (768 cycles), its operand is fetched three pairs ahead
     constexpr int NR = 8 / NQ, TR = NR * RW;                                // row groups per workgroup, tile rows
     constexpr int S3_CK = s3_ck(KS), NPAIR = S3_CK / 4 * KS, NA4 = s3_na4(KS), S3_XC = S3_T + KS - 1;
     constexpr int S3_PL = s3_pitch(TR, KS), S3_NDMA = s3_ndma(TR, KS), S3_BUF = 8 * S3_NDMA * 64, S3_XR = TR + KS - 1;
@@ -97,21 +189,9 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
     const int tr0 = a.ring + ty * (NR * a.rw), tc0 = a.ringw + tx * S3_T;    // input-grid cell of the tile's first output (a.rw: rows per wave of the ordinary tile rows)
     const int blk = blockIdx.y, cblk = NQ * 48;
     const long PLg = (long)a.hp * a.wp;
-    // ---- this lane's cells of a chunk's LDS image: LDS float q = (i * 8 + wave) * 64 + lane <-> (channel q / 336, halo row, halo column)
     unsigned voff[S3_NDMA];
-#pragma unroll
-    for (int i = 0; i < S3_NDMA; ++i) {
-        const int q = (i * 8 + wave) * 64 + lane;
-        int ch = q / S3_PL, rem = q - ch * S3_PL;
-        if (ch >= S3_CK || rem >= S3_XR * S3_XC) { ch = 0; rem = 0; }      // pitch padding and the slack behind the last plane: any valid cell
-        const int r = rem / S3_XC, c = rem - r * S3_XC;
-        int ph = tr0 - KS / 2 + r, pw = tc0 - KS / 2 + c;
-        ph = ph < 0 ? 0 : (ph > a.hp - 1 ? a.hp - 1 : ph);                  // (only cells of outputs outside the window reach past the map)
-        pw = pw < 0 ? 0 : (pw > a.wp - 1 ? a.wp - 1 : pw);
-        if (a.sphere == 1) s3_sphere(ph, pw, a.hp, a.wp, a.pad);
-        else if (a.sphere == 2) { const int W = a.wp - 2 * a.pad; pw = pw < a.pad ? pw + W : (pw >= a.pad + W ? pw - W : pw); }
-        voff[i] = (unsigned)(((long)ch * PLg + (long)ph * a.wp + pw) * 4);
-    }
+#pragma unroll                                                              // (s3_cell_offsets' loop, in place: see there)
+    for (int i = 0; i < S3_NDMA; ++i) voff[i] = s3_cell_offset<S3_CK, S3_PL, S3_XR, S3_XC, KS>(a, tr0, tc0, (i * 8 + wave) * 64 + lane, PLg);
     const float *xb = a.x + (long)img * a.cin * PLg;
     const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) const float *)&xs[0][0];
     auto issue_dma = [&](int ck) __attribute__((always_inline)) {
@@ -189,94 +269,73 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
         __syncthreads();
     }
 #undef S3_WAIT_A
-    // ---- epilogue: bias, PReLU, residual, store.  Accumulator m, row r, register v: channel 48 mq + 16 m + 4 kq + v, position (row, col)
-    const int pw = tc0 + col;
-    const long oPL = (long)a.ohp * a.owp;
-    const float *__restrict__ resp = a.res;
-    float *__restrict__ outp = a.out;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        const int co = blk * cblk + 48 * mq + 16 * m + 4 * kq;
-        const s3_f4 bs = *(const s3_f4 *)(a.bias + co);
-        s3_f4 sl = {1.f, 1.f, 1.f, 1.f};
-        if (a.slope) sl = *(const s3_f4 *)(a.slope + co);
-        s3_f4 rv[RW];
-        if (resp) {                                                         // all residual loads of the row tile in flight before its first store
-#pragma unroll
-            for (int r = 0; r < RW; ++r) {
-                const int ph = tr0 + nh * RW + r;
-                const bool ok = ph < a.hp - a.ring && pw < a.wp - a.ringw;
-                const int rh = ok ? ph : a.ring, rw_ = ok ? pw : a.ringw;
-                if (a.shuffle) {                                           // the residual has the OUTPUT's (shuffled) geometry
-                    typedef float s3_f2 __attribute__((ext_vector_type(2)));
-                    const long ri = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (rh - a.ooff)) * (2 * a.owp) + 2 * (rw_ - a.ooff);
-                    const s3_f2 lo = *(const s3_f2 *)(resp + ri), hi = *(const s3_f2 *)(resp + ri + 2 * a.owp);
-                    rv[r] = (s3_f4){lo[0], lo[1], hi[0], hi[1]};
-                } else {
-                    const long ri = ((long)img * a.cout + co) * PLg + (long)rh * a.wp + rw_;
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) rv[r][v] = resp[ri + v * PLg];
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RW; ++r) {
-            const int ph = tr0 + nh * RW + r;
-            if (ph < a.hp - a.ring && pw < a.wp - a.ringw) {
-                float y[4];
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    y[v] = acc[m][r][v] + bs[v];
-                    if (a.slope) y[v] = y[v] > 0.f ? y[v] : y[v] * sl[v];
-                    if (resp) y[v] = y[v] + rv[r][v];
-                }
-                if (a.shuffle) {                                           // two 8-byte stores per lane: 16 lanes write 128 contiguous bytes of each of two rows
-                    typedef float s3_f2 __attribute__((ext_vector_type(2)));
-                    const long o = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (ph - a.ooff)) * (2 * a.owp) + 2 * (pw - a.ooff);
-                    *(s3_f2 *)(outp + o) = (s3_f2){y[0], y[1]};
-                    *(s3_f2 *)(outp + o + 2 * a.owp) = (s3_f2){y[2], y[3]};
-                } else {
-                    const long o = ((long)img * a.cout + co) * oPL + (long)(ph - a.ooff) * a.owp + (pw - a.ooff);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) outp[o + v * oPL] = y[v];
-                }
-            }
-        }
-    }
+    s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
 }
 
+#include "sconv_bf16x3.inc"          // b3_body: the split-bf16 form of s3_body (its arithmetic, its pack kernel); everything around the bodies is below
+
+// ---- one workgroup wrapper, one launch for both forms (B3: the split-bf16 body).
+template <bool B3, int NQ, int RW, int KS>
+__device__ __forceinline__ void sconv_body(const S3Args &a, float *lds, int ty, int tx, int img) {
+    if constexpr (B3) b3_body<NQ, RW, KS>(a, lds, ty, tx, img);
+    else s3_body<NQ, RW, KS>(a, lds, ty, tx, img);
+}
 // A window of 16 k + 2 rows (every 1-ring window of these maps) would need a seventeenth tile row with 14 dead rows; instead its LAST tile row
 // runs one more row per wave (18 rows at 192 channels, 20 at 96): the workgroup picks its body by its tile row (uniform per workgroup).
-template <int NQ, int RW, int KS>
-__global__ __launch_bounds__(S3_THREADS) void k_sconv3x3(S3Args a) {
-    constexpr int NR = 8 / NQ;
-    __shared__ float lds[2 * 8 * s3_ndma(NR * (RW + (KS == 3 ? 1 : 0)), KS) * 64];
+template <bool B3, int NQ, int RW, int KS>
+__device__ __forceinline__ void sconv_workgroup(const S3Args &a) {
+    constexpr int TR = 8 / NQ * (RW + (KS == 3 ? 1 : 0));                   // rows of the tallest tile
+    __shared__ __attribute__((aligned(16))) float lds[B3 ? b3_lds(TR, KS) : s3_lds(TR, KS)];
+    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
     const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
     if constexpr (KS == 3) {
-        if (a.tall_last && ty == a.tiles_y - 1) { s3_body<NQ, RW + 1, 1, 3>(a, lds, ty, tx, img); return; }
+        if (a.tall_last && ty == a.tiles_y - 1) { sconv_body<B3, NQ, RW + 1, 3>(a, lds, ty, tx, img); return; }
     }
-    s3_body<NQ, RW, KS == 3 ? 1 : 3, KS>(a, lds, ty, tx, img);            // a 1x1 pair is 24 MFMAs (768 cycles): its A operand is fetched three pairs ahead
+    sconv_body<B3, NQ, RW, KS>(a, lds, ty, tx, img);
+}
+// (two kernel names, so that a profile tells the forms apart)
+template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3(S3Args a) { sconv_workgroup<false, NQ, RW, KS>(a); }
+template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv_b3(S3Args a) { sconv_workgroup<true, NQ, RW, KS>(a); }
+template <bool B3, int NQ, int RW, int KS>
+static auto sconv_kernel() {
+    if constexpr (B3) return &k_sconv_b3<NQ, RW, KS>;
+    else return &k_sconv3x3<NQ, RW, KS>;
 }
 
-static inline bool s3_ok(int cin, int cout, int ks = 3) { return (ks == 3 || ks == 1) && cin >= s3_ck(ks) && cin % s3_ck(ks) == 0 && cout >= 96 && (cout % 192 == 0 || cout == 96); }
-static inline long s3_packed(int cin, int cout, int ks) { return s3_ok(cin, cout, ks) ? (long)cout / 48 * (cin / 4) * ks * s3_na4(ks) * 256 : 0; }
+// the forms differ in their chunk of input channels (and so in the shapes they take), in the pack, and in the body
+static inline int sconv_ck(bool b3, int ks) { return b3 ? B3_CK : s3_ck(ks); }
+static inline bool sconv_ok(bool b3, int cin, int cout, int ks) {
+    return (ks == 3 || ks == 1) && cin >= sconv_ck(b3, ks) && cin % sconv_ck(b3, ks) == 0 && cout >= 96 && (cout % 192 == 0 || cout == 96);
+}
+static inline long s3_packed(int cin, int cout, int ks) { return sconv_ok(false, cin, cout, ks) ? (long)cout / 48 * (cin / 4) * ks * s3_na4(ks) * 256 : 0; }
+static inline long b3_packed_bytes(int cin, int cout, int ks) { return sconv_ok(true, cin, cout, ks) ? (long)cout * cin * ks * ks * 4 : 0; }   // hi + lo bf16 per weight
 static int s3_pack(void *stream, const float *weight, float *packed, int cin, int cout, int ks) {
-    ARG_CHECK(weight && packed && s3_ok(cin, cout, ks));
+    ARG_CHECK(weight && packed && sconv_ok(false, cin, cout, ks));
     const long total = s3_packed(cin, cout, ks);
     hipLaunchKernelGGL(k_sconv3x3_pack, dim3(lic360_blocks(total, 4)), dim3(256), 0, (hipStream_t)stream, weight, packed, cin, cout, cout % 192 == 0 ? 4 : 2, ks, total);
     LAUNCH_CHECK();
     return 0;
 }
-static int s3_launch(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
-                     int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle = 0) {
-    ARG_CHECK(x && packed && bias && out && n > 0 && s3_ok(cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w && out_crop >= 0 &&
-              out_crop <= ring && sphere >= 0 && sphere <= 2);
+static int b3_pack(void *stream, const float *weight, void *packed, int cin, int cout, int ks) {
+    ARG_CHECK(weight && packed && sconv_ok(true, cin, cout, ks) && ((uintptr_t)packed & 15) == 0);
+    const long total = b3_packed_bytes(cin, cout, ks) / 16;
+    hipLaunchKernelGGL(k_sconv_b3_pack, dim3(lic360_blocks(total)), dim3(256), 0, (hipStream_t)stream, weight, (b3_u4 *)packed, cin, cout,
+                       cout % 192 == 0 ? 4 : 2, ks, total);
+    LAUNCH_CHECK();
+    return 0;
+}
+template <bool B3>
+static int sconv_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                        int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle) {
+    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(B3, cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w &&
+              out_crop >= 0 && out_crop <= ring && sphere >= 0 && sphere <= 2);
     ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
-    ARG_CHECK((double)s3_ck(ks) * hp * wp * 4.0 < 4294967296.0 && ((uintptr_t)bias & 15) == 0 && (!slope || ((uintptr_t)slope & 15) == 0));
+    ARG_CHECK((double)sconv_ck(B3, ks) * hp * wp * 4.0 < 4294967296.0 && (!B3 || ((uintptr_t)packed & 15) == 0) && ((uintptr_t)bias & 15) == 0 &&
+              (!slope || ((uintptr_t)slope & 15) == 0));                    // a chunk's cells at 32-bit byte offsets; 16-byte operand loads
     ARG_CHECK(!residual || out_crop == 0 || shuffle);                       // the residual has the input's geometry -- or, shuffled, the output's
     ARG_CHECK(!shuffle || (((uintptr_t)out & 7) == 0 && ((uintptr_t)residual & 7) == 0));   // the shuffled store / residual load move aligned pairs
     S3Args a;
-    a.x = x; a.w = packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
+    a.x = x; a.w = (const float *)packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
     a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = ring; a.ringw = ring_w;
     a.ooff = out_crop; a.ohp = hp - 2 * out_crop; a.owp = wp - 2 * out_crop; a.shuffle = shuffle;
     a.tiles_x = (wp - 2 * ring_w + S3_T - 1) / S3_T;
@@ -287,27 +346,41 @@ static int s3_launch(void *stream, const float *x, const float *packed, const fl
     const long tiles = (long)n * a.tiles_x * a.tiles_y;
     ARG_CHECK(tiles < (1L << 31));
     const dim3 grid((unsigned)tiles, nq == 4 ? cout / 192 : 1);
-    if (ks == 3 && nq == 4) hipLaunchKernelGGL((k_sconv3x3<4, 8, 3>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (ks == 3) hipLaunchKernelGGL((k_sconv3x3<2, 4, 3>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (nq == 4) hipLaunchKernelGGL((k_sconv3x3<4, 8, 1>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_sconv3x3<2, 4, 1>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    if (ks == 3 && nq == 4) hipLaunchKernelGGL((sconv_kernel<B3, 4, 8, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else if (ks == 3) hipLaunchKernelGGL((sconv_kernel<B3, 2, 4, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else if (nq == 4) hipLaunchKernelGGL((sconv_kernel<B3, 4, 8, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((sconv_kernel<B3, 2, 4, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK();
     return 0;
 }
-LIC360_API int lic360_sconv3x3_supported(int cin, int cout) { return s3_ok(cin, cout, 3) ? 1 : 0; }
+
+LIC360_API int lic360_sconv3x3_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 3) ? 1 : 0; }
 LIC360_API long lic360_sconv3x3_packed_floats(int cin, int cout) { return s3_packed(cin, cout, 3); }
 LIC360_API int lic360_sconv3x3_pack(void *stream, const float *weight, float *packed, int cin, int cout) { return s3_pack(stream, weight, packed, cin, cout, 3); }
 LIC360_API int lic360_sconv3x3(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    return s3_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+    return sconv_launch<false>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
 }
 // the transforms' 1x1 layers on the same body (K = input channels only, no halo): bias + PReLU + residual in the epilogue, the window as above
-LIC360_API int lic360_sconv1x1_supported(int cin, int cout) { return s3_ok(cin, cout, 1) ? 1 : 0; }
+LIC360_API int lic360_sconv1x1_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 1) ? 1 : 0; }
 LIC360_API long lic360_sconv1x1_packed_floats(int cin, int cout) { return s3_packed(cin, cout, 1); }
 LIC360_API int lic360_sconv1x1_pack(void *stream, const float *weight, float *packed, int cin, int cout) { return s3_pack(stream, weight, packed, cin, cout, 1); }
 LIC360_API int lic360_sconv1x1(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
-    return s3_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+    return sconv_launch<false>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
 }
-
-#include "sconv_bf16x3.inc"          // the split-bf16 form of these convolutions (lic360_sconv3x3_bf16x3 / lic360_sconv1x1_bf16x3)
+// the split-bf16 forms of the four
+LIC360_API int lic360_sconv3x3_bf16x3_supported(int cin, int cout) { return sconv_ok(true, cin, cout, 3) ? 1 : 0; }
+LIC360_API long lic360_sconv3x3_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(cin, cout, 3); }
+LIC360_API int lic360_sconv3x3_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(stream, weight, packed, cin, cout, 3); }
+LIC360_API int lic360_sconv3x3_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
+    return sconv_launch<true>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+}
+LIC360_API int lic360_sconv1x1_bf16x3_supported(int cin, int cout) { return sconv_ok(true, cin, cout, 1) ? 1 : 0; }
+LIC360_API long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(cin, cout, 1); }
+LIC360_API int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(stream, weight, packed, cin, cout, 1); }
+LIC360_API int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                      int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
+    return sconv_launch<true>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+}

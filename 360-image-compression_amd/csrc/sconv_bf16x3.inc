@@ -21,95 +21,16 @@
 // [hl][kq < 4][PS cells] x 16 bytes, PS = halo cells rounded up to 16 (a plane = 0 mod 64 banks: the four kq planes of a ds_read_b128 fall
 // on disjoint banks, the 16 columns of a lane group on all 64).  Cost: 3 pass iterations per lane and chunk and a second barrier per chunk
 // against 648 MFMAs per wave (192 channels, 3x3); measurements: DESIGN 7c'.
-// Included at the end of conv3x3_kernels.hip (one translation unit: S3Args, the LDS-DMA helpers and the sphere rule are that file's; the tests
-// that check every M0-writing translation unit compile it).  s3_cell_offsets / s3_epilogue restate the fp32 body's inline code for this body;
-// the fp32 body keeps its own copy, so its code is unchanged.
+// Included by conv3x3_kernels.hip behind its fp32 body (one translation unit; the tests that check every M0-writing translation unit compile it).
+// This file holds only what the form does differently: the split, the weight pack kernel and b3_body's chunk loop.  S3Args, the LDS-DMA helpers,
+// the sphere rule, the loader's cell offsets (s3_cell_offsets), the epilogue (s3_epilogue), the kernel wrapper, the launch and the C entry
+// points are that file's, shared with the fp32 body.
 #include <type_traits>
-
-// this lane's cells of a chunk's LDS image: LDS float q = (i * 8 + wave) * 64 + lane <-> (channel q / PL, halo row, halo column) of the CK
-// channels of a chunk, a channel's (tile rows + KS - 1) x XC halo cells at pitch PL.  voff[i] = byte offset of the cell's source in the
-// chunk's first input plane (sphere rule applied).
-template <int NDMA, int CK, int PL, int XR, int XC, int KS>
-__device__ __forceinline__ void s3_cell_offsets(const S3Args &a, int tr0, int tc0, int wave, int lane, long PLg, unsigned (&voff)[NDMA]) {
-#pragma unroll
-    for (int i = 0; i < NDMA; ++i) {
-        const int q = (i * 8 + wave) * 64 + lane;
-        int ch = q / PL, rem = q - ch * PL;
-        if (ch >= CK || rem >= XR * XC) { ch = 0; rem = 0; }      // pitch padding and the slack behind the last plane: any valid cell
-        const int r = rem / XC, c = rem - r * XC;
-        int ph = tr0 - KS / 2 + r, pw = tc0 - KS / 2 + c;
-        ph = ph < 0 ? 0 : (ph > a.hp - 1 ? a.hp - 1 : ph);                  // (only cells of outputs outside the window reach past the map)
-        pw = pw < 0 ? 0 : (pw > a.wp - 1 ? a.wp - 1 : pw);
-        if (a.sphere == 1) s3_sphere(ph, pw, a.hp, a.wp, a.pad);
-        else if (a.sphere == 2) { const int W = a.wp - 2 * a.pad; pw = pw < a.pad ? pw + W : (pw >= a.pad + W ? pw - W : pw); }
-        voff[i] = (unsigned)(((long)ch * PLg + (long)ph * a.wp + pw) * 4);
-    }
-}
-
-// bias, PReLU, residual, store.  Accumulator m, row r, register v: channel co0 + 16 m + 4 kq + v (co0 = the wave's first output channel),
-// position (tr0 + nh * RW + r, tc0 + col) of the input grid (col = lane & 15, kq = lane >> 4, PLg = hp * wp); cells outside the window are not written
-template <int RW>
-__device__ __forceinline__ void s3_epilogue(const S3Args &a, const s3_f4 (&acc)[3][RW], int img, int tr0, int tc0, int co0, int nh, int col, int kq,
-                                            long PLg) {
-    const int pw = tc0 + col;
-    const long oPL = (long)a.ohp * a.owp;
-    const float *__restrict__ resp = a.res;
-    float *__restrict__ outp = a.out;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        const int co = co0 + 16 * m + 4 * kq;
-        const s3_f4 bs = *(const s3_f4 *)(a.bias + co);
-        s3_f4 sl = {1.f, 1.f, 1.f, 1.f};
-        if (a.slope) sl = *(const s3_f4 *)(a.slope + co);
-        s3_f4 rv[RW];
-        if (resp) {                                                         // all residual loads of the row tile in flight before its first store
-#pragma unroll
-            for (int r = 0; r < RW; ++r) {
-                const int ph = tr0 + nh * RW + r;
-                const bool ok = ph < a.hp - a.ring && pw < a.wp - a.ringw;
-                const int rh = ok ? ph : a.ring, rw_ = ok ? pw : a.ringw;
-                if (a.shuffle) {                                           // the residual has the OUTPUT's (shuffled) geometry
-                    typedef float s3_f2 __attribute__((ext_vector_type(2)));
-                    const long ri = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (rh - a.ooff)) * (2 * a.owp) + 2 * (rw_ - a.ooff);
-                    const s3_f2 lo = *(const s3_f2 *)(resp + ri), hi = *(const s3_f2 *)(resp + ri + 2 * a.owp);
-                    rv[r] = (s3_f4){lo[0], lo[1], hi[0], hi[1]};
-                } else {
-                    const long ri = ((long)img * a.cout + co) * PLg + (long)rh * a.wp + rw_;
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) rv[r][v] = resp[ri + v * PLg];
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RW; ++r) {
-            const int ph = tr0 + nh * RW + r;
-            if (ph < a.hp - a.ring && pw < a.wp - a.ringw) {
-                float y[4];
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    y[v] = acc[m][r][v] + bs[v];
-                    if (a.slope) y[v] = y[v] > 0.f ? y[v] : y[v] * sl[v];
-                    if (resp) y[v] = y[v] + rv[r][v];
-                }
-                if (a.shuffle) {                                           // two 8-byte stores per lane: 16 lanes write 128 contiguous bytes of each of two rows
-                    typedef float s3_f2 __attribute__((ext_vector_type(2)));
-                    const long o = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (ph - a.ooff)) * (2 * a.owp) + 2 * (pw - a.ooff);
-                    *(s3_f2 *)(outp + o) = (s3_f2){y[0], y[1]};
-                    *(s3_f2 *)(outp + o + 2 * a.owp) = (s3_f2){y[2], y[3]};
-                } else {
-                    const long o = ((long)img * a.cout + co) * oPL + (long)(ph - a.ooff) * a.owp + (pw - a.ooff);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) outp[o + v * oPL] = y[v];
-                }
-            }
-        }
-    }
-}
 
 typedef __bf16 b3_bf8 __attribute__((ext_vector_type(8)));
 typedef unsigned b3_u4 __attribute__((ext_vector_type(4)));
 
-#define B3_THREADS 512
+#define B3_THREADS S3_THREADS
 #define B3_CK 32                                                            // input channels per chunk (= the K of one MFMA)
 constexpr int b3_ndma(int ncell) { return (B3_CK * ncell + 511) / 512; }   // DMA instructions per wave and chunk (fp32 staging pitch = halo cells)
 constexpr int b3_ps(int ncell) { return (ncell + 15) / 16 * 16; }          // split-image plane pitch in 16-byte cells
@@ -238,69 +159,4 @@ __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int
     }
 #undef B3_WAIT_A
     s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
-}
-
-template <int NQ, int RW, int KS>
-__global__ __launch_bounds__(B3_THREADS) void k_sconv_b3(S3Args a) {
-    constexpr int NR = 8 / NQ;
-    __shared__ __attribute__((aligned(16))) float lds[b3_lds(NR * (RW + (KS == 3 ? 1 : 0)), KS)];
-    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
-    const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
-    if constexpr (KS == 3) {
-        if (a.tall_last && ty == a.tiles_y - 1) { b3_body<NQ, RW + 1, 3>(a, lds, ty, tx, img); return; }
-    }
-    b3_body<NQ, RW, KS>(a, lds, ty, tx, img);
-}
-
-static inline bool b3_ok(int cin, int cout, int ks) { return (ks == 3 || ks == 1) && cin >= B3_CK && cin % B3_CK == 0 && cout >= 96 && (cout % 192 == 0 || cout == 96); }
-static inline long b3_packed_bytes(int cin, int cout, int ks) { return b3_ok(cin, cout, ks) ? (long)cout * cin * ks * ks * 4 : 0; }   // hi + lo bf16 per weight
-static int b3_pack(void *stream, const float *weight, void *packed, int cin, int cout, int ks) {
-    ARG_CHECK(weight && packed && b3_ok(cin, cout, ks) && ((uintptr_t)packed & 15) == 0);
-    const long total = b3_packed_bytes(cin, cout, ks) / 16;
-    hipLaunchKernelGGL(k_sconv_b3_pack, dim3(lic360_blocks(total)), dim3(256), 0, (hipStream_t)stream, weight, (b3_u4 *)packed, cin, cout,
-                       cout % 192 == 0 ? 4 : 2, ks, total);
-    LAUNCH_CHECK();
-    return 0;
-}
-static int b3_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                     int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle) {
-    // the fp32 launch's argument contract (csrc/conv3x3_kernels.hip, s3_launch), with the 32-channel chunk of this body
-    ARG_CHECK(x && packed && bias && out && n > 0 && b3_ok(cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w && out_crop >= 0 &&
-              out_crop <= ring && sphere >= 0 && sphere <= 2);
-    ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));
-    ARG_CHECK((double)B3_CK * hp * wp * 4.0 < 4294967296.0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)bias & 15) == 0 && (!slope || ((uintptr_t)slope & 15) == 0));
-    ARG_CHECK(!residual || out_crop == 0 || shuffle);
-    ARG_CHECK(!shuffle || (((uintptr_t)out & 7) == 0 && ((uintptr_t)residual & 7) == 0));
-    S3Args a;
-    a.x = x; a.w = (const float *)packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
-    a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = ring; a.ringw = ring_w;
-    a.ooff = out_crop; a.ohp = hp - 2 * out_crop; a.owp = wp - 2 * out_crop; a.shuffle = shuffle;
-    a.tiles_x = (wp - 2 * ring_w + S3_T - 1) / S3_T;
-    const int nq = cout % 192 == 0 ? 4 : 2, nrg = 8 / nq, nr = hp - 2 * ring, full = nr / S3_T, rem = nr - full * S3_T;
-    a.rw = S3_T / nrg;
-    a.tall_last = ks == 3 && rem > 0 && rem <= nrg && full > 0;
-    a.tiles_y = a.tall_last ? full : (nr + S3_T - 1) / S3_T;
-    const long tiles = (long)n * a.tiles_x * a.tiles_y;
-    ARG_CHECK(tiles < (1L << 31));
-    const dim3 grid((unsigned)tiles, nq == 4 ? cout / 192 : 1);
-    if (ks == 3 && nq == 4) hipLaunchKernelGGL((k_sconv_b3<4, 8, 3>), grid, dim3(B3_THREADS), 0, (hipStream_t)stream, a);
-    else if (ks == 3) hipLaunchKernelGGL((k_sconv_b3<2, 4, 3>), grid, dim3(B3_THREADS), 0, (hipStream_t)stream, a);
-    else if (nq == 4) hipLaunchKernelGGL((k_sconv_b3<4, 8, 1>), grid, dim3(B3_THREADS), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_sconv_b3<2, 4, 1>), grid, dim3(B3_THREADS), 0, (hipStream_t)stream, a);
-    LAUNCH_CHECK();
-    return 0;
-}
-LIC360_API int lic360_sconv3x3_bf16x3_supported(int cin, int cout) { return b3_ok(cin, cout, 3) ? 1 : 0; }
-LIC360_API long lic360_sconv3x3_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(cin, cout, 3); }
-LIC360_API int lic360_sconv3x3_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(stream, weight, packed, cin, cout, 3); }
-LIC360_API int lic360_sconv3x3_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    return b3_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
-}
-LIC360_API int lic360_sconv1x1_bf16x3_supported(int cin, int cout) { return b3_ok(cin, cout, 1) ? 1 : 0; }
-LIC360_API long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(cin, cout, 1); }
-LIC360_API int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(stream, weight, packed, cin, cout, 1); }
-LIC360_API int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                                      int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
-    return b3_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
 }

@@ -44,21 +44,6 @@ def _fusable(conv, x, ring, ring_w=None, mod=None):
     return tiles >= FUSED_MIN_WORKGROUPS and tiles >= FUSED_MIN_FILL * 256 * ((tiles + 255) // 256)
 
 
-def _packed(conv, precision="fp32"):
-    """the conv's weight in the operand order of lic360.sconv3x3 / sconv1x1 (precision "fp32") or of their bf16x3 forms, repacked when the parameter
-    was written (its version counter) or moved; each precision keeps its own pack under the same key"""
-    key = (conv.weight.data_ptr(), conv.weight._version)
-    if precision == "bf16x3":
-        if getattr(conv, "_b3_key", None) != key:
-            pack = lic360.sconv3x3_bf16x3_pack if conv.kernel_size == (3, 3) else lic360.sconv1x1_bf16x3_pack
-            conv._b3_packed, conv._b3_key = pack(conv.weight.detach()), key
-        return conv._b3_packed
-    if getattr(conv, "_s3_key", None) != key:
-        pack = lic360.sconv3x3_pack if conv.kernel_size == (3, 3) else lic360.sconv1x1_pack
-        conv._s3_packed, conv._s3_key = pack(conv.weight.detach()), key
-    return conv._s3_packed
-
-
 CONV_PRECISIONS = ("fp32", "bf16x3")
 
 
@@ -74,25 +59,30 @@ def set_conv_precision(module, precision):
     return module
 
 
-def _bf16x3(mod, conv):
-    """does block `mod` run the fused convolution `conv` in its bf16x3 form?"""
-    if getattr(mod, "_conv_precision", "fp32") != "bf16x3":
-        return False
+# (kernel size, precision) -> the names of the convolution, its pack and its shape predicate in lic360
+_SCONV = {(3, "fp32"): ("sconv3x3", "sconv3x3_pack", "sconv3x3_supported"),
+          (1, "fp32"): ("sconv1x1", "sconv1x1_pack", "sconv1x1_supported"),
+          (3, "bf16x3"): ("sconv3x3_bf16x3", "sconv3x3_bf16x3_pack", "sconv3x3_bf16x3_supported"),
+          (1, "bf16x3"): ("sconv1x1_bf16x3", "sconv1x1_bf16x3_pack", "sconv1x1_bf16x3_supported")}
+
+
+def _sconv(mod, conv, x, slope, residual, out, **kw):
+    """the fused convolution `conv` (3x3 or 1x1) of block `mod` in the block's precision: lic360.sconv3x3 / sconv1x1 (the fp32 call is exactly
+    theirs), or their bf16x3 forms when the block asks for them and they take the layer's shape.  The functions are lic360's attributes at
+    call time.  The weight travels in the chosen form's operand order, repacked when the parameter was written (its version counter) or moved;
+    each precision keeps its own pack, so switching modes never reuses the other's."""
+    ks, precision = conv.kernel_size[0], getattr(mod, "_conv_precision", "fp32")
     cout, cin = conv.weight.shape[:2]
-    return (lic360.sconv3x3_bf16x3_supported if conv.kernel_size == (3, 3) else lic360.sconv1x1_bf16x3_supported)(cin, cout)
-
-
-def _sconv3x3(mod, conv, x, slope, residual, out, **kw):
-    """the fused 3x3 convolution of block `mod` in the block's precision (the fp32 call is exactly lic360.sconv3x3's)"""
-    if _bf16x3(mod, conv):
-        return lic360.sconv3x3_bf16x3(x, _packed(conv, "bf16x3"), conv.bias, slope, residual, out, **kw)
-    return lic360.sconv3x3(x, _packed(conv), conv.bias, slope, residual, out, **kw)
-
-
-def _sconv1x1(mod, conv, x, slope, residual, out, **kw):
-    if _bf16x3(mod, conv):
-        return lic360.sconv1x1_bf16x3(x, _packed(conv, "bf16x3"), conv.bias, slope, residual, out, **kw)
-    return lic360.sconv1x1(x, _packed(conv), conv.bias, slope, residual, out, **kw)
+    if precision != "fp32" and not getattr(lic360, _SCONV[ks, precision][2])(cin, cout):
+        precision = "fp32"
+    fn, pack, _ = _SCONV[ks, precision]
+    key = (conv.weight.data_ptr(), conv.weight._version)
+    packs = getattr(conv, "_sconv_packs", None)                             # precision -> (key, packed)
+    if packs is None:
+        packs = conv._sconv_packs = {}
+    if packs.get(precision, (None, None))[0] != key:
+        packs[precision] = (key, getattr(lic360, pack)(conv.weight.detach()))
+    return getattr(lic360, fn)(x, packs[precision][1], conv.bias, slope, residual, out, **kw)
 
 
 def _scratch(shape, like):
@@ -123,14 +113,14 @@ class ResidualBlock(nn.Module):
             one = lic360.sconv1x1_supported(c, c // 2) and lic360.sconv1x1_supported(c // 2, c) and self.conv1.bias is not None and self.conv3.bias is not None
             if one:
                 y = _scratch((n, c // 2, hp, wp), x)
-                _sconv1x1(self, self.conv1, x, self.relu1.weight, None, y, ring=2)
+                _sconv(self, self.conv1, x, self.relu1.weight, None, y, ring=2)
             else:
                 y = self.relu1(self.conv1(x)).contiguous()
             y2 = _scratch(y.shape, y)
-            _sconv3x3(self, self.conv2, y, self.relu2.weight, None, y2, pad=2, sphere=True, ring=2)
+            _sconv(self, self.conv2, y, self.relu2.weight, None, y2, pad=2, sphere=True, ring=2)
             if one:
                 out = torch.empty_like(x)
-                _sconv1x1(self, self.conv3, y2, None, x, out, ring=2)
+                _sconv(self, self.conv3, y2, None, x, out, ring=2)
                 return self.trim(out)
             return self.trim(x + self.conv3(y2))
         y = self.pad(x)
@@ -167,9 +157,9 @@ class ResidualBlockV2(nn.Module):
             # column bit for bit -- conv2 reads them there (longitude wrap), reads the rows as they are, adds x on the interior; the
             # output's apron is x's refreshed apron, as `x + trim2(...)` leaves it in the reference
             y1 = _scratch(x.shape, x)
-            _sconv3x3(self, self.conv1, x, self.relu1.weight, None, y1, pad=2, sphere=1, ring=1, ring_w=2)
+            _sconv(self, self.conv1, x, self.relu1.weight, None, y1, pad=2, sphere=1, ring=1, ring_w=2)
             out = torch.empty_like(x)
-            _sconv3x3(self, self.conv2, y1, self.relu2.weight, x, out, pad=2, sphere=2, ring=2)
+            _sconv(self, self.conv2, y1, self.relu2.weight, x, out, pad=2, sphere=2, ring=2)
             return lic360.sphere_apron_from(x, out, 2)
         y = self.trim1(self.relu1(self.conv1(self.pad(x))))
         return x + self.trim2(self.relu2(self.conv2(y)))
@@ -203,7 +193,7 @@ class ResidualBlockDown(nn.Module):
         if _fusable(self.conv2, y, 2, mod=self) and y.is_contiguous():
             # conv2 reads the apron of y by index (no pad2); GDN is pointwise over positions, its frame cells are trimmed below
             y2 = _scratch(y.shape, y)
-            y = self.relu2(_sconv3x3(self, self.conv2, y, None, None, y2, pad=2, sphere=True, ring=2))
+            y = self.relu2(_sconv(self, self.conv2, y, None, None, y2, pad=2, sphere=True, ring=2))
         else:
             y = self.relu2(self.conv2(self.pad2(y)))
         return self.trim((self.short_cut(x) if skip is None else skip) + y)
@@ -268,14 +258,14 @@ class ResidualBlockUp(nn.Module):
             # never read (conv2 reads aprons by index, or pad2 refreshes it), so trim1 has nothing to do.
             n, c, hp, wp = x.shape
             b = _scratch((n, self.conv1.out_channels // 4, 2 * (hp - 2), 2 * (wp - 2)), x)
-            _sconv3x3(self, self.conv1, x, self.relu1.weight, None, b, pad=2, sphere=1, ring=2, crop=1, shuffle=True)
+            _sconv(self, self.conv1, x, self.relu1.weight, None, b, pad=2, sphere=1, ring=2, crop=1, shuffle=True)
         else:
             b = self.dtow1(self.relu1(self.conv1(self.pad1(x))))           # (trim1 -> pad2 in place, model_zoo.py:160-161: the refresh overwrites what the trim zeroed)
             if torch.is_grad_enabled() and b.requires_grad:
                 b = self.trim1(b)                                           # (recording pass: the reference's sequence, see ResidualBlockDown)
         if _fusable(self.conv2, b, 2, mod=self) and b.is_contiguous():
             b2 = _scratch(b.shape, b)
-            b = self.relu2(_sconv3x3(self, self.conv2, b, None, None, b2, pad=2, sphere=True, ring=2))
+            b = self.relu2(_sconv(self, self.conv2, b, None, None, b2, pad=2, sphere=True, ring=2))
         else:
             b = self.relu2(self.conv2(self.pad2(b)))
         c_in, c_out = self.short_cut.in_channels, self.short_cut.out_channels
@@ -284,7 +274,7 @@ class ResidualBlockUp(nn.Module):
             # the shortcut -- cut_edge(1) -> 1x1 conv to 4c -> Dtow(2) -- and the `b +` in one launch: the 1x1 instantiation with the shuffled store,
             # b as its (shuffled) residual, on the interior window (trim2 zeroes the rest)
             out = torch.empty_like(b)
-            _sconv1x1(self, self.short_cut, x, None, b, out, ring=2, crop=1, shuffle=True)
+            _sconv(self, self.short_cut, x, None, b, out, ring=2, crop=1, shuffle=True)
             return self.trim2(out)
         return self.trim2(b + self.dtow2(self.short_cut(self.cut_edge(x))))
 

@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from util import _block_params, _refresh
+
 pytestmark = pytest.mark.gpu
 
 
@@ -15,20 +17,6 @@ def lic():
         pytest.skip("needs a HIP device")
     import lic360
     return lic360
-
-
-def _pad_torch(x, pad):
-    W = x.shape[-1]
-    body = torch.cat([x[..., W - pad:], x, x[..., :pad]], -1)
-    def across(r):
-        r = torch.flip(r, (-1,))
-        return torch.cat([r[..., W - pad:], r, r[..., :pad]], -1)
-    return torch.cat([across(torch.flip(x[..., :pad, :], (-2,))), body, across(torch.flip(x[..., x.shape[-2] - pad:, :], (-2,)))], -2)
-
-
-def _refresh(x, pad=2):
-    """SpherePad in place: the apron of a padded map recomputed from its interior"""
-    return _pad_torch(x[..., pad:-pad, pad:-pad], pad)
 
 
 def _trim(x, pad):
@@ -120,15 +108,6 @@ def test_block_gradients_match_index_only_torch(lic):
             if name == "input":                                             # interior only: what the reference's in-place pad backward leaves in the
                 a, b = a[..., 2:-2, 2:-2], b[..., 2:-2, 2:-2]               # apron cells of its input gradient is its own (an upstream trim zeroes it)
             assert torch.allclose(a, b, rtol=2e-3, atol=2e-4), "%s %s: max abs diff %g" % (type(blk).__name__, name, float((a - b).abs().max()))
-
-
-def _block_params(blk):
-    """numpy parameters of a block under its state_dict keys + the constants of its GDN (the oracle's `blocks` take these)"""
-    p = {k: v.detach().cpu().numpy() for k, v in blk.state_dict().items()}
-    for name, m in blk.named_modules():
-        if type(m).__name__ == "GDN":
-            p[name + ".pedestal"], p[name + ".beta_bound"], p[name + ".gamma_bound"] = m.pedestal, m.beta_bound, m.gamma_bound
-    return p
 
 
 def test_blocks_match_the_oracle(lic):

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from util import _block_params, _refresh
+
 pytestmark = pytest.mark.gpu
 
 
@@ -18,27 +20,6 @@ def lic():
         pytest.skip("needs a HIP device")
     import lic360
     return lic360
-
-
-def _pad_torch(x, pad):
-    W = x.shape[-1]
-    body = torch.cat([x[..., W - pad:], x, x[..., :pad]], -1)
-    def across(r):
-        r = torch.flip(r, (-1,))
-        return torch.cat([r[..., W - pad:], r, r[..., :pad]], -1)
-    return torch.cat([across(torch.flip(x[..., :pad, :], (-2,))), body, across(torch.flip(x[..., x.shape[-2] - pad:, :], (-2,)))], -2)
-
-
-def _refresh(x, pad=2):
-    return _pad_torch(x[..., pad:-pad, pad:-pad], pad)
-
-
-def _block_params(blk):
-    p = {k: v.detach().cpu().numpy() for k, v in blk.state_dict().items()}
-    for name, m in blk.named_modules():
-        if type(m).__name__ == "GDN":
-            p[name + ".pedestal"], p[name + ".beta_bound"], p[name + ".gamma_bound"] = m.pedestal, m.beta_bound, m.gamma_bound
-    return p
 
 
 def _bf16(a):
@@ -180,6 +161,42 @@ def test_pack_layout_and_operand_checks(lic):
     with pytest.raises(lic.Lic360Error):
         lic.sconv3x3(x, lic.sconv3x3_bf16x3_pack(w), b, ring=2)
     assert not lic.sconv3x3_bf16x3_supported(16, 192) and not lic.sconv1x1_bf16x3_supported(48, 96)
+    # the launch's argument contract, both precisions: each of these is refused by the native check ("bad argument") before anything is launched
+    cin, cout, hp, wp = 64, 192, 20, 36
+    x = torch.zeros((1, cin, hp, wp), device="cuda:0")
+    b, sl = torch.zeros(cout, device="cuda:0"), torch.ones(cout, device="cuda:0")
+    off = lambda t: torch.cat([t[:1], t])[1:]                               # the same values 4 bytes past a 16-byte boundary
+    for ks in (3, 1):
+        for form in ("", "_bf16x3"):
+            conv, pack = getattr(lic, "sconv%dx%d%s" % (ks, ks, form)), getattr(lic, "sconv%dx%d%s_pack" % (ks, ks, form))
+            w = torch.from_numpy(rng.standard_normal((cout, cin, ks, ks)).astype(np.float32)).cuda()
+            pk, kw = pack(w), (dict(pad=2, sphere=1) if ks == 3 else {})
+            for ci, co in ((40, 192), (64, 100), (8, 96), (64, 48)):        # unsupported channel counts
+                with pytest.raises(lic.Lic360Error, match="not supported" if form else "bad argument"):
+                    pack(torch.zeros((co, ci, ks, ks), device="cuda:0"))
+            crop1 = (1, cout, hp - 2, wp - 2)
+            for what, shape, args, kws in (
+                    ("ring below ks / 2", (1, cout, hp, wp), (x, pk, b, sl, None), dict(ring=ks // 2 - 1)),
+                    ("crop above ring", (1, cout, hp - 6, wp - 6), (x, pk, b, sl, None), dict(ring=2, crop=3)),
+                    ("residual with crop and no shuffle", crop1, (x, pk, b, sl, torch.zeros(crop1, device="cuda:0")), dict(ring=2, crop=1)),
+                    ("misaligned bias", (1, cout, hp, wp), (x, pk, off(b), sl, None), dict(ring=2)),
+                    ("misaligned slope", (1, cout, hp, wp), (x, pk, b, off(sl), None), dict(ring=2))):
+                out = torch.full(shape, 777.0, device="cuda:0")
+                with pytest.raises(lic.Lic360Error, match="bad argument"):
+                    conv(*args, out, **kws, **kw)
+                torch.cuda.synchronize()
+                assert bool((out == 777.0).all()), "sconv%dx%d%s, %s: out was written" % (ks, ks, form, what)
+            out = torch.full((1, cout, hp, wp), 777.0, device="cuda:0")
+            for bad in (pk[:-8].contiguous(), pk.float() if form else pk.bfloat16()):      # wrong size, wrong dtype
+                with pytest.raises(lic.Lic360Error, match="packed must"):
+                    conv(x, bad, b, sl, None, out, ring=2, **kw)
+            torch.cuda.synchronize()
+            assert bool((out == 777.0).all())
+            with pytest.raises(lic.Lic360Error, match="packed must"):       # an unsupported channel count at the call: no pack of that shape exists
+                conv(torch.zeros((1, 40, hp, wp), device="cuda:0"), pk, b, sl, None, out, ring=2, **kw)
+            conv(x, pk, b, sl, None, out, ring=2, **kw)                     # and the good call still runs
+            torch.cuda.synchronize()
+            assert not bool((out == 777.0).all())
 
 
 def _counting(lic, monkeypatch):

@@ -92,3 +92,29 @@ def make_imp_params(seed, cpg=144, nsym=49):
         w, b, a = conv_params(rng, None, nout, C, act=act)
         layers.append(dict(w=w, b=b, a=a, constrain=constrain))
     return layers
+
+
+# ---- torch-side helpers of the transforms' GPU tests (test_gpu_models.py, test_gpu_sconv_bf16x3.py)
+def _pad_torch(x, pad):
+    """the sphere apron of `pad` cells around a torch map [..., H, W]: longitude wraps, pole rows reflect and mirror"""
+    import torch
+    W = x.shape[-1]
+    body = torch.cat([x[..., W - pad:], x, x[..., :pad]], -1)
+    def across(r):
+        r = torch.flip(r, (-1,))
+        return torch.cat([r[..., W - pad:], r, r[..., :pad]], -1)
+    return torch.cat([across(torch.flip(x[..., :pad, :], (-2,))), body, across(torch.flip(x[..., x.shape[-2] - pad:, :], (-2,)))], -2)
+
+
+def _refresh(x, pad=2):
+    """SpherePad in place: the apron of a padded map recomputed from its interior"""
+    return _pad_torch(x[..., pad:-pad, pad:-pad], pad)
+
+
+def _block_params(blk):
+    """numpy parameters of a block under its state_dict keys + the constants of its GDN (the oracle's `blocks` take these)"""
+    p = {k: v.detach().cpu().numpy() for k, v in blk.state_dict().items()}
+    for name, m in blk.named_modules():
+        if type(m).__name__ == "GDN":
+            p[name + ".pedestal"], p[name + ".beta_bound"], p[name + ".gamma_bound"] = m.pedestal, m.beta_bound, m.gamma_bound
+    return p
