@@ -1,4 +1,5 @@
-// conv3x3_kernels.hip -- the 3x3 stride-1 convolutions of the analysis / synthesis transforms on sphere-apron maps,
+// conv3x3_kernels.hip -- the 3x3 and 1x1 convolutions of the analysis / synthesis transforms on sphere-apron maps: stride 1, and the
+// stride-2 (down-sampling) layers of the analysis transform as a stride parameter of the same body (below: "Stride 2"),
 // hand-written for gfx950: the tile loader reads the SPHERE APRON BY INDEX (no padded copy, no SpherePad launch), the epilogue applies
 // bias + PReLU + the block's residual add, and the SphereTrim that follows every such convolution becomes the output window (cells outside
 // it are simply not computed).  Replaces, per layer, nn.Conv2d + SpherePad + nn.PReLU + SphereTrim (+ the residual add) of
@@ -17,6 +18,19 @@
 // output row r at tap row kh reads input row r + kh) and 9 A operands (3 kh x 3 row tiles, three 16-byte loads per lane from a stream
 // packed in exactly this order, one pair ahead) for 9 RW MFMAs: 0.26 operand fetches per MFMA.  LDS plane pitch 336 = 16 (mod 64)
 // banks: the four k-planes of a B read fall on disjoint bank quarters.
+//
+// Stride 2 (k_sconv3x3s2, fp32 form only; lic360_sconv3x3s2 / lic360_sconv1x1s2).  Replaces SpherePad(2) + nn.Conv2d(c, c', 3, 2, 3) + nn.PReLU + SphereTrim of
+// test/model_zoo.py:64-106 (ResidualBlockDown.conv1, SphereConv2) and nn.Conv2d(c, c', 1, 2, 2) + the block's add (ResidualBlockDown.short_cut).  A tile is
+// 16 x 16 cells of the OUTPUT's interior; the output has its own grid, and the residual has the output's geometry.  3x3: the halo is 33 x 33 cells per
+// channel (output (r, col) at tap (kh, kw) reads halo cell (2 r + kh, 2 col + kw)), 2 RW + 1 B operands per pair for the same 72 MFMAs.  Decisions:
+//   LDS      16 channels x 1089 cells = 70 KB per chunk image, 140 KB double-buffered (one workgroup per CU); no tall last tile row (a 35-row halo does not
+//            fit twice): a remainder takes an ordinary extra tile row -- every production window is a multiple of 16.
+//   waits    35 DMAs per wave and chunk: the counted wait at a chunk's second pair is vmcnt(35), under the 6-bit limit of 63 (static_assert in s3_body).
+//   banks    the 16 columns of a plane fall on the even banks, so the plane pitch is ODD (1089): of the two kq planes that a ds_read_b32 group of 32 lanes
+//            covers, the second takes the odd banks -- conflict-free, and the per-lane loader needs no de-interleave.  (16 mod 64, the stride-1 pitch,
+//            would put every plane on the even banks.)
+//   1x1      the loader fetches the even / even cells only: LDS image, reads and waits are the stride-1 1x1's.
+// The weight packs are the stride-1 ones.  The stride-1 instantiations compile to the instructions they had before the stride parameter existed.
 //
 // Two arithmetic forms, one of everything else.  s3_body (here) is the fp32 form, b3_body (sconv_bf16x3.inc, opt-in) the split-bf16 form; they
 // differ in their chunk loop, LDS layout and weight pack.  What decides which cells a convolution reads and writes exists once and serves both:
@@ -72,12 +86,18 @@ __device__ __forceinline__ void s3_sphere(int &ph, int &pw, int hp, int wp, int 
 
 // float q of a chunk's LDS image <-> (channel q / PL, halo row, halo column) of the CK channels of a chunk, a channel's XR x XC halo cells at
 // pitch PL; returns the byte offset of the cell's source in the chunk's first input plane (sphere rule applied).
-template <int CK, int PL, int XR, int XC, int KS>
+// ST = 2 (the down-sampling forms): (tr0, tc0) is the tile's first output in INTERIOR coordinates of the output, and halo cell (r, c) is input cell
+// (pad + 2 tr0 - KS / 2 + r, pad + 2 tc0 - KS / 2 + c) at KS = 3 -- a (2 TR + 1) x 33 halo -- and the even / even cell (pad + 2 (tr0 + r), pad + 2 (tc0 + c))
+// at KS = 1, whose LDS image is therefore the stride-1 one (TR x 16).
+template <int CK, int PL, int XR, int XC, int KS, int ST = 1>
 __device__ __forceinline__ unsigned s3_cell_offset(const S3Args &a, int tr0, int tc0, int q, long PLg) {
     int ch = q / PL, rem = q - ch * PL;
     if (ch >= CK || rem >= XR * XC) { ch = 0; rem = 0; }                    // pitch padding and the slack behind the last plane: any valid cell
     const int r = rem / XC, c = rem - r * XC;
-    int ph = tr0 - KS / 2 + r, pw = tc0 - KS / 2 + c;
+    int ph, pw;
+    if constexpr (ST == 1) { ph = tr0 - KS / 2 + r; pw = tc0 - KS / 2 + c; }
+    else if constexpr (KS == 3) { ph = a.pad + 2 * tr0 - 1 + r; pw = a.pad + 2 * tc0 - 1 + c; }
+    else { ph = a.pad + 2 * (tr0 + r); pw = a.pad + 2 * (tc0 + c); }
     ph = ph < 0 ? 0 : (ph > a.hp - 1 ? a.hp - 1 : ph);                      // (only cells of outputs outside the window reach past the map)
     pw = pw < 0 ? 0 : (pw > a.wp - 1 ? a.wp - 1 : pw);
     if (a.sphere == 1) s3_sphere(ph, pw, a.hp, a.wp, a.pad);
@@ -96,12 +116,14 @@ __device__ __forceinline__ void s3_cell_offsets(const S3Args &a, int tr0, int tc
 }
 
 // bias, PReLU, residual, store.  Accumulator m, row r, register v: channel co0 + 16 m + 4 kq + v (co0 = the wave's first output channel),
-// position (tr0 + nh * RW + r, tc0 + col) of the input grid (col = lane & 15, kq = lane >> 4, PLg = hp * wp); cells outside the window are not written
-template <int RW>
+// position (tr0 + nh * RW + r, tc0 + col) of the input grid (col = lane & 15, kq = lane >> 4, PLg = hp * wp); cells outside the window are not written.
+// ST = 2: the position is a cell of the OUTPUT's own grid (ohp x owp, window [ring, ohp - ring) x [ringw, owp - ringw)), and so is the residual's.
+template <int RW, int ST = 1>
 __device__ __forceinline__ void s3_epilogue(const S3Args &a, const s3_f4 (&acc)[3][RW], int img, int tr0, int tc0, int co0, int nh, int col, int kq,
                                             long PLg) {
     const int pw = tc0 + col;
     const long oPL = (long)a.ohp * a.owp;
+    const int wh = ST == 1 ? a.hp : a.ohp, ww = ST == 1 ? a.wp : a.owp;    // the grid the window is a window of
     const float *__restrict__ resp = a.res;
     float *__restrict__ outp = a.out;
 #pragma unroll
@@ -115,9 +137,13 @@ __device__ __forceinline__ void s3_epilogue(const S3Args &a, const s3_f4 (&acc)[
 #pragma unroll
             for (int r = 0; r < RW; ++r) {
                 const int ph = tr0 + nh * RW + r;
-                const bool ok = ph < a.hp - a.ring && pw < a.wp - a.ringw;
+                const bool ok = ph < wh - a.ring && pw < ww - a.ringw;
                 const int rh = ok ? ph : a.ring, rw_ = ok ? pw : a.ringw;
-                if (a.shuffle) {                                           // the residual has the OUTPUT's (shuffled) geometry
+                if constexpr (ST == 2) {                                   // the residual has the OUTPUT's geometry
+                    const long ri = ((long)img * a.cout + co) * oPL + (long)rh * a.owp + rw_;
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) rv[r][v] = resp[ri + v * oPL];
+                } else if (a.shuffle) {                                    // the residual has the OUTPUT's (shuffled) geometry
                     typedef float s3_f2 __attribute__((ext_vector_type(2)));
                     const long ri = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (rh - a.ooff)) * (2 * a.owp) + 2 * (rw_ - a.ooff);
                     const s3_f2 lo = *(const s3_f2 *)(resp + ri), hi = *(const s3_f2 *)(resp + ri + 2 * a.owp);
@@ -132,7 +158,7 @@ __device__ __forceinline__ void s3_epilogue(const S3Args &a, const s3_f4 (&acc)[
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             const int ph = tr0 + nh * RW + r;
-            if (ph < a.hp - a.ring && pw < a.wp - a.ringw) {
+            if (ph < wh - a.ring && pw < ww - a.ringw) {
                 float y[4];
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
@@ -140,7 +166,7 @@ __device__ __forceinline__ void s3_epilogue(const S3Args &a, const s3_f4 (&acc)[
                     if (a.slope) y[v] = y[v] > 0.f ? y[v] : y[v] * sl[v];
                     if (resp) y[v] = y[v] + rv[r][v];
                 }
-                if (a.shuffle) {                                           // two 8-byte stores per lane: 16 lanes write 128 contiguous bytes of each of two rows
+                if (ST == 1 && a.shuffle) {                                // two 8-byte stores per lane: 16 lanes write 128 contiguous bytes of each of two rows
                     typedef float s3_f2 __attribute__((ext_vector_type(2)));
                     const long o = (((long)img * (a.cout >> 2) + (co >> 2)) * (2 * a.ohp) + 2 * (ph - a.ooff)) * (2 * a.owp) + 2 * (pw - a.ooff);
                     *(s3_f2 *)(outp + o) = (s3_f2){y[0], y[1]};
@@ -176,22 +202,32 @@ __global__ void k_sconv3x3_pack(const float *__restrict__ w, float *__restrict__
     }
 }
 
-template <int NQ, int RW, int KS>                                           // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps
+// the LDS geometry with the stride (file header, "Stride 2"): a (2 TR + 1) x 33 halo at an odd pitch for the 3x3 at stride 2, the stride-1 image otherwise
+constexpr int s3_xr(int tr, int ks, int st) { return st == 2 && ks == 3 ? 2 * tr + 1 : tr + ks - 1; }       // halo rows / columns of a tile
+constexpr int s3_xc(int ks, int st) { return st == 2 && ks == 3 ? 2 * S3_T + 1 : S3_T + ks - 1; }
+constexpr int s3_pitch_st(int tr, int ks, int st) { return st == 2 && ks == 3 ? (s3_xr(tr, ks, st) * s3_xc(ks, st)) | 1 : s3_pitch(tr, ks); }
+constexpr int s3_ndma_st(int tr, int ks, int st) { return (s3_ck(ks) * s3_pitch_st(tr, ks, st) + 511) / 512; }
+constexpr int s3_lds_st(int tr, int ks, int st) { return 2 * 8 * s3_ndma_st(tr, ks, st) * 64; }
+template <int NQ, int RW, int KS, int ST = 1>                               // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, stride ST
 __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int tx, int img) {
     constexpr int PD = KS == 3 ? 1 : 3;                                     // A operands PD pairs ahead: a 1x1 pair is 24 MFMAs (768 cycles), its operand is fetched three pairs ahead
     constexpr int NR = 8 / NQ, TR = NR * RW;                                // row groups per workgroup, tile rows
-    constexpr int S3_CK = s3_ck(KS), NPAIR = S3_CK / 4 * KS, NA4 = s3_na4(KS), S3_XC = S3_T + KS - 1;
-    constexpr int S3_PL = s3_pitch(TR, KS), S3_NDMA = s3_ndma(TR, KS), S3_BUF = 8 * S3_NDMA * 64, S3_XR = TR + KS - 1;
+    constexpr int S3_CK = s3_ck(KS), NPAIR = S3_CK / 4 * KS, NA4 = s3_na4(KS), S3_XC = s3_xc(KS, ST);
+    constexpr int S3_PL = s3_pitch_st(TR, KS, ST), S3_NDMA = s3_ndma_st(TR, KS, ST), S3_BUF = 8 * S3_NDMA * 64, S3_XR = s3_xr(TR, KS, ST);
+    constexpr int LS = ST == 2 && KS == 3 ? 2 : 1, NB = LS * (RW - 1) + KS;  // LDS cells between neighbouring outputs; B operands (halo rows) per pair
     static_assert(NPAIR % (PD + 1) == 0, "the operand ring's index must be static across chunks");
+    static_assert(NA4 * (PD - 1) + S3_NDMA <= 63, "s_waitcnt vmcnt takes at most 63 on gfx950");
+    static_assert(S3_CK * S3_PL <= S3_BUF && S3_XR * S3_XC <= S3_PL, "a chunk's planes fit its LDS image");
     float (*xs)[S3_BUF] = (float (*)[S3_BUF])lds;
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), mq = wave % NQ, nh = wave / NQ;
-    const int tr0 = a.ring + ty * (NR * a.rw), tc0 = a.ringw + tx * S3_T;    // input-grid cell of the tile's first output (a.rw: rows per wave of the ordinary tile rows)
+    // input-grid cell of the tile's first output (a.rw: rows per wave of the ordinary tile rows); ST = 2: its interior coordinates in the output
+    const int tr0 = (ST == 1 ? a.ring : 0) + ty * (NR * a.rw), tc0 = (ST == 1 ? a.ringw : 0) + tx * S3_T;
     const int blk = blockIdx.y, cblk = NQ * 48;
     const long PLg = (long)a.hp * a.wp;
     unsigned voff[S3_NDMA];
 #pragma unroll                                                              // (s3_cell_offsets' loop, in place: see there)
-    for (int i = 0; i < S3_NDMA; ++i) voff[i] = s3_cell_offset<S3_CK, S3_PL, S3_XR, S3_XC, KS>(a, tr0, tc0, (i * 8 + wave) * 64 + lane, PLg);
+    for (int i = 0; i < S3_NDMA; ++i) voff[i] = s3_cell_offset<S3_CK, S3_PL, S3_XR, S3_XC, KS, ST>(a, tr0, tc0, (i * 8 + wave) * 64 + lane, PLg);
     const float *xb = a.x + (long)img * a.cin * PLg;
     const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) const float *)&xs[0][0];
     auto issue_dma = [&](int ck) __attribute__((always_inline)) {
@@ -233,10 +269,10 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int ck = 0; ck < nck; ++ck) {
-        const float *xl = &xs[ck & 1][kq * S3_PL + nh * RW * S3_XC + col];
-        float b[2][RW + KS - 1];
+        const float *xl = &xs[ck & 1][kq * S3_PL + nh * RW * LS * S3_XC + col * LS];
+        float b[2][NB];
 #pragma unroll
-        for (int j = 0; j < RW + KS - 1; ++j) b[0][j] = xl[j * S3_XC];       // pair 0 of the chunk (the later pairs are read one pair ahead)
+        for (int j = 0; j < NB; ++j) b[0][j] = xl[j * S3_XC];                // pair 0 of the chunk (the later pairs are read one pair ahead)
 #pragma unroll
         for (int p = 0; p < NPAIR; ++p) {                                   // (4-channel group, kw) pairs of the chunk
             const int cur = p & 1, nxt = cur ^ 1, sa = p % (PD + 1), sn = (p + PD) % (PD + 1);
@@ -253,7 +289,7 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
             if (p + 1 < NPAIR) {
                 const int cgn = (p + 1) / KS, kwn = (p + 1) - KS * cgn;
 #pragma unroll
-                for (int j = 0; j < RW + KS - 1; ++j) b[nxt][j] = xl[cgn * 4 * S3_PL + j * S3_XC + kwn];
+                for (int j = 0; j < NB; ++j) b[nxt][j] = xl[cgn * 4 * S3_PL + j * S3_XC + kwn];
             }
 #pragma unroll
             for (int kh = 0; kh < KS; ++kh)
@@ -262,14 +298,15 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
 #pragma unroll
                     for (int m = 0; m < 3; ++m) {
                         const int e = 3 * kh + m;
-                        acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[sa][e >> 2][e & 3], b[cur][r + kh], acc[m][r], 0, 0, 0);
+                        acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[sa][e >> 2][e & 3], b[cur][LS * r + kh], acc[m][r], 0, 0, 0);
                     }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the next chunk's DMAs have landed (and the prefetched A operands)
         __syncthreads();
     }
 #undef S3_WAIT_A
-    s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
+    if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
+    else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
 }
 
 #include "sconv_bf16x3.inc"          // b3_body: the split-bf16 form of s3_body (its arithmetic, its pack kernel); everything around the bodies is below
@@ -293,6 +330,15 @@ __device__ __forceinline__ void sconv_workgroup(const S3Args &a) {
     }
     sconv_body<B3, NQ, RW, KS>(a, lds, ty, tx, img);
 }
+// the stride-2 workgroup (fp32 form): no tall last tile row -- (2 (TR + NR) + 1) x 33 halos do not fit LDS twice -- a remainder takes an ordinary tile row
+template <int NQ, int RW, int KS>
+__device__ __forceinline__ void sconv_s2_workgroup(const S3Args &a) {
+    __shared__ __attribute__((aligned(16))) float lds[s3_lds_st(8 / NQ * RW, KS, 2)];
+    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
+    const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
+    s3_body<NQ, RW, KS, 2>(a, lds, ty, tx, img);
+}
+template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3s2(S3Args a) { sconv_s2_workgroup<NQ, RW, KS>(a); }
 // (two kernel names, so that a profile tells the forms apart)
 template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3(S3Args a) { sconv_workgroup<false, NQ, RW, KS>(a); }
 template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv_b3(S3Args a) { sconv_workgroup<true, NQ, RW, KS>(a); }
@@ -354,6 +400,35 @@ static int sconv_launch(void *stream, const float *x, const void *packed, const 
     return 0;
 }
 
+// the stride-2 forms: x [n][cin][hp][wp] with a `pad` apron and an even interior H x W; out / residual [n][cout][H / 2 + 2 oring][W / 2 + 2 oring], whose
+// interior window is written.  S3Args: hp / wp / pad / sphere are the input's, ohp / owp / ring / ringw the output's grid and window.
+static int sconv_s2_launch(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
+                           int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring, int ks) {
+    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(false, cin, cout, ks) && pad >= 0 && oring >= 0 && hp > 2 * pad && wp > 2 * pad && sphere >= 0 && sphere <= 1);
+    ARG_CHECK((hp - 2 * pad) % 2 == 0 && (wp - 2 * pad) % 2 == 0);           // even interiors: the last tap row / column is the interior's last
+    ARG_CHECK(ks == 1 || pad >= 1);                                         // the 3x3 taps reach one apron row above / column left of the interior
+    ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
+    ARG_CHECK((double)s3_ck(ks) * hp * wp * 4.0 < 4294967296.0 && ((uintptr_t)bias & 15) == 0 && (!slope || ((uintptr_t)slope & 15) == 0));
+    S3Args a;
+    a.x = x; a.w = packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
+    a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = oring; a.ringw = oring;
+    const int oh = (hp - 2 * pad) / 2, ow = (wp - 2 * pad) / 2;
+    ARG_CHECK((long)oh + 2L * oring < (1L << 30) && (long)ow + 2L * oring < (1L << 30));
+    a.ooff = 0; a.ohp = oh + 2 * oring; a.owp = ow + 2 * oring; a.shuffle = 0; a.tall_last = 0;
+    const int nq = cout % 192 == 0 ? 4 : 2;
+    a.rw = S3_T / (8 / nq);
+    a.tiles_x = (ow + S3_T - 1) / S3_T; a.tiles_y = (oh + S3_T - 1) / S3_T;
+    const long tiles = (long)n * a.tiles_x * a.tiles_y;
+    ARG_CHECK(tiles < (1L << 31));
+    const dim3 grid((unsigned)tiles, nq == 4 ? cout / 192 : 1);
+    if (ks == 3 && nq == 4) hipLaunchKernelGGL((k_sconv3x3s2<4, 8, 3>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else if (ks == 3) hipLaunchKernelGGL((k_sconv3x3s2<2, 4, 3>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else if (nq == 4) hipLaunchKernelGGL((k_sconv3x3s2<4, 8, 1>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_sconv3x3s2<2, 4, 1>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 LIC360_API int lic360_sconv3x3_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 3) ? 1 : 0; }
 LIC360_API long lic360_sconv3x3_packed_floats(int cin, int cout) { return s3_packed(cin, cout, 3); }
 LIC360_API int lic360_sconv3x3_pack(void *stream, const float *weight, float *packed, int cin, int cout) { return s3_pack(stream, weight, packed, cin, cout, 3); }
@@ -383,4 +458,15 @@ LIC360_API int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, vo
 LIC360_API int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                       int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
     return sconv_launch<true>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+}
+// the stride-2 forms of the fp32 pair (the analysis transform's down-sampling layers); they read the stride-1 packs
+LIC360_API int lic360_sconv3x3s2_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 3) ? 1 : 0; }
+LIC360_API int lic360_sconv3x3s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                 int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring) {
+    return sconv_s2_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, oring, 3);
+}
+LIC360_API int lic360_sconv1x1s2_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 1) ? 1 : 0; }
+LIC360_API int lic360_sconv1x1s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                 int n, int cin, int cout, int hp, int wp, int pad, int oring) {
+    return sconv_s2_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, 0, oring, 1);
 }

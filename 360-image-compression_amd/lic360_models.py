@@ -6,8 +6,11 @@ load with `load_state_dict`: the same module tree (`encoder.net.N...`, `decoder.
 generic pieces.  When no gradient is recorded, the 3x3 stride-1 convolutions of 96 / 192 channels on maps large enough to fill the chip run
 on this package's own kernel (csrc/conv3x3_kernels.hip, `lic360.sconv3x3`): fp32 MFMA, the sphere apron read by index in its tile loader
 (no in-place SpherePad in front of it), bias + PReLU + the residual add in its epilogue, the SphereTrim behind it as its output window;
-set_conv_precision(model, "bf16x3") moves these fused layers to their split-bf16 forms (csrc/sconv_bf16x3.inc), per module.
-The stride-2 and 1x1 convolutions, small maps and every recording (training) pass are library work (torch -> MIOpen); native around them:
+the blocks' 1x1 layers ride on the same body (`lic360.sconv1x1`), and so do the down-sampling layers of the analysis transform: the 3x3
+stride-2 convolutions and the 1x1 stride-2 shortcuts of the hidden stages (`lic360.sconv3x3s2` / `sconv1x1s2`, the body's stride-2 forms).
+set_conv_precision(model, "bf16x3") moves the stride-1 fused layers to their split-bf16 forms (csrc/sconv_bf16x3.inc), per module.
+The first stage's stride-2 layers (3 input channels: no 16-channel chunk, and bound by their output, not by MFMAs), convolutions off the fused
+shapes, small maps and every recording (training) pass are library work (torch -> MIOpen); native around them:
 sphere pad / trim / cut-edge / pixel-shuffle / importance map / quantiser kernels and the one-pass GDN (csrc/gdn_kernels.hip)."""
 import torch
 from torch import nn
@@ -24,6 +27,10 @@ FUSED_MIN_WORKGROUPS = 256          # lic360.sconv3x3 is used when its workgroup
 
 
 FUSED_MIN_FILL = 0.8
+FUSED_S2_MIN_WORKGROUPS = 128       # lic360.sconv3x3s2 / sconv1x1s2 (one workgroup per 16x16 tile of the OUTPUT window and 192 channels, one workgroup per CU: a round of
+                                    # up to 256 takes 0.334 ms at 192 -> 192) are used from this many workgroups on: the smallest count from which they are not slower than
+                                    # SpherePad + MIOpen on any measured shape (batches 1..32: tools/conv3x3_probe.py --s2, profiles/sconv_s2_probe.json; at 64 the
+                                    # 3x3 loses 1.8x, so SphereConv2 -- 8 tiles per image -- stays on the library below batch 16); past one round the FUSED_MIN_FILL rule holds
 
 
 def _fusable(conv, x, ring, ring_w=None, mod=None):
@@ -44,12 +51,32 @@ def _fusable(conv, x, ring, ring_w=None, mod=None):
     return tiles >= FUSED_MIN_WORKGROUPS and tiles >= FUSED_MIN_FILL * 256 * ((tiles + 255) // 256)
 
 
+def _fusable_s2(conv, x, mod=None):
+    """does this stride-2 convolution (3x3 or the 1x1 shortcut) of the 2-cell-apron map x run on lic360.sconv3x3s2 / sconv1x1s2?  The rules of
+    _fusable (inference only, fp32, contiguous, a bias, a supported shape), an even interior, and enough tiles of the OUTPUT window: at least FUSED_S2_MIN_WORKGROUPS,
+    and past one round of the 256 CUs whole rounds filled to FUSED_MIN_FILL as in _fusable (one round of 128 or more already wins as measured)."""
+    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (mod is not None and any(p.requires_grad for p in mod.parameters()))):
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and conv.bias is not None):
+        return False
+    cout, cin = conv.weight.shape[:2]
+    if not (lic360.sconv3x3s2_supported if conv.kernel_size[0] == 3 else lic360.sconv1x1s2_supported)(cin, cout):
+        return False
+    n, _, hp, wp = x.shape
+    h, w = hp - 4, wp - 4
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        return False
+    tiles = n * ((h // 2 + 15) // 16) * ((w // 2 + 15) // 16) * (cout // 192 if cout % 192 == 0 else 1)
+    return tiles >= FUSED_S2_MIN_WORKGROUPS and (tiles <= 256 or tiles >= FUSED_MIN_FILL * 256 * ((tiles + 255) // 256))
+
+
 CONV_PRECISIONS = ("fp32", "bf16x3")
 
 
 def set_conv_precision(module, precision):
     """arithmetic of the fused convolutions of every block under `module` (module.modules()): "fp32" (the default: lic360.sconv3x3 / sconv1x1) or
     "bf16x3" (their split-bf16 forms wherever those take the layer's shape, the fp32 kernel elsewhere; about 2^-16 relative error per product).
+    The stride-2 layers have no split-bf16 form: in "bf16x3" mode they stay on the fp32 stride-2 kernel (lic360.sconv3x3s2 / sconv1x1s2).
     A per-module setting, not a global: several copies of the networks may run side by side in different modes.  Library layers, small maps and
     recording passes are the same in either mode.  Returns `module`."""
     if precision not in CONV_PRECISIONS:
@@ -76,13 +103,25 @@ def _sconv(mod, conv, x, slope, residual, out, **kw):
     if precision != "fp32" and not getattr(lic360, _SCONV[ks, precision][2])(cin, cout):
         precision = "fp32"
     fn, pack, _ = _SCONV[ks, precision]
+    return getattr(lic360, fn)(x, _packed(conv, precision, pack), conv.bias, slope, residual, out, **kw)
+
+
+def _packed(conv, precision, pack):
     key = (conv.weight.data_ptr(), conv.weight._version)
     packs = getattr(conv, "_sconv_packs", None)                             # precision -> (key, packed)
     if packs is None:
         packs = conv._sconv_packs = {}
     if packs.get(precision, (None, None))[0] != key:
         packs[precision] = (key, getattr(lic360, pack)(conv.weight.detach()))
-    return getattr(lic360, fn)(x, packs[precision][1], conv.bias, slope, residual, out, **kw)
+    return packs[precision][1]
+
+
+def _sconv_s2(conv, x, slope, residual, out):
+    """the stride-2 convolution `conv` (3x3 or the 1x1 shortcut) of a 2-cell-apron map on lic360.sconv3x3s2 / sconv1x1s2: fp32 in every precision
+    mode of the block (there is no split-bf16 stride-2 form), on the stride-1 fp32 pack of the weight"""
+    ks = conv.kernel_size[0]
+    fn, pack, _ = _SCONV[ks, "fp32"]
+    return getattr(lic360, fn + "s2")(x, _packed(conv, "fp32", pack), conv.bias, slope, residual, out, pad=2, oring=2)
 
 
 def _scratch(shape, like):
@@ -179,6 +218,16 @@ class ResidualBlockDown(nn.Module):
         self.hidden = hidden
 
     def forward(self, x):
+        if self.hidden and _fusable_s2(self.conv1, x, self) and _fusable_s2(self.short_cut, x, self):
+            n, _, hp, wp = x.shape
+            shape = (n, self.conv1.out_channels, (hp - 4) // 2 + 4, (wp - 4) // 2 + 4)
+            y = _scratch(shape, x)
+            if _fusable(self.conv2, y, 2, mod=self):                        # (the whole block goes one way: FUSED_MIN_WORKGROUPS rules its stride-2 layers too)
+                # conv1 reads x's apron by index (no pad1: x is not modified), conv2 reads conv1's likewise, GDN is pointwise, the shortcut reads the interior
+                # only and adds the GDN output in its epilogue; every apron cell on the way is scratch, the final trim zeroes the output's
+                _sconv_s2(self.conv1, x, self.relu1.weight, None, y)
+                y = self.relu2(_sconv(self, self.conv2, y, None, None, _scratch(shape, x), pad=2, sphere=True, ring=2))
+                return self.trim(_sconv_s2(self.short_cut, x, None, y, _scratch(shape, x)))
         if self.hidden:
             skip = self.short_cut(x)                                        # before pad1 refreshes the apron in place
             y = self.pad1(x)
@@ -206,6 +255,9 @@ class SphereConv2(nn.Module):
         self.pad, self.trim = SpherePad(2, device_id, True), SphereTrim(2, device_id)
 
     def forward(self, x):
+        c = self.conv
+        if (c.kernel_size, c.stride, c.padding) == ((3, 3), (2, 2), (3, 3)) and type(self) is SphereConv2 and _fusable_s2(c, x, self):
+            return _sconv_s2(c, x, None, None, None)                        # pad, convolution and trim: the interior window of a zero-filled map
         return self.trim(self.conv(self.pad(x)))
 
 

@@ -367,6 +367,21 @@ long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout);
 int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout);
 int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                            int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle);
+/* ---- the stride-2 (down-sampling) forms of the two, fp32, on the same kernel body with a stride parameter (csrc/conv3x3_kernels.hip).
+ * lic360_sconv3x3s2 replaces the in-place SpherePad(2) + nn.Conv2d(cin, c, 3, 2, 3) + nn.PReLU + SphereTrim of test/model_zoo.py:64-106
+ * (ResidualBlockDown.conv1, SphereConv2); lic360_sconv1x1s2 replaces nn.Conv2d(cin, c, 1, 2, 2) + the `t + y` add of ResidualBlockDown.short_cut.
+ * x [n][cin][hp][wp] with a pad-cell apron, interior H x W = (hp - 2 pad) x (wp - 2 pad), both even; out (and residual: the OUTPUT's geometry)
+ * [n][cout][H / 2 + 2 oring][W / 2 + 2 oring].  With X(r, c) the value the sphere rule puts at interior coordinates (r, c) (sphere = 0: the apron cell
+ * as it is), interior output (i, j) = bias + sum w[kh][kw] X(2 i + kh - 1, 2 j + kw - 1), resp. bias + w X(2 i, 2 j); PReLU if slope; + residual if given.
+ * The interior window [oring, oring + H / 2) x [oring, oring + W / 2) of out is written, every other cell left untouched.  The 3x3 form reads one apron
+ * row above and one apron column left of the interior (pad >= 1), the 1x1 form the interior only.  packed = the STRIDE-1 packs (lic360_sconv3x3_pack,
+ * lic360_sconv1x1_pack); shapes as the stride-1 forms (cin % 16 resp. % 32, cout = 96 or a multiple of 192); bias / slope 16-byte aligned. */
+int lic360_sconv3x3s2_supported(int cin, int cout);
+int lic360_sconv3x3s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
+                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring);
+int lic360_sconv1x1s2_supported(int cin, int cout);
+int lic360_sconv1x1s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
+                      int n, int cin, int cout, int hp, int wp, int pad, int oring);
 /* apron of dst <- sphere-wrapped interior of src (src == dst: lic360_sphere_pad_inplace); [nc][hp][wp] planes      sphere_pad_cuda.cu:48-65 */
 int lic360_sphere_apron_from(void *stream, const float *src, float *dst, int nc, int hp, int wp, int pad);
 

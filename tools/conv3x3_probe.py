@@ -1,8 +1,11 @@
 """lic360_sconv3x3 (csrc/conv3x3_kernels.hip) next to torch.nn.functional.conv2d (MIOpen) on the transforms' 3x3 stride-1 shapes, batch 8:
 correctness (max |diff| against conv2d over the sphere-padded map, fp32) and time per launch -- the library form timed WITH the launches the
 fused kernel absorbs (in-place apron refresh, PReLU, trim) and without.  VERDICT r4 next #2.
---precision bf16x3: "ours" is the split-bf16 form (lic360_sconv3x3_bf16x3 / sconv1x1_bf16x3), timed in the same run next to the fp32 kernel."""
-import argparse, os, sys
+--precision bf16x3: "ours" is the split-bf16 form (lic360_sconv3x3_bf16x3 / sconv1x1_bf16x3), timed in the same run next to the fp32 kernel.
+--s2: the stride-2 forms instead (lic360_sconv3x3s2 / sconv1x1s2) on the analysis transform's three down-sampling shapes and two shortcuts, batches
+1, 2, 4, 8, 32, each next to the library form of the same work (in-place SpherePad + conv2d(stride 2) + PReLU; shortcut conv2d + add + trim): median
+of alternating repeats with the spread, and the smallest tile count from which the native form is not slower on any shape; --json FILE keeps the table."""
+import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "360-image-compression_amd"))
 import torch
@@ -12,7 +15,10 @@ import lic360
 dev = "cuda:0"
 ap = argparse.ArgumentParser()
 ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32")
-B3 = ap.parse_args().precision == "bf16x3"
+ap.add_argument("--s2", action="store_true")
+ap.add_argument("--json", default=None)
+ARGS = ap.parse_args()
+B3 = ARGS.precision == "bf16x3"
 
 
 def timed(fn, reps=10):
@@ -24,6 +30,65 @@ def timed(fn, reps=10):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
 
+
+def s2_probe():
+    rows = []
+    batches = [int(v) for v in os.environ.get("S3_BATCHES", "1,2,4,8,32").split(",")]
+    pad_op, trim_op = lic360.SpherePadOp(2, True, 0, False), lic360.SphereTrimOp(2, 0, False)
+    for ks, hp, wp, what in ((3, 260, 516, "stage-2 conv1"), (3, 132, 260, "stage-3 conv1"), (3, 68, 132, "SphereConv2"),
+                             (1, 260, 516, "stage-2 shortcut"), (1, 132, 260, "stage-3 shortcut")):
+        for n in batches:
+            c = 192
+            oh, ow = (hp - 4) // 2, (wp - 4) // 2
+            x = torch.randn(n, c, hp, wp, device=dev)
+            w = torch.randn(c, c, ks, ks, device=dev) * 0.05
+            b, sl = torch.randn(c, device=dev), torch.rand(c, device=dev) * 0.5
+            res = torch.randn(n, c, oh + 4, ow + 4, device=dev)
+            out = torch.zeros(n, c, oh + 4, ow + 4, device=dev)
+            if ks == 3:
+                pk = lic360.sconv3x3_pack(w)
+                slope = None if what == "SphereConv2" else sl
+                def lib():                                                  # SpherePad in place + conv + PReLU (SphereConv2: + trim, no PReLU)
+                    y = F.conv2d(pad_op.forward(x)[0], w, b, 2, 3)
+                    return trim_op.forward(y)[0] if slope is None else F.prelu(y, slope)
+                ours = lambda: lic360.sconv3x3s2(x, pk, b, slope, None, out, pad=2, sphere=True, oring=2)
+            else:
+                pk = lic360.sconv1x1_pack(w)
+                lib = lambda: trim_op.forward(F.conv2d(x, w, b, 2, 2) + res)[0]      # shortcut + the block's add + its final trim
+                ours = lambda: lic360.sconv1x1s2(x, pk, b, None, res, out, pad=2, oring=2)
+            win = (slice(None), slice(None), slice(2, 2 + oh), slice(2, 2 + ow))
+            err = (ours()[win] - lib()[win]).abs().max().item()
+            tl, to = [], []
+            for _ in range(5):                                              # alternating repeats
+                tl.append(timed(lib, 40))
+                to.append(timed(ours, 40))
+            tiles = n * ((oh + 15) // 16) * ((ow + 15) // 16)
+            row = dict(layer=what, ks=ks, n=n, hp=hp, wp=wp, tiles=tiles, max_abs_diff=err, library_ms=sorted(tl)[2], library_min=min(tl), library_max=max(tl),
+                       native_ms=sorted(to)[2], native_min=min(to), native_max=max(to), native_over_library=sorted(to)[2] / sorted(tl)[2])
+            rows.append(row)
+            print("s2 %dx%d %-16s @%dx%d x%-2d (%4d tiles): max|diff| %.2e | library %.3f ms (%.3f .. %.3f) | native %.3f ms (%.3f .. %.3f) | native / library = %.2f" % (
+                ks, ks, what, hp, wp, n, tiles, err, row["library_ms"], row["library_min"], row["library_max"], row["native_ms"], row["native_min"], row["native_max"],
+                row["native_over_library"]), flush=True)
+            del x, res, out
+    # the smallest tile count from which the native form is not slower (medians) on every measured (shape, batch) with at least that many tiles
+    counts = sorted({r["tiles"] for r in rows})
+    thr = None
+    for t in reversed(counts):
+        if all(r["native_over_library"] <= 1.0 for r in rows if r["tiles"] >= t):
+            thr = t
+        else:
+            break
+    print("smallest tile count from which the native form is not slower on any measured shape: %s" % thr, flush=True)
+    if ARGS.json:
+        with open(ARGS.json, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), repeats="median of 5 alternating repeats of 40 launches, each after 3 warm-up launches; ms per launch",
+                           threshold_tiles=thr, rows=rows), f, indent=1)
+
+
+if ARGS.s2:
+    torch.manual_seed(0)
+    s2_probe()
+    sys.exit(0)
 
 torch.manual_seed(0)
 # ring 1 = the first convolution of ResidualBlockV2: rows of the 1-ring window, columns of the interior (its 1-ring columns repeat interior columns: ring_w = 2)

@@ -221,7 +221,37 @@ def ab_transforms(batch=8, device=0, reps=3, repeats=5):
     print(json.dumps({"summary": "median of %d alternating repeats" % repeats, **med, **spread}))
 
 
+def ab_stride2(batch=8, device=0, reps=3, repeats=5):
+    """analysis ms per image with the stride-2 layers on lic360.sconv3x3s2 / sconv1x1s2 and on the library (FUSED_S2_MIN_WORKGROUPS out of reach: the
+    launches the models made before the stride-2 kernels existed), alternating on the same networks and inputs; the synthesis transform, which has no
+    stride-2 layer, is timed in each turn as the control for drift"""
+    import lic360_models as lm
+    dev = "cuda:%d" % device
+    torch.manual_seed(0)
+    enc, dec = lm.CMP_Encoder(gpu_id=device).to(dev).eval(), lm.CMP_Decoder(gpu_id=device).to(dev).eval()
+    native_thr = lm.FUSED_S2_MIN_WORKGROUPS
+    t = {(p, k): [] for p in ("native", "library") for k in ("analysis", "synthesis")}
+    with torch.no_grad():
+        img = torch.rand((batch, 3, 512, 1024), device=dev)
+        code, mask, _ = enc(img)
+        for i in range(repeats):
+            for p in ("native", "library"):
+                lm.FUSED_S2_MIN_WORKGROUPS = native_thr if p == "native" else 1 << 30
+                row = {"repeat": i, "stride2": p, "batch": batch}
+                for k, fn in (("analysis", lambda: enc(img)), ("synthesis", lambda: dec(code, mask))):
+                    row[k + "_ms_per_image"] = timed(fn, reps) / batch * 1e3
+                    t[(p, k)].append(row[k + "_ms_per_image"])
+                print(json.dumps(row), flush=True)
+    lm.FUSED_S2_MIN_WORKGROUPS = native_thr
+    med = {"%s_%s_ms_per_image" % (k, p): sorted(v)[len(v) // 2] for (p, k), v in t.items()}
+    spread = {"%s_%s_min_max" % (k, p): [min(v), max(v)] for (p, k), v in t.items()}
+    print(json.dumps({"summary": "median of %d alternating repeats, batch %d, FUSED_S2_MIN_WORKGROUPS %d" % (repeats, batch, native_thr), **med, **spread}))
+
+
 if __name__ == "__main__":
+    if "--ab-s2" in sys.argv:
+        ab_stride2()
+        sys.exit(0)
     if "--ab" in sys.argv:
         ab_transforms()
         sys.exit(0)
