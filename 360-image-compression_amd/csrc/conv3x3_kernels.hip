@@ -32,10 +32,10 @@
 //   1x1      the loader fetches the even / even cells only: LDS image, reads and waits are the stride-1 1x1's.
 // The weight packs are the stride-1 ones.  The stride-1 instantiations compile to the instructions they had before the stride parameter existed.
 //
-// Two arithmetic forms, one of everything else.  s3_body (here) is the fp32 form, b3_body (sconv_bf16x3.inc, opt-in) the split-bf16 form; they
-// differ in their chunk loop, LDS layout and weight pack.  What decides which cells a convolution reads and writes exists once and serves both:
-// s3_cell_offset (the source cell of a loader's LDS cell), s3_epilogue (bias, PReLU, residual, window test, store), the kernel wrapper sconv_workgroup<B3, ..>
-// (tile decode, tall last tile row) and the host's sconv_launch<B3> (shape predicate, argument contract, tile geometry, grid).
+// Three arithmetic forms, one of everything else.  s3_body (here) is the fp32 form, b3_body (sconv_bf16x3.inc, opt-in) the split-bf16 form ("bf16x3") and,
+// with its lo parts left out, the single-pass bf16 form ("bf16x1"); they differ in their chunk loop, LDS layout and weight pack.  What decides which cells a convolution reads and writes exists once and serves both:
+// s3_cell_offset (the source cell of a loader's LDS cell), s3_epilogue (bias, PReLU, residual, window test, store), the kernel wrapper sconv_workgroup<NT, ..>
+// (tile decode, tall last tile row) and the host's sconv_launch<NT> (shape predicate, argument contract, tile geometry, grid).
 #include "common.h"
 #include <cstdint>
 
@@ -309,26 +309,27 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
     else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
 }
 
-#include "sconv_bf16x3.inc"          // b3_body: the split-bf16 form of s3_body (its arithmetic, its pack kernel); everything around the bodies is below
+#include "sconv_bf16x3.inc"          // b3_body: the split-bf16 and single-pass bf16 forms of s3_body (arithmetic, pack kernel); everything around the bodies is below
 
-// ---- one workgroup wrapper, one launch for both forms (B3: the split-bf16 body).
-template <bool B3, int NQ, int RW, int KS>
+// ---- one workgroup wrapper, one launch for all forms.  NT = bf16 MFMAs per product: 0 the fp32 body, 3 the split-bf16 body, 1 its single-pass form.
+template <int NT, int NQ, int RW, int KS>
 __device__ __forceinline__ void sconv_body(const S3Args &a, float *lds, int ty, int tx, int img) {
-    if constexpr (B3) b3_body<NQ, RW, KS>(a, lds, ty, tx, img);
+    if constexpr (NT == 3) b3_body<NQ, RW, KS>(a, lds, ty, tx, img);
+    else if constexpr (NT == 1) b3_body<NQ, RW, KS, 1>(a, lds, ty, tx, img);
     else s3_body<NQ, RW, KS>(a, lds, ty, tx, img);
 }
 // A window of 16 k + 2 rows (every 1-ring window of these maps) would need a seventeenth tile row with 14 dead rows; instead its LAST tile row
 // runs one more row per wave (18 rows at 192 channels, 20 at 96): the workgroup picks its body by its tile row (uniform per workgroup).
-template <bool B3, int NQ, int RW, int KS>
+template <int NT, int NQ, int RW, int KS>
 __device__ __forceinline__ void sconv_workgroup(const S3Args &a) {
     constexpr int TR = 8 / NQ * (RW + (KS == 3 ? 1 : 0));                   // rows of the tallest tile
-    __shared__ __attribute__((aligned(16))) float lds[B3 ? b3_lds(TR, KS) : s3_lds(TR, KS)];
+    __shared__ __attribute__((aligned(16))) float lds[NT ? b3_lds(TR, KS, NT) : s3_lds(TR, KS)];
     static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
     const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
     if constexpr (KS == 3) {
-        if (a.tall_last && ty == a.tiles_y - 1) { sconv_body<B3, NQ, RW + 1, 3>(a, lds, ty, tx, img); return; }
+        if (a.tall_last && ty == a.tiles_y - 1) { sconv_body<NT, NQ, RW + 1, 3>(a, lds, ty, tx, img); return; }
     }
-    sconv_body<B3, NQ, RW, KS>(a, lds, ty, tx, img);
+    sconv_body<NT, NQ, RW, KS>(a, lds, ty, tx, img);
 }
 // the stride-2 workgroup (fp32 form): no tall last tile row -- (2 (TR + NR) + 1) x 33 halos do not fit LDS twice -- a remainder takes an ordinary tile row
 template <int NQ, int RW, int KS>
@@ -339,44 +340,46 @@ __device__ __forceinline__ void sconv_s2_workgroup(const S3Args &a) {
     s3_body<NQ, RW, KS, 2>(a, lds, ty, tx, img);
 }
 template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3s2(S3Args a) { sconv_s2_workgroup<NQ, RW, KS>(a); }
-// (two kernel names, so that a profile tells the forms apart)
-template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3(S3Args a) { sconv_workgroup<false, NQ, RW, KS>(a); }
-template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv_b3(S3Args a) { sconv_workgroup<true, NQ, RW, KS>(a); }
-template <bool B3, int NQ, int RW, int KS>
+// (a kernel name per form, so that a profile tells the forms apart)
+template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3(S3Args a) { sconv_workgroup<0, NQ, RW, KS>(a); }
+template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv_b3(S3Args a) { sconv_workgroup<3, NQ, RW, KS>(a); }
+template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv_b1(S3Args a) { sconv_workgroup<1, NQ, RW, KS>(a); }
+template <int NT, int NQ, int RW, int KS>
 static auto sconv_kernel() {
-    if constexpr (B3) return &k_sconv_b3<NQ, RW, KS>;
+    if constexpr (NT == 3) return &k_sconv_b3<NQ, RW, KS>;
+    else if constexpr (NT == 1) return &k_sconv_b1<NQ, RW, KS>;
     else return &k_sconv3x3<NQ, RW, KS>;
 }
 
 // the forms differ in their chunk of input channels (and so in the shapes they take), in the pack, and in the body
-static inline int sconv_ck(bool b3, int ks) { return b3 ? B3_CK : s3_ck(ks); }
-static inline bool sconv_ok(bool b3, int cin, int cout, int ks) {
-    return (ks == 3 || ks == 1) && cin >= sconv_ck(b3, ks) && cin % sconv_ck(b3, ks) == 0 && cout >= 96 && (cout % 192 == 0 || cout == 96);
+static inline int sconv_ck(int nt, int ks) { return nt ? B3_CK : s3_ck(ks); }
+static inline bool sconv_ok(int nt, int cin, int cout, int ks) {
+    return (ks == 3 || ks == 1) && cin >= sconv_ck(nt, ks) && cin % sconv_ck(nt, ks) == 0 && cout >= 96 && (cout % 192 == 0 || cout == 96);
 }
-static inline long s3_packed(int cin, int cout, int ks) { return sconv_ok(false, cin, cout, ks) ? (long)cout / 48 * (cin / 4) * ks * s3_na4(ks) * 256 : 0; }
-static inline long b3_packed_bytes(int cin, int cout, int ks) { return sconv_ok(true, cin, cout, ks) ? (long)cout * cin * ks * ks * 4 : 0; }   // hi + lo bf16 per weight
+static inline long s3_packed(int cin, int cout, int ks) { return sconv_ok(0, cin, cout, ks) ? (long)cout / 48 * (cin / 4) * ks * s3_na4(ks) * 256 : 0; }
+static inline long b3_packed_bytes(int nt, int cin, int cout, int ks) { return sconv_ok(nt, cin, cout, ks) ? (long)cout * cin * ks * ks * (nt == 3 ? 4 : 2) : 0; }   // hi + lo bf16 per weight, or hi
 static int s3_pack(void *stream, const float *weight, float *packed, int cin, int cout, int ks) {
-    ARG_CHECK(weight && packed && sconv_ok(false, cin, cout, ks));
+    ARG_CHECK(weight && packed && sconv_ok(0, cin, cout, ks));
     const long total = s3_packed(cin, cout, ks);
     hipLaunchKernelGGL(k_sconv3x3_pack, dim3(lic360_blocks(total, 4)), dim3(256), 0, (hipStream_t)stream, weight, packed, cin, cout, cout % 192 == 0 ? 4 : 2, ks, total);
     LAUNCH_CHECK();
     return 0;
 }
-static int b3_pack(void *stream, const float *weight, void *packed, int cin, int cout, int ks) {
-    ARG_CHECK(weight && packed && sconv_ok(true, cin, cout, ks) && ((uintptr_t)packed & 15) == 0);
-    const long total = b3_packed_bytes(cin, cout, ks) / 16;
+static int b3_pack(int nt, void *stream, const float *weight, void *packed, int cin, int cout, int ks) {
+    ARG_CHECK(weight && packed && sconv_ok(nt, cin, cout, ks) && ((uintptr_t)packed & 15) == 0);
+    const long total = b3_packed_bytes(nt, cin, cout, ks) / 16;
     hipLaunchKernelGGL(k_sconv_b3_pack, dim3(lic360_blocks(total)), dim3(256), 0, (hipStream_t)stream, weight, (b3_u4 *)packed, cin, cout,
-                       cout % 192 == 0 ? 4 : 2, ks, total);
+                       cout % 192 == 0 ? 4 : 2, ks, nt == 3 ? 2 : 1, total);
     LAUNCH_CHECK();
     return 0;
 }
-template <bool B3>
+template <int NT>
 static int sconv_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                         int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle) {
-    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(B3, cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w &&
+    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(NT, cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w &&
               out_crop >= 0 && out_crop <= ring && sphere >= 0 && sphere <= 2);
     ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
-    ARG_CHECK((double)sconv_ck(B3, ks) * hp * wp * 4.0 < 4294967296.0 && (!B3 || ((uintptr_t)packed & 15) == 0) && ((uintptr_t)bias & 15) == 0 &&
+    ARG_CHECK((double)sconv_ck(NT, ks) * hp * wp * 4.0 < 4294967296.0 && (!NT || ((uintptr_t)packed & 15) == 0) && ((uintptr_t)bias & 15) == 0 &&
               (!slope || ((uintptr_t)slope & 15) == 0));                    // a chunk's cells at 32-bit byte offsets; 16-byte operand loads
     ARG_CHECK(!residual || out_crop == 0 || shuffle);                       // the residual has the input's geometry -- or, shuffled, the output's
     ARG_CHECK(!shuffle || (((uintptr_t)out & 7) == 0 && ((uintptr_t)residual & 7) == 0));   // the shuffled store / residual load move aligned pairs
@@ -392,10 +395,10 @@ static int sconv_launch(void *stream, const float *x, const void *packed, const 
     const long tiles = (long)n * a.tiles_x * a.tiles_y;
     ARG_CHECK(tiles < (1L << 31));
     const dim3 grid((unsigned)tiles, nq == 4 ? cout / 192 : 1);
-    if (ks == 3 && nq == 4) hipLaunchKernelGGL((sconv_kernel<B3, 4, 8, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (ks == 3) hipLaunchKernelGGL((sconv_kernel<B3, 2, 4, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (nq == 4) hipLaunchKernelGGL((sconv_kernel<B3, 4, 8, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((sconv_kernel<B3, 2, 4, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    if (ks == 3 && nq == 4) hipLaunchKernelGGL((sconv_kernel<NT, 4, 8, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else if (ks == 3) hipLaunchKernelGGL((sconv_kernel<NT, 2, 4, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else if (nq == 4) hipLaunchKernelGGL((sconv_kernel<NT, 4, 8, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((sconv_kernel<NT, 2, 4, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK();
     return 0;
 }
@@ -404,7 +407,7 @@ static int sconv_launch(void *stream, const float *x, const void *packed, const 
 // interior window is written.  S3Args: hp / wp / pad / sphere are the input's, ohp / owp / ring / ringw the output's grid and window.
 static int sconv_s2_launch(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                            int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring, int ks) {
-    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(false, cin, cout, ks) && pad >= 0 && oring >= 0 && hp > 2 * pad && wp > 2 * pad && sphere >= 0 && sphere <= 1);
+    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(0, cin, cout, ks) && pad >= 0 && oring >= 0 && hp > 2 * pad && wp > 2 * pad && sphere >= 0 && sphere <= 1);
     ARG_CHECK((hp - 2 * pad) % 2 == 0 && (wp - 2 * pad) % 2 == 0);           // even interiors: the last tap row / column is the interior's last
     ARG_CHECK(ks == 1 || pad >= 1);                                         // the 3x3 taps reach one apron row above / column left of the interior
     ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
@@ -429,43 +432,58 @@ static int sconv_s2_launch(void *stream, const float *x, const float *packed, co
     return 0;
 }
 
-LIC360_API int lic360_sconv3x3_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 3) ? 1 : 0; }
+LIC360_API int lic360_sconv3x3_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 3) ? 1 : 0; }
 LIC360_API long lic360_sconv3x3_packed_floats(int cin, int cout) { return s3_packed(cin, cout, 3); }
 LIC360_API int lic360_sconv3x3_pack(void *stream, const float *weight, float *packed, int cin, int cout) { return s3_pack(stream, weight, packed, cin, cout, 3); }
 LIC360_API int lic360_sconv3x3(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    return sconv_launch<false>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+    return sconv_launch<0>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
 }
 // the transforms' 1x1 layers on the same body (K = input channels only, no halo): bias + PReLU + residual in the epilogue, the window as above
-LIC360_API int lic360_sconv1x1_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 1) ? 1 : 0; }
+LIC360_API int lic360_sconv1x1_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 1) ? 1 : 0; }
 LIC360_API long lic360_sconv1x1_packed_floats(int cin, int cout) { return s3_packed(cin, cout, 1); }
 LIC360_API int lic360_sconv1x1_pack(void *stream, const float *weight, float *packed, int cin, int cout) { return s3_pack(stream, weight, packed, cin, cout, 1); }
 LIC360_API int lic360_sconv1x1(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
-    return sconv_launch<false>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+    return sconv_launch<0>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
 }
 // the split-bf16 forms of the four
-LIC360_API int lic360_sconv3x3_bf16x3_supported(int cin, int cout) { return sconv_ok(true, cin, cout, 3) ? 1 : 0; }
-LIC360_API long lic360_sconv3x3_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(cin, cout, 3); }
-LIC360_API int lic360_sconv3x3_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(stream, weight, packed, cin, cout, 3); }
+LIC360_API int lic360_sconv3x3_bf16x3_supported(int cin, int cout) { return sconv_ok(3, cin, cout, 3) ? 1 : 0; }
+LIC360_API long lic360_sconv3x3_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(3, cin, cout, 3); }
+LIC360_API int lic360_sconv3x3_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(3, stream, weight, packed, cin, cout, 3); }
 LIC360_API int lic360_sconv3x3_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                       int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    return sconv_launch<true>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+    return sconv_launch<3>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
 }
-LIC360_API int lic360_sconv1x1_bf16x3_supported(int cin, int cout) { return sconv_ok(true, cin, cout, 1) ? 1 : 0; }
-LIC360_API long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(cin, cout, 1); }
-LIC360_API int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(stream, weight, packed, cin, cout, 1); }
+LIC360_API int lic360_sconv1x1_bf16x3_supported(int cin, int cout) { return sconv_ok(3, cin, cout, 1) ? 1 : 0; }
+LIC360_API long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(3, cin, cout, 1); }
+LIC360_API int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(3, stream, weight, packed, cin, cout, 1); }
 LIC360_API int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                       int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
-    return sconv_launch<true>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+    return sconv_launch<3>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+}
+// the single-pass bf16 forms of the four: the argument lists of the split-bf16 ones, a pack of their own (hi planes only, 2 bytes per weight)
+LIC360_API int lic360_sconv3x3_bf16x1_supported(int cin, int cout) { return sconv_ok(1, cin, cout, 3) ? 1 : 0; }
+LIC360_API long lic360_sconv3x3_bf16x1_packed_bytes(int cin, int cout) { return b3_packed_bytes(1, cin, cout, 3); }
+LIC360_API int lic360_sconv3x3_bf16x1_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(1, stream, weight, packed, cin, cout, 3); }
+LIC360_API int lic360_sconv3x3_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
+    return sconv_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+}
+LIC360_API int lic360_sconv1x1_bf16x1_supported(int cin, int cout) { return sconv_ok(1, cin, cout, 1) ? 1 : 0; }
+LIC360_API long lic360_sconv1x1_bf16x1_packed_bytes(int cin, int cout) { return b3_packed_bytes(1, cin, cout, 1); }
+LIC360_API int lic360_sconv1x1_bf16x1_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(1, stream, weight, packed, cin, cout, 1); }
+LIC360_API int lic360_sconv1x1_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                      int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
+    return sconv_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
 }
 // the stride-2 forms of the fp32 pair (the analysis transform's down-sampling layers); they read the stride-1 packs
-LIC360_API int lic360_sconv3x3s2_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 3) ? 1 : 0; }
+LIC360_API int lic360_sconv3x3s2_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 3) ? 1 : 0; }
 LIC360_API int lic360_sconv3x3s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                  int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring) {
     return sconv_s2_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, oring, 3);
 }
-LIC360_API int lic360_sconv1x1s2_supported(int cin, int cout) { return sconv_ok(false, cin, cout, 1) ? 1 : 0; }
+LIC360_API int lic360_sconv1x1s2_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 1) ? 1 : 0; }
 LIC360_API int lic360_sconv1x1s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                  int n, int cin, int cout, int hp, int wp, int pad, int oring) {
     return sconv_s2_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, 0, oring, 1);

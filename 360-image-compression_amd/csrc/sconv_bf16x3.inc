@@ -25,6 +25,12 @@
 // This file holds only what the form does differently: the split, the weight pack kernel and b3_body's chunk loop.  S3Args, the LDS-DMA helpers,
 // the sphere rule, the loader's cell offsets (s3_cell_offsets), the epilogue (s3_epilogue), the kernel wrapper, the launch and the C entry
 // points are that file's, shared with the fp32 body.
+//
+// The single-pass form ("bf16x1", NT = 1 below; kernels k_sconv_b1).  The same body with the lo parts left out: every input value and every weight is
+// rounded ONCE to bf16 (nearest even) and each product is one MFMA, w_hi x_hi, accumulated in fp32 -- the fp32-accumulated convolution of the rounded
+// operands (about 2^-8 relative per operand); bias, PReLU and residual stay fp32 in the shared epilogue.  What NT = 1 changes: the conversion pass writes
+// hi cells only (split image: 4 planes, not 8), the pack holds hi planes only (2 bytes per weight), a K step loads three A operands (one 3 KiB block per
+// wave, one address register) and issues one MFMA per (row, row tile).  Loader, staging, chunk, counted waits, barriers and epilogue are the split form's.
 #include <type_traits>
 
 typedef __bf16 b3_bf8 __attribute__((ext_vector_type(8)));
@@ -34,8 +40,10 @@ typedef unsigned b3_u4 __attribute__((ext_vector_type(4)));
 #define B3_CK 32                                                            // input channels per chunk (= the K of one MFMA)
 constexpr int b3_ndma(int ncell) { return (B3_CK * ncell + 511) / 512; }   // DMA instructions per wave and chunk (fp32 staging pitch = halo cells)
 constexpr int b3_ps(int ncell) { return (ncell + 15) / 16 * 16; }          // split-image plane pitch in 16-byte cells
-// LDS floats of a body: two fp32 staging buffers + the split image (2 x 4 planes of PS 16-byte cells)
-constexpr int b3_lds(int tr, int ks) { return 2 * 8 * b3_ndma((tr + ks - 1) * (S3_T + ks - 1)) * 64 + 32 * b3_ps((tr + ks - 1) * (S3_T + ks - 1)); }
+// LDS floats of a body: two fp32 staging buffers + the split image (hi and lo, or at NT = 1 hi only: 4 planes of PS 16-byte cells each)
+constexpr int b3_lds(int tr, int ks, int nt = 3) {
+    return 2 * 8 * b3_ndma((tr + ks - 1) * (S3_T + ks - 1)) * 64 + (nt == 3 ? 32 : 16) * b3_ps((tr + ks - 1) * (S3_T + ks - 1));
+}
 
 __device__ __forceinline__ b3_u4 b3_split(const float (&v)[8], bool lo) {  // 8 values -> their bf16 hi (lo = false) or lo parts, packed
     b3_bf8 r;
@@ -50,12 +58,13 @@ __device__ __forceinline__ b3_u4 b3_split(const float (&v)[8], bool lo) {  // 8 
 // weights: [cout block of NQ * 48][it = (cg * ks + kw) * ks + kh < cin / 32 * ks * ks][mq][mt < 3][hl < 2][lane] x 8 bf16; lane l = 16 kq + i,
 // element j: the hi (hl = 0) or lo (hl = 1) part of W[co = 48 mq + 16 mt + i][ci = 32 cg + 8 kq + j][kh][kw] -- the A operand of the K step
 // (cg, kw, kh) for row tile mt; a wave reads its six operands of a step as one 6 KiB block.  One thread per 16-byte cell.
-__global__ void k_sconv_b3_pack(const float *__restrict__ w, b3_u4 *__restrict__ packed, int cin, int cout, int nq, int ks, long total) {
+// nhl = 1 (the single-pass form's pack): no hl index, hi parts only -- three operands, 3 KiB per wave and step.
+__global__ void k_sconv_b3_pack(const float *__restrict__ w, b3_u4 *__restrict__ packed, int cin, int cout, int nq, int ks, int nhl, long total) {
     const int nit = cin / B3_CK * ks * ks;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const int lane = (int)(idx & 63);
         long r = idx >> 6;
-        const int hl = (int)(r & 1); r >>= 1;
+        const int hl = (int)(r % nhl); r /= nhl;
         const int mt = (int)(r % 3); r /= 3;
         const int mq = (int)(r % nq); r /= nq;
         const int it = (int)(r % nit), blk = (int)(r / nit);
@@ -68,12 +77,16 @@ __global__ void k_sconv_b3_pack(const float *__restrict__ w, b3_u4 *__restrict__
     }
 }
 
-template <int NQ, int RW, int KS>                                           // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps
+// NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, NT bf16 MFMAs per product: 3 = the split form, 1 = single pass (hi parts only)
+template <int NQ, int RW, int KS, int NT = 3>
 __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int tx, int img) {
     constexpr int NR = 8 / NQ, TR = NR * RW, XR = TR + KS - 1, XC = S3_T + KS - 1, NCELL = XR * XC;
     constexpr int NDMA = b3_ndma(NCELL), BUF = 8 * NDMA * 64, PS = b3_ps(NCELL), NSTEP = KS * KS;
+    constexpr int NA = NT == 3 ? 6 : 3;                                     // A operands of a K step: (row tile, hi | lo), or the row tiles' hi parts
+    static_assert(NT == 3 || NT == 1, "split (hi + lo) or single pass (hi)");
+    static_assert(NDMA <= 63, "s_waitcnt vmcnt takes at most 63 on gfx950");
     float (*xs)[BUF] = (float (*)[BUF])lds;
-    b3_u4 *sp = (b3_u4 *)(lds + 2 * BUF);                                   // split image [hl][kq][PS]
+    b3_u4 *sp = (b3_u4 *)(lds + 2 * BUF);                                   // split image [hl][kq][PS] (NT = 1: [kq][PS])
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), mq = wave % NQ, nh = wave / NQ;
     const int tr0 = a.ring + ty * (NR * a.rw), tc0 = a.ringw + tx * S3_T;
@@ -90,22 +103,31 @@ __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int
         for (int i = 0; i < NDMA; ++i) s3_dma(voff[i], sb, lb + (unsigned)(i * 8 * 64 * 4));
     };
     const int nck = a.cin / B3_CK, niter = nck * NSTEP;
-    // A operands: six 16-byte loads per lane and K step (two address registers: the offset field stops at 4 KiB), one step ahead, waited for by
-    // counted vmcnt as in the fp32 body: the chunk's DMAs are issued behind the loads of its second step, so the wait at step 1 skips them
-    const char *wl = (const char *)a.w + (((long)blk * niter * NQ + mq) * 6 * 64 + lane) * 16;   // + it * NQ * 6 KiB per K step
-    auto load_a = [&](int it, b3_u4 (&A)[6]) __attribute__((always_inline)) {
-        const char *p = wl + (long)it * (NQ * 6 * 1024), *q = p + 3072;
-        asm volatile("global_load_dwordx4 %0, %6, off\n\tglobal_load_dwordx4 %1, %6, off offset:1024\n\tglobal_load_dwordx4 %2, %6, off offset:2048\n\t"
-                     "global_load_dwordx4 %3, %7, off\n\tglobal_load_dwordx4 %4, %7, off offset:1024\n\tglobal_load_dwordx4 %5, %7, off offset:2048"
-                     : "=&v"(A[0]), "=&v"(A[1]), "=&v"(A[2]), "=&v"(A[3]), "=&v"(A[4]), "=&v"(A[5]) : "v"(p), "v"(q));
+    // A operands: six 16-byte loads per lane and K step (two address registers: the offset field stops at 4 KiB; NT = 1: three loads, one register), one
+    // step ahead, waited for by counted vmcnt as in the fp32 body: the chunk's DMAs are issued behind the loads of its second step, so the wait at step 1 skips them
+    const char *wl = (const char *)a.w + (((long)blk * niter * NQ + mq) * NA * 64 + lane) * 16;   // + it * NQ * NA KiB per K step
+    auto load_a = [&](int it, b3_u4 (&A)[NA]) __attribute__((always_inline)) {
+        const char *p = wl + (long)it * (NQ * NA * 1024);
+        if constexpr (NA == 6) {
+            const char *q = p + 3072;
+            asm volatile("global_load_dwordx4 %0, %6, off\n\tglobal_load_dwordx4 %1, %6, off offset:1024\n\tglobal_load_dwordx4 %2, %6, off offset:2048\n\t"
+                         "global_load_dwordx4 %3, %7, off\n\tglobal_load_dwordx4 %4, %7, off offset:1024\n\tglobal_load_dwordx4 %5, %7, off offset:2048"
+                         : "=&v"(A[0]), "=&v"(A[1]), "=&v"(A[2]), "=&v"(A[3]), "=&v"(A[4]), "=&v"(A[5]) : "v"(p), "v"(q));
+        } else
+            asm volatile("global_load_dwordx4 %0, %3, off\n\tglobal_load_dwordx4 %1, %3, off offset:1024\n\tglobal_load_dwordx4 %2, %3, off offset:2048"
+                         : "=&v"(A[0]), "=&v"(A[1]), "=&v"(A[2]) : "v"(p));
     };
-#define B3_WAIT_A(N, A_) asm volatile("s_waitcnt vmcnt(%6)" : "+v"(A_[0]), "+v"(A_[1]), "+v"(A_[2]), "+v"(A_[3]), "+v"(A_[4]), "+v"(A_[5]) : "n"(N))
+#define B3_WAIT_A(N, A_)                                                                                                                                     \
+    do {                                                                                                                                                     \
+        if constexpr (NA == 6) asm volatile("s_waitcnt vmcnt(%6)" : "+v"(A_[0]), "+v"(A_[1]), "+v"(A_[2]), "+v"(A_[3]), "+v"(A_[4]), "+v"(A_[5]) : "n"(N)); \
+        else asm volatile("s_waitcnt vmcnt(%3)" : "+v"(A_[0]), "+v"(A_[1]), "+v"(A_[2]) : "n"(N));                                                           \
+    } while (0)
     s3_f4 acc[3][RW];
 #pragma unroll
     for (int m = 0; m < 3; ++m)
 #pragma unroll
         for (int r = 0; r < RW; ++r) acc[m][r] = (s3_f4){0.f, 0.f, 0.f, 0.f};
-    b3_u4 A[2][6];                                                          // operand ring: K step `it` in set it & 1
+    b3_u4 A[2][NA];                                                         // operand ring: K step `it` in set it & 1
     issue_dma(xb, 0);
     load_a(0, A[0]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -124,7 +146,7 @@ __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = xf[(8 * g + j) * NCELL + pos];
                 sp[g * PS + pos] = b3_split(v, false);
-                sp[(4 + g) * PS + pos] = b3_split(v, true);
+                if constexpr (NT == 3) sp[(4 + g) * PS + pos] = b3_split(v, true);
             }
         }
         __syncthreads();
@@ -140,13 +162,19 @@ __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int
             const b3_u4 *bl = sp + kq * PS + (nh * RW + kh) * XC + col + kw;
 #pragma unroll
             for (int r = 0; r < RW; ++r) {
-                const b3_bf8 bh = __builtin_bit_cast(b3_bf8, bl[r * XC]), blo = __builtin_bit_cast(b3_bf8, bl[4 * PS + r * XC]);
+                const b3_bf8 bh = __builtin_bit_cast(b3_bf8, bl[r * XC]);
+                if constexpr (NT == 3) {
+                    const b3_bf8 blo = __builtin_bit_cast(b3_bf8, bl[4 * PS + r * XC]);
 #pragma unroll
-                for (int m = 0; m < 3; ++m) {
-                    const b3_bf8 ah = __builtin_bit_cast(b3_bf8, A[sa][2 * m]), alo = __builtin_bit_cast(b3_bf8, A[sa][2 * m + 1]);
-                    acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bh, acc[m][r], 0, 0, 0);
-                    acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, blo, acc[m][r], 0, 0, 0);
-                    acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[m][r], 0, 0, 0);
+                    for (int m = 0; m < 3; ++m) {
+                        const b3_bf8 ah = __builtin_bit_cast(b3_bf8, A[sa][2 * m]), alo = __builtin_bit_cast(b3_bf8, A[sa][2 * m + 1]);
+                        acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bh, acc[m][r], 0, 0, 0);
+                        acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, blo, acc[m][r], 0, 0, 0);
+                        acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[m][r], 0, 0, 0);
+                    }
+                } else {
+#pragma unroll
+                    for (int m = 0; m < 3; ++m) acc[m][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b3_bf8, A[sa][m]), bh, acc[m][r], 0, 0, 0);
                 }
             }
         }

@@ -8,7 +8,8 @@ on this package's own kernel (csrc/conv3x3_kernels.hip, `lic360.sconv3x3`): fp32
 (no in-place SpherePad in front of it), bias + PReLU + the residual add in its epilogue, the SphereTrim behind it as its output window;
 the blocks' 1x1 layers ride on the same body (`lic360.sconv1x1`), and so do the down-sampling layers of the analysis transform: the 3x3
 stride-2 convolutions and the 1x1 stride-2 shortcuts of the hidden stages (`lic360.sconv3x3s2` / `sconv1x1s2`, the body's stride-2 forms).
-set_conv_precision(model, "bf16x3") moves the stride-1 fused layers to their split-bf16 forms (csrc/sconv_bf16x3.inc), per module.
+set_conv_precision(model, "bf16x3") moves the stride-1 fused layers to their split-bf16 forms (csrc/sconv_bf16x3.inc), "bf16x1" to their
+single-pass bf16 forms (operands rounded once, one MFMA per product), per module.
 The first stage's stride-2 layers (3 input channels: no 16-channel chunk, and bound by their output, not by MFMAs), convolutions off the fused
 shapes, small maps and every recording (training) pass are library work (torch -> MIOpen); native around them:
 sphere pad / trim / cut-edge / pixel-shuffle / importance map / quantiser kernels and the one-pass GDN (csrc/gdn_kernels.hip)."""
@@ -70,13 +71,16 @@ def _fusable_s2(conv, x, mod=None):
     return tiles >= FUSED_S2_MIN_WORKGROUPS and (tiles <= 256 or tiles >= FUSED_MIN_FILL * 256 * ((tiles + 255) // 256))
 
 
-CONV_PRECISIONS = ("fp32", "bf16x3")
+CONV_PRECISIONS = ("fp32", "bf16x3", "bf16x1")
 
 
 def set_conv_precision(module, precision):
-    """arithmetic of the fused convolutions of every block under `module` (module.modules()): "fp32" (the default: lic360.sconv3x3 / sconv1x1) or
-    "bf16x3" (their split-bf16 forms wherever those take the layer's shape, the fp32 kernel elsewhere; about 2^-16 relative error per product).
-    The stride-2 layers have no split-bf16 form: in "bf16x3" mode they stay on the fp32 stride-2 kernel (lic360.sconv3x3s2 / sconv1x1s2).
+    """arithmetic of the fused convolutions of every block under `module` (module.modules()): "fp32" (the default: lic360.sconv3x3 / sconv1x1),
+    "bf16x3" (their split-bf16 forms wherever those take the layer's shape, the fp32 kernel elsewhere; about 2^-16 relative error per product) or
+    "bf16x1" (their single-pass bf16 forms under the same shape rule: every input value and weight rounded once to bf16, one MFMA per product, fp32
+    accumulation, bias / PReLU / residual in fp32; about 2^-8 relative per operand -- reduced-precision inference: a latent from any mode codes
+    bit-exactly, only decoded pixels depend on the decoder's mode).
+    The stride-2 layers have no bf16 form: in "bf16x3" and "bf16x1" mode they stay on the fp32 stride-2 kernel (lic360.sconv3x3s2 / sconv1x1s2).
     A per-module setting, not a global: several copies of the networks may run side by side in different modes.  Library layers, small maps and
     recording passes are the same in either mode.  Returns `module`."""
     if precision not in CONV_PRECISIONS:
@@ -86,16 +90,19 @@ def set_conv_precision(module, precision):
     return module
 
 
-# (kernel size, precision) -> the names of the convolution, its pack and its shape predicate in lic360
+# (kernel size, precision) -> the names of the convolution, its pack and its shape predicate in lic360.  A bf16x1 row serves every shape its predicate takes:
+# each 3x3 and 1x1 shape of the transforms ran faster on it than on bf16x3 by more than the spread of the repeats (DESIGN §7c″, profiles/sconv_bf16x1_probe.json)
 _SCONV = {(3, "fp32"): ("sconv3x3", "sconv3x3_pack", "sconv3x3_supported"),
           (1, "fp32"): ("sconv1x1", "sconv1x1_pack", "sconv1x1_supported"),
           (3, "bf16x3"): ("sconv3x3_bf16x3", "sconv3x3_bf16x3_pack", "sconv3x3_bf16x3_supported"),
-          (1, "bf16x3"): ("sconv1x1_bf16x3", "sconv1x1_bf16x3_pack", "sconv1x1_bf16x3_supported")}
+          (1, "bf16x3"): ("sconv1x1_bf16x3", "sconv1x1_bf16x3_pack", "sconv1x1_bf16x3_supported"),
+          (3, "bf16x1"): ("sconv3x3_bf16x1", "sconv3x3_bf16x1_pack", "sconv3x3_bf16x1_supported"),
+          (1, "bf16x1"): ("sconv1x1_bf16x1", "sconv1x1_bf16x1_pack", "sconv1x1_bf16x1_supported")}
 
 
 def _sconv(mod, conv, x, slope, residual, out, **kw):
     """the fused convolution `conv` (3x3 or 1x1) of block `mod` in the block's precision: lic360.sconv3x3 / sconv1x1 (the fp32 call is exactly
-    theirs), or their bf16x3 forms when the block asks for them and they take the layer's shape.  The functions are lic360's attributes at
+    theirs), or their bf16x3 / bf16x1 forms when the block asks for them and they take the layer's shape.  The functions are lic360's attributes at
     call time.  The weight travels in the chosen form's operand order, repacked when the parameter was written (its version counter) or moved;
     each precision keeps its own pack, so switching modes never reuses the other's."""
     ks, precision = conv.kernel_size[0], getattr(mod, "_conv_precision", "fp32")
@@ -118,7 +125,7 @@ def _packed(conv, precision, pack):
 
 def _sconv_s2(conv, x, slope, residual, out):
     """the stride-2 convolution `conv` (3x3 or the 1x1 shortcut) of a 2-cell-apron map on lic360.sconv3x3s2 / sconv1x1s2: fp32 in every precision
-    mode of the block (there is no split-bf16 stride-2 form), on the stride-1 fp32 pack of the weight"""
+    mode of the block (there is no bf16 stride-2 form), on the stride-1 fp32 pack of the weight"""
     ks = conv.kernel_size[0]
     fn, pack, _ = _SCONV[ks, "fp32"]
     return getattr(lic360, fn + "s2")(x, _packed(conv, "fp32", pack), conv.bias, slope, residual, out, pad=2, oring=2)

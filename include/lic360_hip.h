@@ -367,6 +367,22 @@ long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout);
 int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout);
 int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                            int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle);
+/* ---- the single-pass bf16 ("bf16x1") form of the same four (csrc/sconv_bf16x3.inc with the lo parts left out; kernels k_sconv_b1), opt-in: the same
+ * operation, argument lists and shape predicate as the bf16x3 entry points.  Every input value and every weight is rounded ONCE to bf16 (nearest even);
+ * each product is one v_mfma_f32_16x16x32_bf16 with fp32 accumulation; bias, PReLU and residual are applied in fp32, unrounded: the result is the
+ * fp32-accumulated convolution of the rounded operands (about 2^-8 relative per operand, this kernel's own summation order).  Inference only; NaN,
+ * infinity and values within 2^-8 of FLT_MAX are outside the contract.  packed = lic360_sconv{3x3,1x1}_bf16x1_pack (packed_bytes = cout cin ks^2 2
+ * bytes, 16-byte aligned: the hi bf16 planes in the waves' operand order) -- neither the fp32 nor the bf16x3 pack. */
+int lic360_sconv3x3_bf16x1_supported(int cin, int cout);
+long lic360_sconv3x3_bf16x1_packed_bytes(int cin, int cout);
+int lic360_sconv3x3_bf16x1_pack(void *stream, const float *weight, void *packed, int cin, int cout);
+int lic360_sconv3x3_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                           int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int crop, int shuffle);
+int lic360_sconv1x1_bf16x1_supported(int cin, int cout);
+long lic360_sconv1x1_bf16x1_packed_bytes(int cin, int cout);
+int lic360_sconv1x1_bf16x1_pack(void *stream, const float *weight, void *packed, int cin, int cout);
+int lic360_sconv1x1_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                           int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle);
 /* ---- the stride-2 (down-sampling) forms of the two, fp32, on the same kernel body with a stride parameter (csrc/conv3x3_kernels.hip).
  * lic360_sconv3x3s2 replaces the in-place SpherePad(2) + nn.Conv2d(cin, c, 3, 2, 3) + nn.PReLU + SphereTrim of test/model_zoo.py:64-106
  * (ResidualBlockDown.conv1, SphereConv2); lic360_sconv1x1s2 replaces nn.Conv2d(cin, c, 1, 2, 2) + the `t + y` add of ResidualBlockDown.short_cut.

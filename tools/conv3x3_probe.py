@@ -2,6 +2,8 @@
 correctness (max |diff| against conv2d over the sphere-padded map, fp32) and time per launch -- the library form timed WITH the launches the
 fused kernel absorbs (in-place apron refresh, PReLU, trim) and without.  VERDICT r4 next #2.
 --precision bf16x3: "ours" is the split-bf16 form (lic360_sconv3x3_bf16x3 / sconv1x1_bf16x3), timed in the same run next to the fp32 kernel.
+--precision bf16x1: "ours" is the single-pass bf16 form (lic360_sconv3x3_bf16x1 / sconv1x1_bf16x1); fp32, bf16x3 and bf16x1 launches alternate in the same
+run (median, min, max of 5 repeats of 10 launches), and --json FILE keeps that table.
 --s2: the stride-2 forms instead (lic360_sconv3x3s2 / sconv1x1s2) on the analysis transform's three down-sampling shapes and two shortcuts, batches
 1, 2, 4, 8, 32, each next to the library form of the same work (in-place SpherePad + conv2d(stride 2) + PReLU; shortcut conv2d + add + trim): median
 of alternating repeats with the spread, and the smallest tile count from which the native form is not slower on any shape; --json FILE keeps the table."""
@@ -14,11 +16,33 @@ import lic360
 
 dev = "cuda:0"
 ap = argparse.ArgumentParser()
-ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32")
+ap.add_argument("--precision", choices=("fp32", "bf16x3", "bf16x1"), default="fp32")
 ap.add_argument("--s2", action="store_true")
 ap.add_argument("--json", default=None)
 ARGS = ap.parse_args()
-B3 = ARGS.precision == "bf16x3"
+B3 = ARGS.precision != "fp32"                                             # a bf16 form is "ours", timed alternating with the forms before it in FORMS
+FORMS = ("fp32", "bf16x3", "bf16x1")[:("fp32", "bf16x3", "bf16x1").index(ARGS.precision) + 1]
+AB_ROWS = []
+
+
+def alternating(kernel, what, fns):
+    """5 repeats of 10 launches of every form in turn: median, min, max ms per launch; one line (--precision bf16x3: the line that mode always printed) and, for
+    --precision bf16x1, one row of the --json table"""
+    t = {f: [] for f in FORMS}
+    for _ in range(5):
+        for f in FORMS:
+            t[f].append(timed(fns[f]))
+    row = dict(layer=what)
+    for f in FORMS:
+        row.update({f + "_ms": sorted(t[f])[2], f + "_min": min(t[f]), f + "_max": max(t[f])})
+    if ARGS.precision == "bf16x3":
+        print("    bf16x3 vs fp32 %s, 5 alternating repeats: fp32 %.3f ms (min %.3f max %.3f), bf16x3 %.3f ms (min %.3f max %.3f), speedup %.2f" % (
+            kernel, row["fp32_ms"], row["fp32_min"], row["fp32_max"], row["bf16x3_ms"], row["bf16x3_min"], row["bf16x3_max"], row["fp32_ms"] / row["bf16x3_ms"]), flush=True)
+        return
+    AB_ROWS.append(row)
+    print("    %s, 5 alternating repeats: %s, speedup over fp32 %s" % (
+        what, ", ".join("%s %.3f ms (min %.3f max %.3f)" % (f, row[f + "_ms"], row[f + "_min"], row[f + "_max"]) for f in FORMS),
+        " / ".join("%.2f" % (row["fp32_ms"] / row[f + "_ms"]) for f in FORMS[1:])), flush=True)
 
 
 def timed(fn, reps=10):
@@ -101,7 +125,8 @@ for (n, cin, cout, hp, wp, ring, crop) in shapes:
     w = torch.randn(cout, cin, 3, 3, device=dev) * 0.05
     b, sl = torch.randn(cout, device=dev), torch.rand(cout, device=dev) * 0.5
     res = torch.randn(n, cout, hp, wp, device=dev) if crop == 0 else None
-    pk, pk3 = lic360.sconv3x3_pack(w), (lic360.sconv3x3_bf16x3_pack(w) if B3 else None)
+    pk = lic360.sconv3x3_pack(w)
+    packs = {f: getattr(lic360, "sconv3x3_%s_pack" % f)(w) for f in FORMS[1:]}
     out = torch.zeros(n, cout, hp - 2 * crop, wp - 2 * crop, device=dev)
     pad_op, trim_op = lic360.SpherePadOp(2, True, 0, False), lic360.SphereTrimOp(ring, 0, False)
 
@@ -118,10 +143,12 @@ for (n, cin, cout, hp, wp, ring, crop) in shapes:
     def fp32():
         return lic360.sconv3x3(x, pk, b, sl, res, out, pad=2, sphere=True, ring=ring, crop=crop, ring_w=max(ring, 2 - 2 * crop))
 
-    def ours():
-        if not B3:
-            return fp32()
-        return lic360.sconv3x3_bf16x3(x, pk3, b, sl, res, out, pad=2, sphere=True, ring=ring, crop=crop, ring_w=max(ring, 2 - 2 * crop))
+    def form(f):
+        if f == "fp32":
+            return fp32
+        return lambda: getattr(lic360, "sconv3x3_" + f)(x, packs[f], b, sl, res, out, pad=2, sphere=True, ring=ring, crop=crop, ring_w=max(ring, 2 - 2 * crop))
+
+    ours = form(ARGS.precision)
 
     want = lib(True)                                                    # (refreshes x's apron in place: the fused kernel ignores it anyway)
     got = ours()
@@ -140,12 +167,7 @@ for (n, cin, cout, hp, wp, ring, crop) in shapes:
               cin, cout, hp, wp, n, ring, crop, err, t_conv, fl_lib / t_conv / 1e9, t_full, t_ours, fl_win / t_ours / 1e9, hp - 2 * ring, wp - 2 * rw_,
               fl_lib / t_ours / 1e9, t_ours / t_full), flush=True)
     if B3:
-        t32, t3 = [], []
-        for _ in range(5):
-            t32.append(timed(fp32))
-            t3.append(timed(ours))
-        print("    bf16x3 vs fp32 sconv3x3, 5 alternating repeats: fp32 %.3f ms (min %.3f max %.3f), bf16x3 %.3f ms (min %.3f max %.3f), speedup %.2f" % (
-            sorted(t32)[2], min(t32), max(t32), sorted(t3)[2], min(t3), max(t3), sorted(t32)[2] / sorted(t3)[2]), flush=True)
+        alternating("sconv3x3", "3x3 %d->%d @%dx%d x%d ring %d crop %d" % (cin, cout, hp, wp, n, ring, crop), {f: form(f) for f in FORMS})
 
 # ---- the 1x1 layers of ResidualBlock on the same kernel body, against the library GEMM (+ the elementwise launch each one absorbs)
 for (n, cin, cout, hp, wp, what) in [(8, 192, 96, 132, 260, "prelu"), (8, 96, 192, 132, 260, "add"), (8, 192, 192, 132, 260, "prelu")]:
@@ -155,13 +177,15 @@ for (n, cin, cout, hp, wp, what) in [(8, 192, 96, 132, 260, "prelu"), (8, 96, 19
     b, sl = torch.randn(cout, device=dev), torch.rand(cout, device=dev) * 0.5
     res = torch.randn(n, cout, hp, wp, device=dev)
     pk = lic360.sconv1x1_pack(w)
-    conv1, pk1 = lic360.sconv1x1, pk
-    if B3:
-        conv1, pk1 = lic360.sconv1x1_bf16x3, lic360.sconv1x1_bf16x3_pack(w)
+    packs = dict({f: getattr(lic360, "sconv1x1_%s_pack" % f)(w) for f in FORMS[1:]}, fp32=pk)
     out = torch.zeros(n, cout, hp, wp, device=dev)
     lib = (lambda: F.prelu(F.conv2d(x, w, b), sl)) if what == "prelu" else (lambda: F.conv2d(x, w, b) + res)
-    ours = (lambda: conv1(x, pk1, b, sl, None, out, ring=2)) if what == "prelu" else (lambda: conv1(x, pk1, b, None, res, out, ring=2))
-    fp32 = (lambda: lic360.sconv1x1(x, pk, b, sl, None, out, ring=2)) if what == "prelu" else (lambda: lic360.sconv1x1(x, pk, b, None, res, out, ring=2))
+
+    def form(f):
+        conv1 = getattr(lic360, "sconv1x1" + ("" if f == "fp32" else "_" + f))
+        return (lambda: conv1(x, packs[f], b, sl, None, out, ring=2)) if what == "prelu" else (lambda: conv1(x, packs[f], b, None, res, out, ring=2))
+
+    ours = form(ARGS.precision)
     win = (slice(None), slice(None), slice(2, hp - 2), slice(2, wp - 2))
     err = (ours()[win] - lib()[win]).abs().max().item()
     t_conv, t_lib, t_ours = timed(lambda: F.conv2d(x, w, b)), timed(lib), timed(ours)
@@ -169,9 +193,9 @@ for (n, cin, cout, hp, wp, what) in [(8, 192, 96, 132, 260, "prelu"), (8, 96, 19
     print("1x1 %d->%d @%dx%d x%d + %s: max|diff| %.2e | library conv alone %.3f ms, with the %s %.3f ms | sconv1x1 %.3f ms (%.1f TF on its window) | ours / library = %.2f" % (
         cin, cout, hp, wp, n, what, err, t_conv, what, t_lib, t_ours, fl / t_ours / 1e9, t_ours / t_lib), flush=True)
     if B3:
-        t32, t3 = [], []
-        for _ in range(5):
-            t32.append(timed(fp32))
-            t3.append(timed(ours))
-        print("    bf16x3 vs fp32 sconv1x1, 5 alternating repeats: fp32 %.3f ms (min %.3f max %.3f), bf16x3 %.3f ms (min %.3f max %.3f), speedup %.2f" % (
-            sorted(t32)[2], min(t32), max(t32), sorted(t3)[2], min(t3), max(t3), sorted(t32)[2] / sorted(t3)[2]), flush=True)
+        alternating("sconv1x1", "1x1 %d->%d @%dx%d x%d + %s" % (cin, cout, hp, wp, n, what), {f: form(f) for f in FORMS})
+
+if ARGS.precision == "bf16x1" and ARGS.json:
+    with open(ARGS.json, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), forms=list(FORMS),
+                       repeats="median of 5 repeats of 10 launches, each after 3 warm-up launches, the forms alternating within a repeat; ms per launch", rows=AB_ROWS), f, indent=1)

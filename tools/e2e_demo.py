@@ -33,7 +33,7 @@ def main():
     ap.add_argument("--images", nargs="*", default=[])
     ap.add_argument("--checkpoint")
     ap.add_argument("--imp-checkpoint")
-    ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32", help="arithmetic of the transforms' fused convolutions")
+    ap.add_argument("--precision", choices=("fp32", "bf16x3", "bf16x1"), default="fp32", help="arithmetic of the transforms' fused convolutions")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     import lic360_container as box

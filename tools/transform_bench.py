@@ -1,8 +1,8 @@
 """Analysis / synthesis transforms (lic360_models.py) at the reference's width (192 channels, 512x1024 ERPs): ms per image and nominal
 TFLOP/s (library convolutions through MIOpen + this package's sphere / shuffle / quantiser / GDN kernels), and the one-pass GDN against
 its four-kernel torch form.  Seeded random weights.  Writes one JSON document to stdout.
---precision {fp32,bf16x3}: the mode of the fused convolutions (lic360_models.set_conv_precision) for every row; --ab: only the analysis and
-synthesis transforms, ms per image in both modes, alternating in one run (one JSON line per repeat and a summary)."""
+--precision {fp32,bf16x3,bf16x1}: the mode of the fused convolutions (lic360_models.set_conv_precision) for every row; --ab: only the analysis and
+synthesis transforms, ms per image in all three modes, alternating in one run (one JSON line per repeat and a summary)."""
 import json
 import os
 import sys
@@ -65,9 +65,9 @@ def measure(batch=8, device=0, reps=3, precision="fp32"):
             ww, bb, sl = torch.randn((c, c, 3, 3), device=dev) * 0.05, torch.randn((c,), device=dev), torch.rand((c,), device=dev) * 0.5
             res, oo, pk = torch.randn_like(xx), torch.zeros_like(xx), lic360.sconv3x3_pack(ww)
             pad_op, trim_op = lic360.SpherePadOp(2, True, device, False), lic360.SphereTrimOp(2, device, False)
-            if precision == "bf16x3":
-                pk3 = lic360.sconv3x3_bf16x3_pack(ww)
-                t_o = timed(lambda: lic360.sconv3x3_bf16x3(xx, pk3, bb, sl, res, oo, pad=2, sphere=True, ring=2), 5)
+            if precision != "fp32":
+                conv3, pk3 = getattr(lic360, "sconv3x3_" + precision), getattr(lic360, "sconv3x3_%s_pack" % precision)(ww)
+                t_o = timed(lambda: conv3(xx, pk3, bb, sl, res, oo, pad=2, sphere=True, ring=2), 5)
             else:
                 t_o = timed(lambda: lic360.sconv3x3(xx, pk, bb, sl, res, oo, pad=2, sphere=True, ring=2), 5)
             t_c = timed(lambda: F.conv2d(xx, ww, bb, padding=1), 5)
@@ -198,17 +198,17 @@ def whole_codec_streams(enc, dec, device, batch=48, reps=2, nstreams=2):
 
 
 def ab_transforms(batch=8, device=0, reps=3, repeats=5):
-    """analysis and synthesis ms per image, fp32 and bf16x3 modes alternating on the same networks and inputs"""
+    """analysis and synthesis ms per image, the fp32, bf16x3 and bf16x1 modes alternating on the same networks and inputs"""
     import lic360_models as lm
     dev = "cuda:%d" % device
     torch.manual_seed(0)
     enc, dec = lm.CMP_Encoder(gpu_id=device).to(dev).eval(), lm.CMP_Decoder(gpu_id=device).to(dev).eval()
-    t = {(p, k): [] for p in ("fp32", "bf16x3") for k in ("analysis", "synthesis")}
+    t = {(p, k): [] for p in lm.CONV_PRECISIONS for k in ("analysis", "synthesis")}
     with torch.no_grad():
         img = torch.rand((batch, 3, 512, 1024), device=dev)
         code, mask, _ = enc(img)
         for i in range(repeats):
-            for p in ("fp32", "bf16x3"):
+            for p in lm.CONV_PRECISIONS:
                 lm.set_conv_precision(enc, p)
                 lm.set_conv_precision(dec, p)
                 row = {"repeat": i, "precision": p, "batch": batch}
@@ -256,8 +256,8 @@ if __name__ == "__main__":
         ab_transforms()
         sys.exit(0)
     precision = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp32"
-    if precision not in ("fp32", "bf16x3"):
-        sys.exit("--precision must be fp32 or bf16x3")
+    if precision not in ("fp32", "bf16x3", "bf16x1"):
+        sys.exit("--precision must be fp32, bf16x3 or bf16x1")
     if len(sys.argv) > 1 and sys.argv[1] == "streams":                      # the whole codec as N sub-batches on N streams (experiment: N = 2, 3)
         import lic360_models as lm
         torch.manual_seed(0)
