@@ -98,12 +98,9 @@ def decode_main(data, mask, layers, G):
     return (b[0:1] + np.float32(3.5) * mask).astype(np.float32)
 
 
-def encode_imp(levels, layers, nsym=49):
-    """D3 ImpEntEncoderFast.forward: levels [1,1,h,w] in {0..48} -> bytes."""
+def _imp_coder(y, levels, nsym, idx, pidx):
+    """the coder half of D3: the net's output y [1,nsym,h,w] and the levels [1,1,h,w] of ONE image -> bytes"""
     _, _, H, W = levels.shape
-    idx, pidx = orc.code_contex(H, W)
-    x = orc.scale(levels, -1.0, np.float32(2.0 / (nsym - 2)))
-    y = net_ec(x, layers, 1)
     enc = orc.Encoder()
     z = np.zeros(nsym * H * W, np.float32)
     lab = np.zeros(H * W, np.float32)
@@ -113,6 +110,25 @@ def encode_imp(levels, layers, nsym=49):
         orc.tile_extract(levels, lab, 1, True, idx, pidx, p)
         enc.encode(tab.astype(np.int32), nsym, lab[:tn].astype(np.int32), None, tn)
     return enc.finish()
+
+
+def encode_imp(levels, layers, nsym=49):
+    """D3 ImpEntEncoderFast.forward: levels [1,1,h,w] in {0..48} -> bytes."""
+    _, _, H, W = levels.shape
+    idx, pidx = orc.code_contex(H, W)
+    x = orc.scale(levels, -1.0, np.float32(2.0 / (nsym - 2)))
+    return _imp_coder(net_ec(x, layers, 1), levels, nsym, idx, pidx)
+
+
+def encode_imp_batch(levels, layers, nsym=49):
+    """encode_imp of every image of levels [b,1,h,w] -> list of bytes: the net once over the whole batch (images are independent, and a call
+    of the oracle's convolution costs the same for one small map as for forty), the coder per image.  Pinned to encode_imp, image by image,
+    by tests/test_cconv144_cases_cpu.py."""
+    B, _, H, W = levels.shape
+    idx, pidx = orc.code_contex(H, W)
+    levels = np.ascontiguousarray(levels, np.float32)
+    y = net_ec(orc.scale(levels, -1.0, np.float32(2.0 / (nsym - 2))), layers, 1)
+    return [_imp_coder(np.ascontiguousarray(y[i:i + 1]), levels[i:i + 1], nsym, idx, pidx) for i in range(B)]
 
 
 def decode_imp(data, layers, H, W, nsym=49):

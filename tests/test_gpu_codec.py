@@ -168,6 +168,84 @@ def test_fused_importance_codec_matches_oracle(cpg, nsym, H, W, B, seed):
     assert np.array_equal(rc.decode_imp(streams[0], layers, H, W, nsym), levels[0:1])
 
 
+def _imp_levels(rng, B, H, W, nsym):
+    """levels over the full range, image 1 constant 0 and the last image constant nsym - 1"""
+    levels = rng.integers(0, nsym, (B, 1, H, W)).astype(np.float32)
+    levels[1], levels[B - 1] = 0.0, nsym - 1.0
+    assert levels.min() == 0 and levels.max() == nsym - 1
+    return levels
+
+
+def _imp_batch_roundtrip(fc, levels, layers, nsym):
+    """encode == the oracle's bytes image by image, decode == levels, and the oracle decodes the first and the last image's bytes"""
+    B, _, H, W = levels.shape
+    streams = fc.encode(dev(levels))
+    ref = rc.encode_imp_batch(levels, layers, nsym)
+    for i in range(B):
+        assert streams[i] == ref[i], "image %d of %d" % (i, B)
+    fc.levels_out.fill_(-3.0)
+    bad = np.argwhere(fc.decode(streams).cpu().numpy() != levels)
+    assert len(bad) == 0, "%d cells differ, first (image, _, row, column) = %s" % (len(bad), bad[0])
+    for i in (0, B - 1):
+        assert np.array_equal(rc.decode_imp(streams[i], layers, H, W, nsym), levels[i:i + 1]), "image %d" % i
+    return streams
+
+
+# The importance-map codec at batches where the 144-channel kernel's decode-order tasks take several output tiles and its workgroups take
+# several tasks (tests/cconv144_cases.py restates the launch geometry; tests/test_gpu_cconv144_batch.py holds the kernel itself)
+def test_fused_importance_codec_batch40_with_mask():
+    """hidden_channels = 144, 40 maps of 4 x 6: every decode-order hidden layer runs with output-tile groups [2, 2, 2, 2, 1].  Bytes, decode, and
+    the masked decode into a garbage-filled mask buffer: exactly Dtow(2)(Imp2mask(levels)) and the same levels."""
+    import cconv144_cases as cc
+    import oracle as orc
+    from lic360_fused import FusedImpCodec
+    B, H, W, nsym, seed = 40, 4, 6, 49, 34
+    assert all(cc.dc_geometry(B, H, W, 144, s).groups == (2, 2, 2, 2, 1) for s in range(H + W - 1))
+    rng = np.random.default_rng(seed)
+    layers = rc.make_imp_params(4000 + seed, 144, nsym)
+    levels = _imp_levels(rng, B, H, W, nsym)
+    fc = FusedImpCodec(H, W, max_batch=B, hidden_channels=144, nsym=nsym)
+    fc.load_layers(layers)
+    _imp_batch_roundtrip(fc, levels, layers, nsym)
+    mbuf = torch.full((B, 12, 2 * H, 2 * W), 7.0, dtype=torch.float32, device="cuda:0")
+    fc.levels_out.fill_(-3.0)
+    fc.decode_masked_async(B, mbuf, mask_channels=48, stride=2)
+    torch.cuda.synchronize()
+    assert int(fc.err[:B].abs().sum().item()) == 0
+    assert np.array_equal(fc.levels_out[:B].cpu().numpy(), levels)
+    assert np.array_equal(mbuf.cpu().numpy(), orc.dtow(orc.imp2mask(levels, 48, 48), 2, True))
+
+
+def test_fused_importance_codec_batch72_then_a_smaller_batch():
+    """hidden_channels = 144, 72 maps of 3 x 4 in a codec of 80: hidden layers with groups [4, 4, 1] (the production split), the last layer with
+    288 tasks on 256 workgroups.  Then 5 other maps on the same codec: a smaller batch after a larger one reads no stale state."""
+    import cconv144_cases as cc
+    from lic360_fused import FusedImpCodec
+    B, H, W, nsym, seed = 72, 3, 4, 49, 35
+    for s in range(H + W - 1):
+        assert cc.dc_geometry(B, H, W, 144, s).groups == (4, 4, 1)
+        g = cc.dc_geometry(B, H, W, nsym, s)
+        assert g.og == 1 and g.tasks == 288 and g.grid == 256
+    rng = np.random.default_rng(seed)
+    layers = rc.make_imp_params(4000 + seed, 144, nsym)
+    fc = FusedImpCodec(H, W, max_batch=80, hidden_channels=144, nsym=nsym)
+    fc.load_layers(layers)
+    big = _imp_batch_roundtrip(fc, _imp_levels(rng, B, H, W, nsym), layers, nsym)
+    small = _imp_batch_roundtrip(fc, _imp_levels(rng, 5, H, W, nsym), layers, nsym)
+    assert small != big[:5]
+
+
+def test_fused_importance_codec_generic_kernels_batch40():
+    """hidden_channels = 8: the generic-kernel path of the importance codec at a real batch size"""
+    from lic360_fused import FusedImpCodec
+    B, H, W, nsym, seed = 40, 8, 12, 49, 36
+    rng = np.random.default_rng(seed)
+    layers = rc.make_imp_params(4000 + seed, 8, nsym)
+    fc = FusedImpCodec(H, W, max_batch=B, hidden_channels=8, nsym=nsym)
+    fc.load_layers(layers)
+    _imp_batch_roundtrip(fc, _imp_levels(rng, B, H, W, nsym), layers, nsym)
+
+
 @pytest.mark.parametrize("kind", ["latent", "importance"])
 def test_fused_codec_needs_every_layer(kind):
     """Both codecs' weight store: encode and decode before all 12 layers have weights raise "has no weights"; set_layer rejects a layer

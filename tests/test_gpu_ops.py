@@ -770,17 +770,7 @@ def test_cconv16_ec_bit_exact(lic, case):
 
 
 # ------------------------------------------------------------------ importance-map net layers (one group, C = 144) on 16x16x4 MFMAs
-def _i144_setup(lic, rng, nout, act):
-    import ctypes as C
-    w, b, a = conv_params(rng, None, nout, 144, act=act)
-    L = lic._lib
-    plan = C.c_void_p(0)
-    assert L.lic360_conv_plan_create(144, 1, nout, 5, 6, C.byref(plan)) == 0
-    assert L.lic360_conv144_supported(plan) == 1
-    packed = torch.empty(L.lic360_conv144_packed_floats(plan), dtype=torch.float32, device="cuda:0")
-    wd = dev(w)
-    assert L.lic360_conv144_pack(lic._stream(0), plan, lic._p(wd), lic._p(packed)) == 0, L.lic360_last_error()
-    return w, b, a, plan, packed
+from cconv144_cases import i144_setup as _i144_setup        # (shared with tests/test_gpu_cconv144_batch.py)
 
 
 @pytest.mark.parametrize("case", [(2, 7, 21, 144, True, 2), (1, 4, 6, 49, False, 0), (3, 32, 64, 144, True, 2), (1, 1, 1, 20, True, 0), (1, 33, 17, 49, False, 0)],
