@@ -14,10 +14,11 @@
 //   * wave c of a workgroup (8 waves) owns lanes l = c (mod 8): 16 chains, the top four tree levels (+64, +32, +16, +8) in
 //     registers; the last three levels cross the waves through LDS;
 //   * a workgroup keeps the zero-haloed x tile of ALL 144 input channels of NT position tiles in LDS (LDS-DMA once per task)
-//     and sweeps the output-channel tiles over it; weights go straight to registers, prefetched four blocks ahead;
+//     and sweeps the output-channel tiles over it; weights go straight to registers, prefetched 512 pipe cycles ahead, the x operands of
+//     a block are read from LDS two blocks (NT = 1: four) ahead of its MFMAs, what the epilogue reads from memory a whole tile ahead;
 //   * EC layout: zero-haloed NCHW planes, a task = NT consecutive rows x 16 columns of one map;
 //     DC layout: zero-padded diagonal-major planes (cell (th, tw) at row th+tw+4, column th+2), a task = the NT x 16
-//     positions th0.. of anti-diagonal s of one map: what decode plane s touches.
+//     positions th0.. of anti-diagonal s of one map: what decode plane s touches (NT = 1 where the plane's rows fit 16, else 2).
 #include "common.h"
 #include "conv_plan.h"
 #include "cconv_tree.h"
@@ -148,7 +149,18 @@ __device__ __forceinline__ unsigned i144_lds_addr(const float *p) {
 }
 __device__ __forceinline__ f32x4 i144_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
-#define I144_PFG 2                              // weight prefetch depth (groups of four blocks)
+// Look-ahead of the block loop, both stated for NT = 2 and doubled for NT = 1: a block is NT MFMAs = 32 NT cycles of the SIMD's matrix pipe, and what
+// a look-ahead has to cover is a latency in cycles (an L2 hit 180-225, a ds_read ~50 from issue to use plus the queue of eight waves), not a block count.
+#define I144_PFG 2                              // A operands (weights): groups of four blocks fetched ahead = 512 pipe cycles
+#ifndef I144_BD
+#define I144_BD 2                               // B operands (x tile): blocks whose ds_read is issued ahead of the block's MFMAs = 128 pipe cycles
+#endif
+// The B addresses do not change from one output tile to the next, so the compiler keeps all of a wave's 74-75 in registers: with 64 NT accumulator
+// registers, the two rings and the DMA offsets that is the whole budget of 256 at NT = 2.  Every I144_BAS-th block therefore takes its address from a
+// copy of `kq` that is opaque per output tile (an empty asm), which keeps its three selects inside the loop, where they run beside the MFMAs.
+#ifndef I144_BAS
+#define I144_BAS 5
+#endif
 
 template <int HIDDEN, bool DC, int NT, int WAVE>
 __device__ __forceinline__ void i144_body(const I144Args &a, float *xs, float *comb, const int tid, const int lane) {
@@ -193,23 +205,53 @@ __device__ __forceinline__ void i144_body(const I144Args &a, float *xs, float *c
             constexpr int m = decltype(mm)::value;
             if constexpr ((WAVE + 8 * m) * 64 < XQ) i144_dma_x4(xt + soff[m], lds_x + (unsigned)((WAVE + 8 * m) * 1024));
         });
-        I144_WAIT0();
-        __syncthreads();
-        for (int ot = ot_lo; ot < ot_hi; ++ot) {
-            const float *wot = a.packed + ((long)ot * 8 + WAVE) * (T::NG * 256) + lane * 4;
-            f32x4 acc[NT][16];
-            // ---- the 16 chains of this wave, quad by quad; block index b runs over (a = lane slot, q) in order; the A operands of blocks
-            // 4 g .. 4 g + 3 are one f32x4 per lane, fetched I144_PFG groups ahead
-            constexpr int NB = T::nblocks(WAVE), NGW = (NB + 3) / 4, RING = I144_PFG + 1;
-            f32x4 aring[RING];
-            static_for<(I144_PFG < NGW ? I144_PFG : NGW)>([&](auto gg) {
+        // the A operands of blocks 4 g .. 4 g + 3 are one f32x4 per lane, fetched PFG groups ahead through a ring; the head of an output tile's
+        // stream is fetched before the tile starts: beside the x-tile DMA for a task's first tile, over the previous tile's tree and epilogue after it
+        constexpr int NB = T::nblocks(WAVE), NGW = (NB + 3) / 4, PFG = I144_PFG * 2 / NT, RING = PFG + 1;
+        f32x4 aring[RING];
+        const float *wot = a.packed + ((long)ot_lo * 8 + WAVE) * (T::NG * 256) + lane * 4;
+        auto a_head = [&]() {
+            static_for<(PFG < NGW ? PFG : NGW)>([&](auto gg) {
                 constexpr int g = decltype(gg)::value;
                 aring[g % RING] = *(const f32x4 *)(wot + g * 256);
             });
-            static_for<NB>([&](auto bb) {
+        };
+        a_head();
+        I144_WAIT0();
+        __syncthreads();
+        for (int ot = ot_lo; ot < ot_hi; ++ot) {
+            // ---- this thread's cell of the output tile (tile t, row v of the MFMA's four, lane: NT * 256 cells, at most one per thread) and what its
+            // epilogue reads from memory: fetched here, a block loop ahead of its use, not behind the tile's last barrier where every wave would wait for it
+            static_assert(NT * 256 <= I144_THREADS, "one epilogue cell per thread");
+            constexpr bool EPI = WAVE * 64 < NT * 256;
+            const int e_t = WAVE >> 2, e_v = WAVE & 3, e_o = ot * 16 + 4 * kq + e_v;
+            bool e_ok = EPI && e_o < a.nout;
+            long e_oi;
+            if constexpr (DC) {
+                const int th = th0 + 16 * e_t + j;
+                e_ok = e_ok && th >= a.th_lo && th <= a.th_hi;
+                e_oi = (long)n * a.osample + (long)e_o * a.oplane + (long)(a.s + I144_R0) * a.opitch + th + I144_C0;
+            } else {
+                const int y = r0 + e_t, xx = c0 + j;
+                e_ok = e_ok && y < a.H && xx < a.W;
+                e_oi = (long)n * a.osample + (long)e_o * a.oplane + (long)(y + a.ooff) * a.opitch + xx + a.ooff;
+            }
+            float e_bias = 0.f, e_act = 0.f, e_res = 0.f;
+            if (e_ok) {
+                e_bias = a.bias[e_o];
+                if (a.act) e_act = a.act[e_o];
+                if (a.residual) e_res = a.residual[e_oi];
+            }
+            f32x4 acc[NT][16];
+            // ---- the 16 chains of this wave, quad by quad; block index b runs over (a = lane slot, q) in order.  The B operands of block b + BD
+            // are read from LDS before the MFMAs of block b are issued, so that an MFMA waits for a read that is BD blocks old (a counted lgkmcnt:
+            // LDS reads return in order) and not for one it has just issued
+            constexpr int BD = I144_BD * 2 / NT, BRING = BD + 1;
+            float bring[BRING][NT];
+            int kq_ot = kq;
+            asm volatile("" : "+v"(kq_ot));
+            auto b_read = [&](auto bb) {
                 constexpr int b = decltype(bb)::value, aa = T::blk_a(WAVE, b), q = T::blk_q(WAVE, b), l = WAVE + 8 * aa;
-                if constexpr (b % 4 == 0 && b / 4 + I144_PFG < NGW) aring[(b / 4 + I144_PFG) % RING] = *(const f32x4 *)(wot + (b / 4 + I144_PFG) * 256);
-                const float av = aring[(b / 4) % RING][b % 4];
                 // B operand address: term k of the quad reads channel gid_k, tap_k (compile-time); past the chain's end any valid cell
                 constexpr int nt = T::nterms(l);
                 auto off_of = [](int k) constexpr {
@@ -217,19 +259,28 @@ __device__ __forceinline__ void i144_body(const I144Args &a, float *xs, float *c
                     return (gid * L::PLANE + L::tap_off(tap / 5, tap % 5)) * 4;
                 };
                 constexpr int o0 = off_of(0), o1 = off_of(1), o2 = off_of(2), o3 = off_of(3);
-                int voff = kq == 1 ? o1 : o0;
-                voff = kq == 2 ? o2 : voff;
-                voff = kq == 3 ? o3 : voff;
+                const int kqb = NT > 1 && b % I144_BAS == I144_BAS - 1 ? kq_ot : kq;
+                int voff = kqb == 1 ? o1 : o0;
+                voff = kqb == 2 ? o2 : voff;
+                voff = kqb == 3 ? o3 : voff;
                 const float *bp = (const float *)((const char *)xs + voff) + j;
-                float bv[NT];
 #pragma unroll
-                for (int t = 0; t < NT; ++t) bv[t] = bp[t * L::TOFF];
+                for (int t = 0; t < NT; ++t) bring[b % BRING][t] = bp[t * L::TOFF];
+            };
+            static_for<(BD < NB ? BD : NB)>(b_read);
+            static_for<NB>([&](auto bb) {
+                constexpr int b = decltype(bb)::value, aa = T::blk_a(WAVE, b), q = T::blk_q(WAVE, b);
+                if constexpr (b % 4 == 0 && b / 4 + PFG < NGW) aring[(b / 4 + PFG) % RING] = *(const f32x4 *)(wot + (b / 4 + PFG) * 256);
+                const float av = aring[(b / 4) % RING][b % 4];
+                if constexpr (b + BD < NB) b_read(IC<b + BD>{});
                 __builtin_amdgcn_sched_barrier(0);
                 const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int t = 0; t < NT; ++t) acc[t][aa] = i144_mfma(av, bv[t], q == 0 ? zero4 : acc[t][aa]);
+                for (int t = 0; t < NT; ++t) acc[t][aa] = i144_mfma(av, bring[b % BRING][t], q == 0 ? zero4 : acc[t][aa]);
                 __builtin_amdgcn_sched_barrier(0);
             });
+            wot += 8 * (T::NG * 256);
+            if (ot + 1 < ot_hi) a_head();
             // ---- tree levels +64, +32, +16, +8 in registers (lane slots aa = l >> 3), then one tile per wave and position tile to LDS
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -246,28 +297,15 @@ __device__ __forceinline__ void i144_body(const I144Args &a, float *xs, float *c
             }
             __syncthreads();
             // ---- last three levels (+4, +2, +1 over the waves' residues c), bias, PReLU, residual, store
-            for (int e = tid; e < NT * 256; e += I144_THREADS) {
-                const int t = e >> 8, rem = e & 255, v = rem >> 6, ln = rem & 63;
-                const float *cb = comb + ((parity * NT + t) * 8) * 256 + v * 64 + ln;
+            if constexpr (EPI) {
+                const float *cb = comb + ((parity * NT + e_t) * 8) * 256 + e_v * 64 + lane;
                 const float r0_ = cb[0], r1 = cb[256], r2 = cb[512], r3 = cb[768], r4 = cb[1024], r5 = cb[1280], r6 = cb[1536], r7 = cb[1792];
                 float sv = ((r0_ + r4) + (r2 + r6)) + ((r1 + r5) + (r3 + r7));
-                const int o = ot * 16 + 4 * (ln >> 4) + v, jj = ln & 15;
-                bool ok = o < a.nout;
-                long oi;
-                if constexpr (DC) {
-                    const int th = th0 + 16 * t + jj;
-                    ok = ok && th >= a.th_lo && th <= a.th_hi;
-                    oi = (long)n * a.osample + (long)o * a.oplane + (long)(a.s + I144_R0) * a.opitch + th + I144_C0;
-                } else {
-                    const int y = r0 + t, xx = c0 + jj;
-                    ok = ok && y < a.H && xx < a.W;
-                    oi = (long)n * a.osample + (long)o * a.oplane + (long)(y + a.ooff) * a.opitch + xx + a.ooff;
-                }
-                if (ok) {
-                    sv = sv + a.bias[o];
-                    if (a.act) sv = DC ? (sv < 0 ? sv * a.act[o] : sv) : (sv > 0 ? sv : sv * a.act[o]);   // cconv_dc_cuda.cu:360-362 / cconv_ec_cuda.cu:311-312
-                    if (a.residual) sv = sv + a.residual[oi];
-                    a.out[oi] = sv;
+                if (e_ok) {
+                    sv = sv + e_bias;
+                    if (a.act) sv = DC ? (sv < 0 ? sv * e_act : sv) : (sv > 0 ? sv : sv * e_act);   // cconv_dc_cuda.cu:360-362 / cconv_ec_cuda.cu:311-312
+                    if (a.residual) sv = sv + e_res;
+                    a.out[e_oi] = sv;
                 }
             }
             parity ^= 1;
@@ -355,7 +393,12 @@ LIC360_API int lic360_cconv144_dc_plane(void *stream, const lic360_conv_plan *p,
     const long ntasks = (long)n * a.n_og * a.n_seg;
     const dim3 grid((unsigned)(ntasks < 256 ? ntasks : 256));
     a.grid = (int)grid.x;
-    hipLaunchKernelGGL((k_cconv144<1, true, I144_NT_DC>), grid, dim3(I144_THREADS), 0, (hipStream_t)stream, a);
+    // a window that fits one 16-row tile (the short anti-diagonals at both ends of a map) runs the one-tile instantiation: same tasks, same buffers,
+    // a 5 x 20 window per channel instead of 5 x 36 and none of the second tile's MFMAs
+    if (a.n_seg == 1 && a.th_hi - a.th0 < 16)
+        hipLaunchKernelGGL((k_cconv144<1, true, 1>), grid, dim3(I144_THREADS), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((k_cconv144<1, true, I144_NT_DC>), grid, dim3(I144_THREADS), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK();
     return 0;
 }

@@ -1837,5 +1837,5 @@ LIC360_API const char *lic360_codec_kernel_names(void) {
            "dc_first=k_cconv4v6<1, false, false>+k_cconv4v6t<1>;"
            "dc_hidden=k_cconv4v6l<4>+k_cconv4v6t<4>+k_cconv4v6<4, false, false>+k_cconv4v6<4, false, true>;"
            "dc_last=k_cconv4v6l<4>+k_cconv4v6t<4>+k_cconv4v6<4, false, false>+k_cconv4v6<4, false, true>;"
-           "imp_ec=k_cconv144<1, false, 2>;imp_dc=k_cconv144<1, true, 2>";
+           "imp_ec=k_cconv144<1, false, 2>;imp_dc=k_cconv144<1, true, 2>+k_cconv144<1, true, 1>";
 }
