@@ -21,6 +21,7 @@
 #include <thread>
 #include <atomic>
 #include <memory>
+#include <type_traits>
 #include <immintrin.h>
 
 struct AcDevState {            // per-image decoder state carried across planes
@@ -28,6 +29,15 @@ struct AcDevState {            // per-image decoder state carried across planes
     int nacc, error, pad;
     long pos;
     unsigned long long acc;
+};
+// The diagonal-major layout of the decode activations, planes of [rows][pitch] floats: cell (th, tw) lives at row th + tw + row0, column th + col0, so
+// that the positions of one anti-diagonal -- what a decode plane touches -- are contiguous.  lic360_dc4_layout and lic360_dc144_layout give the
+// zero-padded forms their kernels read; the generic kernels take the plain one.
+struct DcLayout {
+    int rows, pitch, row0, col0;
+    __host__ __device__ long plane() const { return (long)rows * pitch; }
+    __host__ __device__ long cell(int th, int tw) const { return (long)(th + tw + row0) * pitch + th + col0; }
+    static DcLayout plain(int h, int w) { return DcLayout{h + w - 1, h, 0, 0}; }
 };
 
 struct PlanDeleter { void operator()(lic360_conv_plan *p) const { lic360_conv_plan_destroy(p); } };
@@ -117,7 +127,7 @@ static const char *const PROF_NAMES = "ec_first,ec_hidden,ec_last,enc_tables,ac_
 struct HostLeg;
 struct lic360_codec {
     int G, H, W, maxB, S, P, HW;
-    int sk_rows, sk_pitch, sk_row0, sk_col0;
+    DcLayout sk;
     int e_hp, e_wp, e_off;                     // encode activation planes: [e_hp][e_wp], cell (r, c) at [(r+e_off)*e_wp + c+e_off]
     NetWeights w{"codec", "lic360_codec_set_layer", 3};   // the GMM's weight, delta and mean nets; with use4, xpack[0]: the leaf-resident
                                                // (4x4x1 MFMA) decode-order packing, xpack[1]: the 16x16x4 encode-order one (csrc/cconv16_kernels.hip)
@@ -189,6 +199,18 @@ __global__ void k_enc_prep(const float *__restrict__ code, const float *__restri
     }
 }
 
+// The CDF table T[0..8] of the latent symbol of image b (of B), group g (of G), 0 = T[0] < T[1] < ... < T[8] = 65536: its 3 x 3 GMM parameters gathered
+// from the outputs y of the three stacked nets ([3 B][3 G] planes of `plane` floats, the symbol's cell at offset `cell` of a plane).
+__device__ __forceinline__ void gmm_table(const float *__restrict__ y, int B, int b, int G, int g, long plane, long cell, int *T) {
+    float v[9];
+#pragma unroll
+    for (int net = 0; net < 3; ++net)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            v[net * 3 + c] = y[((long)(net * B + b) * (3 * G) + g * 3 + c) * plane + cell];
+    gmm_cdf9(v, v + 3, v + 6, T);
+}
+
 // one thread per latent element (NCHW-linear, coalesced reads); the (cdf[sym], cdf[sym+1]) pair is
 // written at the symbol's position in coding order: plane p = g+th+tw, diagonals ascending inside a
 // plane, rows ascending inside a diagonal (extension/code_contex_cuda.cu:19-31, tile_extract_cuda.cu:36-41).
@@ -203,15 +225,8 @@ __global__ void k_enc_tables(const float *__restrict__ y, const float *__restric
         long k = plane_start[p] + (pidx[s] - pidx[la]) + (th - (s >= W ? s - W + 1 : 0));
         uint2 r = make_uint2(0u, 0u);
         if (!(mask[i] < 0.5f)) {                                     // coder.cpp:79
-            float v[9];
-            const long cell = e_cell(th, tw, wp, off);
-#pragma unroll
-            for (int net = 0; net < 3; ++net)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    v[net * 3 + c] = y[((long)(net * B + b) * (3 * G) + g * 3 + c) * hp * wp + cell];
             int T[9];
-            gmm_cdf9(v, v + 3, v + 6, T);
+            gmm_table(y, B, b, G, g, (long)hp * wp, e_cell(th, tw, wp, off), T);
             int sym = (int)code[i];
             sym = sym < 0 ? 0 : (sym > 7 ? 7 : sym);
             r = make_uint2((unsigned)T[sym], (unsigned)T[sym + 1]);
@@ -583,49 +598,23 @@ struct DecTablesArgs {
     int G;
     int H;
     int W;
-    int sk_rows;
-    int sk_pitch;
-    int sk_row0;
-    int sk_col0;
+    DcLayout sk;
 };
 __global__ __launch_bounds__(64) void k_dec_tables(const DecTablesArgs a) {
-    const float *__restrict__ y = a.y;
-    const float *__restrict__ mask = a.mask;
-    const int *__restrict__ idx = a.idx;
-    const int start = a.start;
-    const int len = a.len;
-    const int p = a.p;
-    uint4 *__restrict__ tab = a.tab;
-    const int tab_pitch = a.tab_pitch;
-    const int B = a.B;
-    const int G = a.G;
-    const int H = a.H;
-    const int W = a.W;
-    const int sk_rows = a.sk_rows;
-    const int sk_pitch = a.sk_pitch;
-    const int sk_row0 = a.sk_row0;
-    const int sk_col0 = a.sk_col0;
     const int b = blockIdx.y, i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= len) return;
-    const int HW = H * W;
-    const long SK = (long)sk_rows * sk_pitch;
-    const int q = start + i;
-    const int th = idx[q], tw = idx[q + HW], g = p - th - tw;
-    const long nchw = (((long)b * G + g) * H + th) * W + tw;
+    if (i >= a.len) return;
+    const int HW = a.H * a.W;
+    const int q = a.start + i;
+    const int th = a.idx[q], tw = a.idx[q + HW], g = a.p - th - tw;
+    const long nchw = (((long)b * a.G + g) * a.H + th) * a.W + tw;
     uint4 r = make_uint4(0u, 0u, 0u, 0u), r2 = r;
-    if (!(mask[nchw] < 0.5f)) {                                      // coder.cpp:79
-        float v[9];
-#pragma unroll
-        for (int net = 0; net < 3; ++net)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                v[net * 3 + c] = y[((long)(net * B + b) * (3 * G) + g * 3 + c) * SK + (long)(th + tw + sk_row0) * sk_pitch + th + sk_col0];
+    if (!(a.mask[nchw] < 0.5f)) {                                    // coder.cpp:79
         int T[9];
-        gmm_cdf9(v, v + 3, v + 6, T);                                // 0 = T[0] < T[1] < ... < T[8] = 65536
+        gmm_table(a.y, a.B, b, a.G, g, a.sk.plane(), a.sk.cell(th, tw), T);
         dec_pack8(T, r, r2);
     }
-    tab[((long)b * tab_pitch + i) * 2] = r;
-    tab[((long)b * tab_pitch + i) * 2 + 1] = r2;
+    a.tab[((long)b * a.tab_pitch + i) * 2] = r;
+    a.tab[((long)b * a.tab_pitch + i) * 2 + 1] = r2;
 }
 
 // LINEAR (test hook lic360_devcoder_decode): symbols go to code_out[b*G + start + i] instead of the latent layouts
@@ -646,64 +635,42 @@ struct DecPlaneArgs {
     int G;
     int H;
     int W;
-    int sk_rows;
-    int sk_pitch;
-    int sk_row0;
-    int sk_col0;
+    DcLayout sk;
 };
 template <bool LINEAR>
 __global__ __launch_bounds__(64) void k_dec_plane(const DecPlaneArgs a) {
-    const uint4 *__restrict__ tab = a.tab;
-    const int tab_pitch = a.tab_pitch;
-    const int *__restrict__ idx = a.idx;
-    const int start = a.start;
-    const int len = a.len;
-    const int p = a.p;
-    AcDevState *__restrict__ state = a.state;
-    const uint8_t *__restrict__ bytes = a.bytes;
-    const long cap = a.cap;
-    const int *__restrict__ nbytes = a.nbytes;
-    float *__restrict__ x0 = a.x0;
-    float *__restrict__ code_out = a.code_out;
-    const int G = a.G;
-    const int H = a.H;
-    const int W = a.W;
-    const int sk_rows = a.sk_rows;
-    const int sk_pitch = a.sk_pitch;
-    const int sk_row0 = a.sk_row0;
-    const int sk_col0 = a.sk_col0;
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int HW = H * W;
-    const long SK = (long)sk_rows * sk_pitch;
-    AcDevState ds = state[b];
+    const int HW = a.H * a.W;
+    const long SK = a.sk.plane();
+    AcDevState ds = a.state[b];
     AcState st;
     // (the state goes through inline assembly with scalar-register operands: make sure it IS scalar)
     auto sgpr = [](uint32_t v) __attribute__((always_inline)) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     st.low = sgpr(ds.low); st.high = sgpr(ds.high); st.code = sgpr(ds.code); st.underflow = 0; st.error = 0;
     DevBits rd;
-    rd.buf = bytes + (long)b * cap; rd.len = dev_stream_len(nbytes[b], cap); rd.pos = (int)sgpr((uint32_t)ds.pos);
+    rd.buf = a.bytes + (long)b * a.cap; rd.len = dev_stream_len(a.nbytes[b], a.cap); rd.pos = (int)sgpr((uint32_t)ds.pos);
     rd.acc = ((unsigned long long)sgpr((uint32_t)(ds.acc >> 32)) << 32) | sgpr((uint32_t)ds.acc); rd.nacc = (int)sgpr((uint32_t)ds.nacc); rd.lane = lane;
     rd.fetch_window();
     // Tables: eight VGPRs hold the 8 x 8 words of a group's 64 symbols (lane 8q + k of register r = word k of symbol 8r + q); a
     // register is refilled with the next group's words as soon as its eight symbols are decoded, so that no memory latency sits
     // between groups.  The scan positions of the next group are fetched before the serial chain of the current one runs.
-    const uint32_t *const tw32 = (const uint32_t *)(tab + (long)b * tab_pitch * 2);
+    const uint32_t *const tw32 = (const uint32_t *)(a.tab + (long)b * a.tab_pitch * 2);
     auto load_tab = [&](int base, int r) __attribute__((always_inline)) {
         uint32_t t = 0u;
-        if (base + 8 * r + (lane >> 3) < len) t = tw32[(long)(base + 8 * r) * 8 + lane];
+        if (base + 8 * r + (lane >> 3) < a.len) t = tw32[(long)(base + 8 * r) * 8 + lane];
         return t;
     };
     auto load_pos = [&](int base, int &th, int &tw) __attribute__((always_inline)) {
         th = tw = 0;
-        if constexpr (!LINEAR) { if (base + lane < len) { th = idx[start + base + lane]; tw = idx[start + base + lane + HW]; } }
+        if constexpr (!LINEAR) { if (base + lane < a.len) { th = a.idx[a.start + base + lane]; tw = a.idx[a.start + base + lane + HW]; } }
     };
     uint32_t tv[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) tv[r] = load_tab(0, r);
     int th_cur, tw_cur;
     load_pos(0, th_cur, tw_cur);
-    for (int base = 0; base < len; base += 64) {
-        const bool live = base + lane < len;
+    for (int base = 0; base < a.len; base += 64) {
+        const bool live = base + lane < a.len;
         int th_next, tw_next;
         load_pos(base + 64, th_next, tw_next);
         int symv = 0;
@@ -725,11 +692,11 @@ __global__ __launch_bounds__(64) void k_dec_plane(const DecPlaneArgs a) {
         }
         const bool coded = (coded_m >> lane) & 1ull;
         if (live) {
-            if constexpr (LINEAR) code_out[(long)b * G + start + base + lane] = coded ? (float)symv : 0.0f;
+            if constexpr (LINEAR) a.code_out[(long)b * a.G + a.start + base + lane] = coded ? (float)symv : 0.0f;
             else {
-                const int th = th_cur, tw = tw_cur, g = p - th - tw;
-                x0[((long)b * G + g) * SK + (long)(th + tw + sk_row0) * sk_pitch + th + sk_col0] = coded ? (float)symv - 3.5f : 0.0f;
-                code_out[(((long)b * G + g) * H + th) * W + tw] = coded ? (float)symv : 0.0f;
+                const int th = th_cur, tw = tw_cur, g = a.p - th - tw;
+                a.x0[((long)b * a.G + g) * SK + a.sk.cell(th, tw)] = coded ? (float)symv - 3.5f : 0.0f;
+                a.code_out[(((long)b * a.G + g) * a.H + th) * a.W + tw] = coded ? (float)symv : 0.0f;
             }
         }
         th_cur = th_next; tw_cur = tw_next;
@@ -738,7 +705,7 @@ __global__ __launch_bounds__(64) void k_dec_plane(const DecPlaneArgs a) {
     if (lane == 0) {
         ds.low = st.low; ds.high = st.high; ds.code = st.code; ds.error |= st.error;     // sticky: coder faults 1..3, clamp flag 32
         ds.pos = rd.pos; ds.acc = rd.acc; ds.nacc = rd.nacc;
-        state[b] = ds;
+        a.state[b] = ds;
     }
 }
 
@@ -842,7 +809,8 @@ struct DecTablesHostArgs {
     const int *idx;
     int start, len, p;
     uint4 *tab;                                 // pinned: [B][tab_pitch] x 8 halves
-    int tab_pitch, B, G, H, W, sk_rows, sk_pitch, sk_row0, sk_col0;
+    int tab_pitch, B, G, H, W;
+    DcLayout sk;
     int *ctr, *flag;
     int seq, nblocks;
 };
@@ -850,20 +818,13 @@ __global__ __launch_bounds__(64) void k_dec_tables_host(const DecTablesHostArgs 
     const int b = blockIdx.y, i = blockIdx.x * 64 + threadIdx.x;
     if (i < a.len) {
         const int HW = a.H * a.W;
-        const long SK = (long)a.sk_rows * a.sk_pitch;
         const int q = a.start + i;
         const int th = a.idx[q], tw = a.idx[q + HW], g = a.p - th - tw;
         const long nchw = (((long)b * a.G + g) * a.H + th) * a.W + tw;
         uint4 r = make_uint4(0u, 0u, 0u, 0u);
         if (!(a.mask[nchw] < 0.5f)) {                                    // coder.cpp:79
-            float v[9];
-#pragma unroll
-            for (int net = 0; net < 3; ++net)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    v[net * 3 + c] = a.y[((long)(net * a.B + b) * (3 * a.G) + g * 3 + c) * SK + (long)(th + tw + a.sk_row0) * a.sk_pitch + th + a.sk_col0];
             int T[9];
-            gmm_cdf9(v, v + 3, v + 6, T);                                // 0 = T[0] < T[1] < ... < T[8] = 65536: the inner entries fit 16 bits
+            gmm_table(a.y, a.B, b, a.G, g, a.sk.plane(), a.sk.cell(th, tw), T);     // the inner entries fit 16 bits
             r = make_uint4(1u | (unsigned)T[1] << 16, (unsigned)T[2] | (unsigned)T[3] << 16, (unsigned)T[4] | (unsigned)T[5] << 16, (unsigned)T[6] | (unsigned)T[7] << 16);
         }
         a.tab[(long)b * a.tab_pitch + i] = r;
@@ -884,7 +845,8 @@ struct DecWaitArgs {
     const int *idx;
     int start, len, p;
     float *x0, *code_out;
-    int G, H, W, sk_rows, sk_pitch, sk_row0, sk_col0;
+    int G, H, W;
+    DcLayout sk;
 };
 __global__ __launch_bounds__(1024) void k_dec_wait_scatter(const DecWaitArgs a) {
     __shared__ int s_abort;
@@ -904,13 +866,12 @@ __global__ __launch_bounds__(1024) void k_dec_wait_scatter(const DecWaitArgs a) 
         return;
     }
     const int HW = a.H * a.W;
-    const long SK = (long)a.sk_rows * a.sk_pitch;
     for (int e = tid; e < a.B * a.len; e += 1024) {
         const int b = e / a.len, j = e - b * a.len;
         const float v = a.sym[(long)b * a.tab_pitch + j];
         const bool coded = v >= 0.0f;
         const int th = a.idx[a.start + j], tw = a.idx[a.start + j + HW], g = a.p - th - tw;
-        a.x0[((long)b * a.G + g) * SK + (long)(th + tw + a.sk_row0) * a.sk_pitch + th + a.sk_col0] = coded ? v - 3.5f : 0.0f;   // = TileInput + `b[0:1] + 3.5*mask` (lic360_demo.py:222,236-237)
+        a.x0[((long)b * a.G + g) * a.sk.plane() + a.sk.cell(th, tw)] = coded ? v - 3.5f : 0.0f;   // = TileInput + `b[0:1] + 3.5*mask` (lic360_demo.py:222,236-237)
         a.code_out[(((long)b * a.G + g) * a.H + th) * a.W + tw] = coded ? v : 0.0f;
     }
 }
@@ -981,9 +942,9 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     if (acc != ngroup * c->HW) { lic360_set_error("internal: plane schedule does not cover the latent"); return 1; }
     if (c->d_plane_start.alloc(c->h_plane_start.size())) return 1;
     HIP_TRY(hipMemcpy(c->d_plane_start, c->h_plane_start.data(), c->h_plane_start.size() * 4, hipMemcpyHostToDevice));
-    if (c->use4) { if (lic360_dc4_layout(h, w, &c->sk_rows, &c->sk_pitch, &c->sk_row0, &c->sk_col0)) return 1; }
-    else { c->sk_rows = c->S; c->sk_pitch = h; c->sk_row0 = 0; c->sk_col0 = 0; }
-    const size_t B = max_batch, G = ngroup, HW = c->HW, SK = (size_t)c->sk_rows * c->sk_pitch, TAIL = (size_t)lic360_conv4_buffer_floats(0, 1, h, w) - (size_t)c->sk_rows * c->sk_pitch;   // slack for the band fetches of the last plane
+    c->sk = DcLayout::plain(h, w);
+    if (c->use4 && lic360_dc4_layout(h, w, &c->sk.rows, &c->sk.pitch, &c->sk.row0, &c->sk.col0)) return 1;
+    const size_t B = max_batch, G = ngroup, HW = c->HW, SK = (size_t)c->sk.plane(), TAIL = (size_t)lic360_conv4_buffer_floats(0, 1, h, w) - SK;   // slack for the band fetches of the last plane
     c->dc_mode = lic360_dc4_env_mode();
     // encode order: 16x16x4 MFMA kernels on zero-haloed NCHW planes, or plain NCHW for the generic kernels
     if (c->use4) { if (lic360_ec16_layout(h, w, &c->e_hp, &c->e_wp)) return 1; c->e_off = 2; }
@@ -1195,19 +1156,18 @@ static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes
         if (host) {
             const int nblk = (len + 63) / 64 * B;
             PROF(c, PROF_DEC_TABLES, s, hipLaunchKernelGGL(k_dec_tables_host, dim3((len + 63) / 64, B), dim3(64), 0, s, DecTablesHostArgs{c->d_y, mask, c->d_idx, start, len, p,
-                                                           (uint4 *)(unsigned short *)h->tab_h, h->tab_pitch, B, G, H, W, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0, h->d_ctr, h->flags, seq0 + p + 1, nblk}));
+                                                           (uint4 *)(unsigned short *)h->tab_h, h->tab_pitch, B, G, H, W, c->sk, h->d_ctr, h->flags, seq0 + p + 1, nblk}));
             LAUNCH_CHECK();
             PROF(c, PROF_DEC_PLANE, s, hipLaunchKernelGGL(k_dec_wait_scatter, dim3(1), dim3(1024), 0, s, DecWaitArgs{h->flags, h->sym_h, seq0 + p + 1, B, h->tab_pitch, c->d_idx, start, len, p,
-                                                          c->d_x0, code_out, G, H, W, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0}));
+                                                          c->d_x0, code_out, G, H, W, c->sk}));
             LAUNCH_CHECK();
             continue;
         }
         PROF(c, PROF_DEC_TABLES, s, hipLaunchKernelGGL(k_dec_tables, dim3((len + 63) / 64, B), dim3(64), 0, s, DecTablesArgs{c->d_y, mask, c->d_idx, start, len, p,
-                                                       c->d_tab, c->tab_pitch, B, G, H, W, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0}));
+                                                       c->d_tab, c->tab_pitch, B, G, H, W, c->sk}));
         LAUNCH_CHECK();
         PROF(c, PROF_DEC_PLANE, s, hipLaunchKernelGGL(k_dec_plane<false>, dim3(B), dim3(64), 0, s, DecPlaneArgs{c->d_tab, c->tab_pitch, c->d_idx, start, len, p,
-                                                      c->d_state, bytes, cap, nbytes, c->d_x0, code_out, G, H, W, c->sk_rows, c->sk_pitch,
-                                                      c->sk_row0, c->sk_col0}));
+                                                      c->d_state, bytes, cap, nbytes, c->d_x0, code_out, G, H, W, c->sk}));
         LAUNCH_CHECK();
     }
     if (host) hipLaunchKernelGGL(k_hl_err, dim3((B + 63) / 64), dim3(64), 0, s, h->err_h, h->flags, err, B);
@@ -1223,8 +1183,10 @@ LIC360_API int lic360_codec_decode(void *stream, lic360_codec *c, const uint8_t 
 // ------------------------------------------------------------------------------------------------ importance-map stream
 // Device-resident counterpart of ImpEntEncoderFast / ImpEntDecoder (test/lic360_demo.py:143-189, 241-290): one group, a
 // 12-layer spatially causal net with `cpg` hidden channels, an nsym-way softmax table per position
-// (entropy_table_cuda.cu:24-96), symbols = importance levels, input scale 2/(nsym-2) and bias -1.  The convolutions run on
-// the generic 16x16x4 kernels (cin = cpg is outside the leaf-resident kernel's shapes); tables and the coder on the GPU.
+// (entropy_table_cuda.cu:24-96), symbols = importance levels, input scale 2/(nsym-2) and bias -1.  With cpg = 144 the layers
+// after the first run on the leaf-resident kernels of csrc/cconv144_kernels.hip (use144); the first layer, and every layer of
+// another width, on the generic 16x16x4 kernels (cpg is outside the latent nets' leaf-resident shapes).  Tables and the coder
+// on the GPU.
 struct lic360_impcodec {
     int H, W, HW, P, cpg, nsym, maxB;
     float sc;
@@ -1235,11 +1197,11 @@ struct lic360_impcodec {
     DevBuf<uint2> e_rec;
     DevBuf<float> d_x0, d_act[11], d_y;
     // leaf-resident 16x16x4 kernels for the 144-channel layers (csrc/cconv144_kernels.hip): encode on zero-haloed NCHW planes,
-    // decode on zero-padded diagonal-major planes [rows = sk_rows][sk_pitch], cell (th, tw) at (th + tw + sk_row0, th + sk_col0)
+    // decode on zero-padded diagonal-major planes (sk)
     bool use144 = false;
     int e_hp = 0, e_wp = 0;
     DevBuf<float> e_pad[3], e_plain;
-    int sk_rows, sk_pitch, sk_row0, sk_col0;
+    DcLayout sk;
     DevBuf<int> d_tab;                          // [maxB][tab_pitch][IMP_TW] tables of the current plane
     int tab_pitch;
     DevBuf<AcDevState> d_state;
@@ -1282,6 +1244,11 @@ __device__ __forceinline__ void imp_table_t(const float *__restrict__ y, long ba
     softmax_table_static<NSYM>(lg, 65536.0f, T);
 }
 #define IMP_NSYM_FAST 49                                              // the alphabet of every LIC360 importance net (model_zoo.py)
+// launch(std::true_type) for that alphabet, launch(std::false_type) for any other: the table kernels' two instantiations, one argument list
+template <class F>
+static void imp_tables_launch(int nsym, F launch) {
+    if (nsym == IMP_NSYM_FAST) launch(std::true_type()); else launch(std::false_type());
+}
 template <bool FAST>
 __global__ void k_imp_enc_tables(const float *__restrict__ y, const float *__restrict__ lv, const int *__restrict__ pidx, uint2 *__restrict__ rec,
                                  int B, int H, int W, int nsym) {
@@ -1317,40 +1284,24 @@ struct ImpDecTablesArgs {
     int H;
     int W;
     int nsym;
-    int sk_rows;
-    int sk_pitch;
-    int sk_row0;
-    int sk_col0;
+    DcLayout sk;
 };
 template <bool FAST>
 __global__ __launch_bounds__(64) void k_imp_dec_tables(const ImpDecTablesArgs a) {
-    const float *__restrict__ y = a.y;
-    const int *__restrict__ idx = a.idx;
-    const int start = a.start;
-    const int len = a.len;
-    int *__restrict__ tab = a.tab;
-    const int tab_pitch = a.tab_pitch;
-    const int H = a.H;
-    const int W = a.W;
-    const int nsym = a.nsym;
-    const int sk_rows = a.sk_rows;
-    const int sk_pitch = a.sk_pitch;
-    const int sk_row0 = a.sk_row0;
-    const int sk_col0 = a.sk_col0;
     const int b = blockIdx.y, i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= len) return;
-    const long HW = (long)H * W, SK = (long)sk_rows * sk_pitch;
-    const int th = idx[start + i], tw = idx[start + i + HW];
-    int *row = tab + ((long)b * tab_pitch + i) * IMP_TW;
+    if (i >= a.len) return;
+    const long HW = (long)a.H * a.W, SK = a.sk.plane();
+    const int th = a.idx[a.start + i], tw = a.idx[a.start + i + HW];
+    int *row = a.tab + ((long)b * a.tab_pitch + i) * IMP_TW;
     if constexpr (FAST) {
         float T[IMP_NSYM_FAST + 1];
-        imp_table_t<IMP_NSYM_FAST>(y, (long)b * nsym * SK + (long)(th + tw + sk_row0) * sk_pitch + th + sk_col0, SK, T);
+        imp_table_t<IMP_NSYM_FAST>(a.y, (long)b * a.nsym * SK + a.sk.cell(th, tw), SK, T);
 #pragma unroll
         for (int k = 0; k <= IMP_NSYM_FAST; ++k) row[k] = (int)T[k];
     } else {
         float T[65];
-        imp_table(y, (long)b * nsym * SK + (long)(th + tw + sk_row0) * sk_pitch + th + sk_col0, SK, nsym, T);
-        for (int k = 0; k <= nsym; ++k) row[k] = (int)T[k];
+        imp_table(a.y, (long)b * a.nsym * SK + a.sk.cell(th, tw), SK, a.nsym, T);
+        for (int k = 0; k <= a.nsym; ++k) row[k] = (int)T[k];
     }
 }
 // one wave per image: lane k holds T[k] of the current symbol; the symbol is the number of inner entries <= target
@@ -1371,63 +1322,42 @@ struct ImpDecPlaneArgs {
     int W;
     int nsym;
     float sc;
-    int sk_rows = 0;
-    int sk_pitch = 0;
-    int sk_row0 = 0;
-    int sk_col0 = 0;
+    DcLayout sk;
 };
 template <bool LINEAR>
 __global__ __launch_bounds__(64) void k_imp_dec_plane(const ImpDecPlaneArgs a) {
-    const int *__restrict__ tab = a.tab;
-    const int tab_pitch = a.tab_pitch;
-    const int *__restrict__ idx = a.idx;
-    const int start = a.start;
-    const int len = a.len;
-    AcDevState *__restrict__ state = a.state;
-    const uint8_t *__restrict__ bytes = a.bytes;
-    const long cap = a.cap;
-    const int *__restrict__ nbytes = a.nbytes;
-    float *__restrict__ x0 = a.x0;
-    float *__restrict__ out = a.out;
-    const int H = a.H;
-    const int W = a.W;
-    const int nsym = a.nsym;
-    const float sc = a.sc;
-    const int sk_rows = a.sk_rows;
-    const int sk_pitch = a.sk_pitch;
-    const int sk_row0 = a.sk_row0;
-    const int sk_col0 = a.sk_col0;
     const int b = blockIdx.x, lane = threadIdx.x;
-    const long HW = (long)H * W;
-    AcDevState ds = state[b];
+    const long HW = (long)a.H * a.W;
+    AcDevState ds = a.state[b];
     AcState st;
     st.low = ds.low; st.high = ds.high; st.code = ds.code; st.underflow = 0; st.error = 0;
     DevBits rd;
-    rd.buf = bytes + (long)b * cap; rd.len = dev_stream_len(nbytes[b], cap); rd.pos = ds.pos; rd.acc = ds.acc; rd.nacc = ds.nacc; rd.lane = lane;
+    rd.buf = a.bytes + (long)b * a.cap; rd.len = dev_stream_len(a.nbytes[b], a.cap); rd.pos = ds.pos; rd.acc = ds.acc; rd.nacc = ds.nacc; rd.lane = lane;
     rd.fetch_window();
-    const int *rows = tab + (long)b * tab_pitch * IMP_TW;
-    int tnext = len > 0 ? rows[lane] : 0;
-    for (int j = 0; j < len; ++j) {
+    const int *rows = a.tab + (long)b * a.tab_pitch * IMP_TW;
+    int tnext = a.len > 0 ? rows[lane] : 0;
+    for (int j = 0; j < a.len; ++j) {
         const int tl = tnext;
-        if (j + 1 < len) tnext = rows[(long)(j + 1) * IMP_TW + lane];               // next row is in flight while this symbol decodes
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane(tl, nsym);
+        if (j + 1 < a.len) tnext = rows[(long)(j + 1) * IMP_TW + lane];               // next row is in flight while this symbol decodes
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane(tl, a.nsym);
         const uint32_t target = ac_decode_target(st, total);
-        const int sym = __popcll(__ballot(lane >= 1 && lane < nsym && target >= (uint32_t)tl));
+        const int sym = __popcll(__ballot(lane >= 1 && lane < a.nsym && target >= (uint32_t)tl));
         const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane(tl, sym), hi = (uint32_t)__builtin_amdgcn_readlane(tl, sym + 1);
         ac_decode_consume_from(st, rd, lo, hi, total);
         if (lane == 0) {
-            if constexpr (LINEAR) out[(long)b * HW + start + j] = (float)sym;
+            if constexpr (LINEAR) a.out[(long)b * HW + a.start + j] = (float)sym;
             else {
-                const int th = idx[start + j], tw = idx[start + j + HW];
-                x0[(long)b * sk_rows * sk_pitch + (long)(th + tw + sk_row0) * sk_pitch + th + sk_col0] = lic360_affine((float)sym, sc, -1.0f);   // TileInput(1, -1, 2/47, 1): lic360_demo.py:264
-                out[(long)b * HW + (long)th * W + tw] = (float)sym;
+                const int th = a.idx[a.start + j], tw = a.idx[a.start + j + HW];
+                // (sk.cell(th, tw) of plane b, written out: through the call this chain's instructions change, and their count is the decode latency)
+                a.x0[(long)b * a.sk.rows * a.sk.pitch + (long)(th + tw + a.sk.row0) * a.sk.pitch + th + a.sk.col0] = lic360_affine((float)sym, a.sc, -1.0f);   // TileInput(1, -1, 2/47, 1): lic360_demo.py:264
+                a.out[(long)b * HW + (long)th * a.W + tw] = (float)sym;
             }
         }
     }
     if (lane == 0) {
         ds.low = st.low; ds.high = st.high; ds.code = st.code; ds.error |= st.error;     // sticky: coder faults 1..3, clamp flag 32
         ds.pos = rd.pos; ds.acc = rd.acc; ds.nacc = rd.nacc;
-        state[b] = ds;
+        a.state[b] = ds;
     }
 }
 
@@ -1444,14 +1374,15 @@ LIC360_API int lic360_impcodec_create(int h, int w, int hidden_channels, int nsy
     if (c->e_rec.alloc(B * HW)) return 1;
     // 144-channel layers on the leaf-resident 16x16x4 kernels (other widths keep the generic kernels)
     c->use144 = lic360_conv144_supported(c->w.plan[1].get()) && lic360_conv144_supported(c->w.plan[2].get());
+    c->sk = DcLayout::plain(h, w);
     if (c->use144) {
-        if (lic360_ec144_layout(h, w, &c->e_hp, &c->e_wp) || lic360_dc144_layout(h, w, &c->sk_rows, &c->sk_pitch)) return 1;
-        c->sk_row0 = I144_R0; c->sk_col0 = I144_C0;
+        c->sk.row0 = I144_R0; c->sk.col0 = I144_C0;
+        if (lic360_ec144_layout(h, w, &c->e_hp, &c->e_wp) || lic360_dc144_layout(h, w, &c->sk.rows, &c->sk.pitch)) return 1;
         for (DevBuf<float> &b : c->e_pad) if (b.alloc(B * C * (size_t)c->e_hp * c->e_wp)) return 1;
         if (c->e_plain.alloc(B * CE * HW)) return 1;
         for (int i = 0; i < 3; ++i) HIP_TRY(hipMemset(c->e_pad[i], 0, B * C * (size_t)c->e_hp * c->e_wp * 4));   // the halo stays zero
-    } else { c->sk_rows = h + w - 1; c->sk_pitch = h; c->sk_row0 = 0; c->sk_col0 = 0; }
-    const size_t SK = (size_t)c->sk_rows * c->sk_pitch;                   // diagonal-major decode planes
+    }
+    const size_t SK = (size_t)c->sk.plane();                   // diagonal-major decode planes
     if (c->d_x0.alloc(B * SK)) return 1;
     for (DevBuf<float> &b : c->d_act) if (b.alloc(B * C * SK)) return 1;
     if (c->d_y.alloc(B * (size_t)nsym * SK) || c->d_tab.alloc(B * (size_t)c->tab_pitch * IMP_TW) || c->d_state.alloc(B)) return 1;
@@ -1493,8 +1424,9 @@ LIC360_API int lic360_impcodec_encode(void *stream, lic360_impcodec *c, const fl
     };
     float *y = c->use144 ? c->e_plain : c->e_buf[1];                               // [B, nsym, H, W] (the generic path uses the first nsym planes of the buffer)
     if (net_walk(c->e_x0, c->use144 ? c->e_pad : c->e_buf, 3, y, ec)) return 1;
-    if (c->nsym == IMP_NSYM_FAST) hipLaunchKernelGGL(k_imp_enc_tables<true>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, y, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
-    else hipLaunchKernelGGL(k_imp_enc_tables<false>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, y, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
+    imp_tables_launch(c->nsym, [&](auto fast) {
+        hipLaunchKernelGGL(k_imp_enc_tables<decltype(fast)::value>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, y, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
+    });
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_ac_encode, dim3(B), dim3(128), 0, s, c->e_rec, (long)c->HW, bytes, cap, nbytes, err);
     LAUNCH_CHECK();
@@ -1518,27 +1450,16 @@ struct ImpMaskPlaneArgs {
     int cpn;
 };
 __global__ void k_imp_mask_plane(const ImpMaskPlaneArgs a) {
-    const float *__restrict__ levels = a.levels;
-    const int *__restrict__ idx = a.idx;
-    const int start = a.start;
-    const int len = a.len;
-    float *__restrict__ out = a.out;
-    const int B = a.B;
-    const int H = a.H;
-    const int W = a.W;
-    const int C = a.C;
-    const int s = a.s;
-    const int cpn = a.cpn;
-    const long HW = (long)H * W, total = (long)B * len * C;
-    const int Co = C / (s * s), Ho = H * s, Wo = W * s;
+    const long HW = (long)a.H * a.W, total = (long)a.B * a.len * a.C;
+    const int Co = a.C / (a.s * a.s), Ho = a.H * a.s, Wo = a.W * a.s;
     // one thread per element, 256 threads per workgroup (launched once per plane: no gridDim / blockDim, so no implicit kernel arguments)
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e < total) {
-        const int tc = (int)(e % C), i = (int)((e / C) % len), b = (int)(e / C / len);
-        const int th = idx[start + i], tw = idx[start + i + HW];
-        const int imp = (int)((double)levels[(long)b * HW + (long)th * W + tw] + 1e-5) * cpn;
-        const int pc = tc / (s * s), r = tc % (s * s), ph = th * s + r / s, pw = tw * s + r % s;
-        out[(((long)b * Co + pc) * Ho + ph) * Wo + pw] = tc < imp ? 1.0f : 0.0f;
+        const int tc = (int)(e % a.C), i = (int)((e / a.C) % a.len), b = (int)(e / a.C / a.len);
+        const int th = a.idx[a.start + i], tw = a.idx[a.start + i + HW];
+        const int imp = (int)((double)a.levels[(long)b * HW + (long)th * a.W + tw] + 1e-5) * a.cpn;
+        const int pc = tc / (a.s * a.s), r = tc % (a.s * a.s), ph = th * a.s + r / a.s, pw = tw * a.s + r % a.s;
+        a.out[(((long)b * Co + pc) * Ho + ph) * Wo + pw] = tc < imp ? 1.0f : 0.0f;
     }
 }
 static int impcodec_decode_impl(void *stream, lic360_impcodec *c, const uint8_t *bytes, long cap, const int *nbytes, int B,
@@ -1551,28 +1472,26 @@ static int impcodec_decode_impl(void *stream, lic360_impcodec *c, const uint8_t 
     hipLaunchKernelGGL(k_dec_init, dim3((B + 63) / 64), dim3(64), 0, s, bytes, cap, nbytes, c->d_state, B);
     LAUNCH_CHECK();
     const int *pih = c->h_pidx.data();
-    const long SK = (long)c->sk_rows * c->sk_pitch, off0 = (long)c->sk_row0 * c->sk_pitch + c->sk_col0;
+    // the generic kernel takes the layout as an origin and the strides of a step in th and in tw
+    const long SK = c->sk.plane(), off0 = c->sk.cell(0, 0), s_th = c->sk.cell(1, 0) - off0, s_tw = c->sk.cell(0, 1) - off0;
     const NetWeights &nw = c->w;
     for (int p = 0; p < c->P; ++p) {
         if (net_walk(c->d_x0, c->d_act, 11, c->d_y, [&](int layer, const float *xin, const float *res, float *dst) -> int {
                 if (c->use144 && layer > 0)
                     return lic360_cconv144_dc_plane(stream, nw.at(layer), xin, nw.xpack[0][layer], nw.bias[layer], nw.act[layer], res, dst, B, H, W, p);
-                // generic kernel on the diagonal-major planes: cell (th, tw) at th * (pitch + 1) + tw * pitch from the layout's origin
                 return lic360_cconv_dc_plane_strided(stream, nw.at(layer), xin + off0, nw.packed[layer], nw.bias[layer], nw.act[layer],
                                                      res ? res + off0 : nullptr, dst + off0, B, H, W, 1, c->d_idx, c->d_pidx, pih, p, B,
-                                                     SK, c->sk_pitch + 1, c->sk_pitch, SK, c->sk_pitch + 1, c->sk_pitch);
+                                                     SK, s_th, s_tw, SK, s_th, s_tw);
             })) return 1;
         const int start = pih[p], len = pih[p + 1] - pih[p];
         if (len <= 0) continue;
-        if (c->nsym == IMP_NSYM_FAST)
-            hipLaunchKernelGGL(k_imp_dec_tables<true>, dim3((len + 63) / 64, B), dim3(64), 0, s, ImpDecTablesArgs{c->d_y, c->d_idx, start, len, c->d_tab, c->tab_pitch, H, W, c->nsym,
-                               c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0});
-        else
-            hipLaunchKernelGGL(k_imp_dec_tables<false>, dim3((len + 63) / 64, B), dim3(64), 0, s, ImpDecTablesArgs{c->d_y, c->d_idx, start, len, c->d_tab, c->tab_pitch, H, W, c->nsym,
-                               c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0});
+        imp_tables_launch(c->nsym, [&](auto fast) {
+            hipLaunchKernelGGL(k_imp_dec_tables<decltype(fast)::value>, dim3((len + 63) / 64, B), dim3(64), 0, s,
+                               ImpDecTablesArgs{c->d_y, c->d_idx, start, len, c->d_tab, c->tab_pitch, H, W, c->nsym, c->sk});
+        });
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_imp_dec_plane<false>, dim3(B), dim3(64), 0, s, ImpDecPlaneArgs{c->d_tab, c->tab_pitch, c->d_idx, start, len, c->d_state, bytes, cap, nbytes,
-                           c->d_x0, levels_out, H, W, c->nsym, c->sc, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0});
+                           c->d_x0, levels_out, H, W, c->nsym, c->sc, c->sk});
         LAUNCH_CHECK();
         if (mask_out) {
             // the latent mask of the map cells decoded in this plane (cells of later planes hold whatever the buffer held: nobody
@@ -1720,12 +1639,12 @@ LIC360_API int lic360_devcoder_decode(void *stream, const int *tables, int ncode
             hipLaunchKernelGGL(k_test_tab8, dim3((len + 63) / 64), dim3(64), 0, s, tables, mask, start, len, tab8, st);
             LAUNCH_CHECK();
             hipLaunchKernelGGL(k_dec_plane<true>, dim3(1), dim3(64), 0, s, DecPlaneArgs{tab8, chunk, (const int *)nullptr, (int)start, len, 0, st, bytes, cap, nbytes,
-                               (float *)nullptr, out, 0, 1, 1, 0, 0, 0, 0});
+                               (float *)nullptr, out, 0, 1, 1, DcLayout{}});
         } else {
             hipLaunchKernelGGL(k_test_tabn, dim3(len), dim3(64), 0, s, tables, ncode, start, len, tabn);
             LAUNCH_CHECK();
             hipLaunchKernelGGL(k_imp_dec_plane<true>, dim3(1), dim3(64), 0, s, ImpDecPlaneArgs{tabn, chunk, (const int *)nullptr, (int)start, len, st, bytes, cap, nbytes,
-                               (float *)nullptr, out, 0, 0, ncode, 0.0f});
+                               (float *)nullptr, out, 0, 0, ncode, 0.0f, DcLayout{}});
         }
         LAUNCH_CHECK();
     }
@@ -1790,10 +1709,10 @@ __global__ void k_fill_enc(float *buf, long planes, int H, int W, int hp, int wp
         buf[(i / ((long)H * W)) * hp * wp + e_cell(y, x, wp, off)] = v;
     }
 }
-__global__ void k_fill_dec(float *buf, long planes, int H, int W, int sk_rows, int sk_pitch, int row0, int col0, float v) {
+__global__ void k_fill_dec(float *buf, long planes, int H, int W, DcLayout sk, float v) {
     GRID_STRIDE(i, planes * H * W) {
         const int x = (int)(i % W), y = (int)((i / W) % H);
-        buf[(i / ((long)H * W)) * sk_rows * sk_pitch + (long)(y + x + row0) * sk_pitch + y + col0] = v;
+        buf[(i / ((long)H * W)) * sk.plane() + sk.cell(y, x)] = v;
     }
 }
 LIC360_API int lic360_codec_debug_fill(void *stream, lic360_codec *c, float value) {
@@ -1805,10 +1724,10 @@ LIC360_API int lic360_codec_debug_fill(void *stream, lic360_codec *c, float valu
         LAUNCH_CHECK();
     }
     for (int i = 0; i < 11; ++i) {
-        hipLaunchKernelGGL(k_fill_dec, dim3(lic360_blocks(3 * B * 4 * G * c->HW, 4)), dim3(256), 0, s, c->d_act[i], 3 * B * 4 * G, c->H, c->W, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0, value);
+        hipLaunchKernelGGL(k_fill_dec, dim3(lic360_blocks(3 * B * 4 * G * c->HW, 4)), dim3(256), 0, s, c->d_act[i], 3 * B * 4 * G, c->H, c->W, c->sk, value);
         LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_fill_dec, dim3(lic360_blocks(3 * B * 3 * G * c->HW, 4)), dim3(256), 0, s, c->d_y, 3 * B * 3 * G, c->H, c->W, c->sk_rows, c->sk_pitch, c->sk_row0, c->sk_col0, value);
+    hipLaunchKernelGGL(k_fill_dec, dim3(lic360_blocks(3 * B * 3 * G * c->HW, 4)), dim3(256), 0, s, c->d_y, 3 * B * 3 * G, c->H, c->W, c->sk, value);
     LAUNCH_CHECK();
     return 0;
 }
