@@ -93,14 +93,15 @@ LIC360_API int lic360_conv4_pack(void *stream, const lic360_conv_plan *p, const 
 // ------------------------------------------------------------------------------------------------ DC4
 #include "cconv4v6_dc.inc"
 
-// mode: bit 1 = no several-samples-per-wave packing, bits 2-3 = task granularity (4: one group per task always, 8: never; 0: by task count).
+// mode: bit 1 = no several-samples-per-wave packing, bits 2-3 = task granularity (4: one group per task always, 8: never; 0: by task count),
+// bit 4 = the first layer keeps one net per task.
 // Internal entry (hidden visibility) so that the fused codec passes the switches it read ONCE at create time.
 int lic360_cconv4_dc_plane_mode(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
                                 const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod, int mode) {
     ARG_CHECK(p && conv4_ok(p) && x && packed4 && bias && out && n > 0 && nb > 0 && n % nb == 0 && x_mod > 0 && x_mod <= n);
     if (psum < 0 || psum >= h + w + p->ngroup - 2) return 0;
     return launch_cconv4v6_dc((hipStream_t)stream, p, x, packed4, bias, act, residual, out, n, h, w, nb, psum, x_mod, (mode & 2) != 0,
-                              (mode >> 2) & 3);
+                              (mode >> 2) & 3, (mode & 16) != 0);
 }
 int lic360_cconv4_dc_plane_list(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
                                 const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod,
@@ -109,10 +110,11 @@ int lic360_cconv4_dc_plane_list(void *stream, const lic360_conv_plan *p, const f
     if (psum < 0 || psum >= h + w + p->ngroup - 2) return 0;
     return launch_cconv4v6_dc_list((hipStream_t)stream, p, x, packed4, bias, act, residual, out, n, h, w, nb, psum, x_mod, (const uint4 *)list, cnt, cap);
 }
-// LIC360_NOPACK / LIC360_DC_GSTEP force the schedule variants (both are tested against the oracle); read once per process, not per launch
+// LIC360_NOPACK / LIC360_DC_GSTEP force the schedule variants (both are tested against the oracle), LIC360_DC_NONETS the first layer's one-net-per-task
+// form (A/B runs); read once per process, not per launch
 int lic360_dc4_env_mode(void) {
     const char *gsm = getenv("LIC360_DC_GSTEP");                     // "1": one group per task always, "3": never (default: by task count)
-    return (getenv("LIC360_NOPACK") ? 2 : 0) | (gsm && gsm[0] == '1' ? 4 : (gsm && gsm[0] == '3' ? 8 : 0));
+    return (getenv("LIC360_NOPACK") ? 2 : 0) | (gsm && gsm[0] == '1' ? 4 : (gsm && gsm[0] == '3' ? 8 : 0)) | (getenv("LIC360_DC_NONETS") ? 16 : 0);
 }
 LIC360_API int lic360_cconv4_dc_plane(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
                                       const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod) {

@@ -228,10 +228,16 @@ LIC360_API int lic360_dc6_stamps(unsigned long long *host_out, int clear) {
 // LIST (round 6, need.h): the tasks of the launch come from a device-built list of records per XCD (lic360_dc_lists_build: the dead-cone skip -- every
 // sample's row window trimmed to the rows some coded symbol can observe, the windows packed like a tape's) instead of being derived from the plane's
 // geometry.  list: [8][a.tape_total] records, lcnt: [8] counts.  A LIST kernel is a TAPE kernel whose producer wave reads its records.
-template <int CIN, int CLS, bool SEG, bool LAT = false, bool TAPE = false, bool LIST = false>
+// NETS = 3 (first layer, cin = 1; throughput mode, H <= 64): the three stacked nets read the SAME input, so one task = (group block, image or tape of
+// images) carries all three: the band is fetched, staged and read from LDS once, the MFMAs, the tree and the epilogue run once per net, on that net's
+// accumulators (3 x 7) with that net's weights.  The launch then counts IMAGES: a.N = a.npb = a.x_mod = images, net k's weights / bias / slopes lie k nets
+// behind net 0's, its outputs k * a.npb samples behind.  Per accumulator the arithmetic is the one-net kernel's, in the same order.
+template <int CIN, int CLS, bool SEG, bool LAT = false, bool TAPE = false, bool LIST = false, int NETS = 1>
 __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, const uint4 *__restrict__ list, const int *__restrict__ lcnt, float *xs, float *comb,
                                          int (*trec)[16], int tid, int lane, int ps) {
     static_assert(!LIST || (TAPE && !SEG && !LAT), "list launches are throughput-mode launches of images of at most 64 rows");
+    static_assert(NETS == 1 || (NETS == 3 && CIN == 1 && !SEG && !LAT && !LIST), "three nets per task: the first layer in throughput mode");
+    constexpr int NA = NAcc<CIN>::value;
     constexpr int XQ = D6_XQ(CIN), XFL = D6_XFL(CIN);
     static_assert(XQ <= C4_THREADS, "one quad slot per thread");
     constexpr int XPLANE = D6_ROWS * D6_COLS;
@@ -241,7 +247,7 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
     const int gs = a.gstep;
     constexpr int TCS = CIN == 1 ? 4 : 1;                                // input groups per staged step (always 4 channel planes)
     const long SKP = (long)D3_SP(H, W) * HP, tcs = 4 * SKP;
-    f32x4 acc[NAcc<CIN>::value];
+    f32x4 acc[NETS * NA];
 #ifdef DC6_STAMP
     unsigned long long st[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = __builtin_amdgcn_s_memtime();
     const unsigned long long t_entry = t0;
@@ -497,15 +503,31 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
     };
     // weights of the double step starting at input group tc0: half h uses (a0, a1) / (b0, b1) as the two abid-indexed
     // registers (cin = 4) or a0..a3 / b0..b3 as the single register of its four input groups (cin = 1)
-    auto issue_w2 = [&](const char *p, int tc0, W8 &w) __attribute__((always_inline)) {
+    const long wnet_b = NETS > 1 ? (long)G * a.wblk * 4096 : 0;           // bytes from a net's packed weights to the next net's (NETS = 3)
+    auto issue_w2 = [&](const char *p, int tc0, W8 *ws) __attribute__((always_inline)) {
         (void)tc0;                                                          // (blocks past the last input group exist and hold zeros)
-        const f32x4 v = *(const f32x4 *)(p + offW);
-        w.a0 = v[0]; w.a1 = v[1];
-        if constexpr (CIN == 4) { w.b0 = v[2]; w.b1 = v[3]; }
-        else {
-            const f32x4 u = *(const f32x4 *)(p + offW + 4096);
-            w.a2 = v[2]; w.a3 = v[3];
-            w.b0 = u[0]; w.b1 = u[1]; w.b2 = u[2]; w.b3 = u[3];
+#pragma unroll
+        for (int net = 0; net < NETS; ++net) {
+            W8 &w = ws[net];
+            const f32x4 v = *(const f32x4 *)(p + net * wnet_b + offW);
+            w.a0 = v[0]; w.a1 = v[1];
+            if constexpr (CIN == 4) { w.b0 = v[2]; w.b1 = v[3]; }
+            else {
+                const f32x4 u = *(const f32x4 *)(p + net * wnet_b + offW + 4096);
+                w.a2 = v[2]; w.a3 = v[3];
+                w.b0 = u[0]; w.b1 = u[1]; w.b2 = u[2]; w.b3 = u[3];
+            }
+        }
+    };
+    // NETS = 3: one half (four input groups) of a double step's weights, every net's -- see the weight ring below
+    auto issue_wh = [&](const char *p, auto hh, W8 *ws) __attribute__((always_inline)) {
+        constexpr int hf = decltype(hh)::value;
+#pragma unroll
+        for (int net = 0; net < NETS; ++net) {
+            W8 &w = ws[net];
+            const f32x4 v = *(const f32x4 *)(p + net * wnet_b + offW + hf * 4096);
+            if constexpr (hf == 0) { w.a0 = v[0]; w.a1 = v[1]; w.a2 = v[2]; w.a3 = v[3]; }
+            else { w.b0 = v[0]; w.b1 = v[1]; w.b2 = v[2]; w.b3 = v[3]; }
         }
     };
     // register ring: two x sets of two quads, two weight sets; LDS ring: 2 D6_NB double-step buffers.  Double step d reads buffer d mod 2 NB;
@@ -516,10 +538,15 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
     constexpr int NB = D6_NB, NBUF = 2 * D6_NB;
     static_assert(NB == 1 || NB == 2, "one or two double steps per barrier");
     f32x4 xa0 = {0.f, 0.f, 0.f, 0.f}, xb0 = xa0, xa1 = xa0, xb1 = xa0;
-    W8 w0, w1;
+    // Weight ring.  NETS = 1: two sets, the set of double step d is refilled with double step d + 2 behind its last MFMA.  NETS = 3: 48 weight registers
+    // beside 84 accumulators do not fit the 168 registers of three waves per SIMD, so the ring is ONE set per net, refilled by halves: behind the first
+    // half of double step d its a-registers take the first half of double step d + 1, behind the second half the b-registers -- each load still has
+    // half a double step (three nets' MFMAs, ~2 700 cycles) to arrive.
+    W8 w0[NETS], w1[NETS];
+    const char *pw_one = nullptr;                                       // NETS = 3: where the weights of the next double step live
     int tcw;
     { const char *p = issue_x2(xa0, xb0, tcw); issue_w2(p, tcw, w0); }  // double step 0
-    { const char *p = issue_x2(xa1, xb1, tcw); issue_w2(p, tcw, w1); }  // double step 1
+    { const char *p = issue_x2(xa1, xb1, tcw); if constexpr (NETS == 1) issue_w2(p, tcw, w1); else pw_one = p; }  // double step 1
     if (hasA) { *(f32x4 *)ldsA = xa0; *(f32x4 *)(ldsA + XFL) = xb0; }
     int tcw_next, tcw_next2 = 0;
     const char *pw_next = issue_x2(xa0, xb0, tcw_next), *pw_next2 = nullptr;   // double step 2 (its weights are fetched in double step 0)
@@ -534,7 +561,7 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
     int n_lane = 0;                                                     // the sample this lane stores to (packed tasks: two per wave)
     // bias / PReLU slope / residual of the task are fetched when the task STARTS (unconditionally, from clamped
     // addresses): by the epilogue they are the oldest loads in flight, so waiting for them does not drain the ring.
-    float e_bias = 0.f, e_act = 0.f, e_res = 0.f;
+    float e_bias[NETS], e_act[NETS], e_res = 0.f;                       // (net k's output channels lie G * cout behind net k - 1's)
     long e_oi = 0;
     const float *const act_p = a.act ? a.act : a.bias, *const res_p = a.residual ? a.residual : a.x;
     const float *const xl0 = xs + (C4_PS - 1 - ps) * D6_COLS + lane;
@@ -573,13 +600,13 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
             sc = s < 0 ? 0 : (s >= S ? S - 1 : s);
         }
 #pragma unroll
-        for (int i = 0; i < NAcc<CIN>::value; ++i) acc[i] = zero4;
+        for (int i = 0; i < NETS * NA; ++i) acc[i] = zero4;
         tc = 0;
         const int nout = G * a.cout, gc = g < G ? g : G - 1;
         const int o = gc * a.cout + (CLS < a.cout ? CLS : a.cout - 1), bid = (n / a.npb) * nout + o;
         e_oi = ((long)n_lane * nout + o) * SKP + (long)(sc + D3_S0) * HP + row + D3_C0;
-        e_bias = a.bias[bid];
-        e_act = act_p[bid];
+#pragma unroll
+        for (int net = 0; net < NETS; ++net) { e_bias[net] = a.bias[bid + net * nout]; e_act[net] = act_p[bid + net * nout]; }
         e_res = res_p[a.residual ? e_oi : 0];
     };
     // The exchange buffer is double-buffered by task parity (round 6).  A task's partial sums are read AFTER the epilogue's barrier, and the next barrier
@@ -587,22 +614,34 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
     // its own epilogue -- and rewrote the single buffer -- while a slower wave was still reading the previous task's sums.  Needs two consecutive such tasks in
     // one workgroup: never with <= 32 of them per XCD (48 images), four workgroups per XCD with 96 images -- one image of a 96-image sub-batch decoded wrongly
     // in about one of four three-stream steps, with rounds 1-5's kernels as well (tools/debug/stress_big.py).
+    // NETS = 3: one exchange buffer PER NET instead of the pair.  Net k's sums of task t are read between barrier k of t's epilogue and the next barrier
+    // the reading wave arrives at; buffer k is written again at net k of task t + 1, by a wave that has passed the barrier in front of that write in its
+    // own program order -- barrier k - 1 of t + 1's epilogue (k > 0) or the last barrier before that epilogue (k = 0; barrier 2 of t's epilogue if no
+    // step barrier lies in between).  Either one comes AFTER barrier k + 1 (or, for k = 2, barrier 0 of the next epilogue) in every wave's program order,
+    // and a wave arrives at that only with its reads of buffer k behind it: whatever the length of a task and the parity of the step it starts on, two
+    // other nets' barriers lie between a read and the next write of the same buffer.
     auto epilogue = [&]() __attribute__((always_inline)) {
-        conv6_align<CIN, CLS>(acc);
-        const f32x4 part = tree4_eval<CIN, CLS>(acc);
-        float *const cb = CIN == 1 ? comb + (tq & 1) * C4_COMB_FLOATS : comb;   // (cin = 4 tasks are at least three double steps long: a step barrier always lies in between)
+        static_for<NETS>([&](auto nn) {
+            constexpr int net = decltype(nn)::value;
+            f32x4 *const ac = acc + net * NA;
+            conv6_align<CIN, CLS>(ac);
+            const f32x4 part = tree4_eval<CIN, CLS>(ac);
+            // (one net, cin = 4: tasks are at least three double steps long, a step barrier always lies in between)
+            float *const cb = NETS > 1 ? comb + net * C4_COMB_FLOATS : (CIN == 1 ? comb + (tq & 1) * C4_COMB_FLOATS : comb);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) cb[((ps * 4 + CLS) * 4 + r) * 64 + lane] = part[r];
-        __syncthreads();
-        const int r = CLS;
-        if (lane_ok && r < a.cout) {
-            const float f0 = cb[((ps * 4 + 0) * 4 + r) * 64 + lane], f1 = cb[((ps * 4 + 1) * 4 + r) * 64 + lane];
-            const float f2 = cb[((ps * 4 + 2) * 4 + r) * 64 + lane], f3 = cb[((ps * 4 + 3) * 4 + r) * 64 + lane];
-            float sv = ((f0 + f2) + (f1 + f3)) + e_bias;
-            if (a.act) { if (sv < 0) sv = sv * e_act; }                 // cconv_dc_cuda.cu:360-362
-            if (a.residual) sv = sv + e_res;                            // fused TileAdd
-            a.out[e_oi] = sv;
-        }
+            for (int r = 0; r < 4; ++r) cb[((ps * 4 + CLS) * 4 + r) * 64 + lane] = part[r];
+            __syncthreads();
+            const int r = CLS;
+            if (lane_ok && r < a.cout) {
+                const long oi = NETS > 1 ? e_oi + net * ((long)a.npb * G * a.cout * SKP) : e_oi;   // net k stores k * npb samples further
+                const float f0 = cb[((ps * 4 + 0) * 4 + r) * 64 + lane], f1 = cb[((ps * 4 + 1) * 4 + r) * 64 + lane];
+                const float f2 = cb[((ps * 4 + 2) * 4 + r) * 64 + lane], f3 = cb[((ps * 4 + 3) * 4 + r) * 64 + lane];
+                float sv = ((f0 + f2) + (f1 + f3)) + e_bias[net];
+                if (a.act) { if (sv < 0) sv = sv * e_act[net]; }        // cconv_dc_cuda.cu:360-362
+                if (a.residual) sv = sv + (NETS > 1 ? a.residual[oi] : e_res);   // fused TileAdd
+                a.out[oi] = sv;
+            }
+        });
     };
     task_setup();
     // one double step: barrier ; [operands + MFMAs of the first staged step] ; write the next double step's two quads to the
@@ -618,10 +657,13 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
             float r0[9];                                                                        \
             conv6_load<CIN, CLS, XPLANE>(r0, xl + (H_) * XFL + (J_) * XPLANE);                  \
             __builtin_amdgcn_sched_barrier(0);                                                  \
-            const float wa = W_.template get<(H_), (CIN == 4 ? 0 : (J_))>(), wb = W_.template get<(H_), 1>(); \
-            conv6_diags<CIN, CLS, 0, 3>(acc, r0, wa, wb);                                       \
-            if (dl > 4) conv6_diags<CIN, CLS, 4, 5>(acc, r0, wa, wb);                           \
-            if (dl > 6) conv6_diags<CIN, CLS, 6, 8>(acc, r0, wa, wb);                           \
+            static_for<NETS>([&](auto nn) {         /* the operands are read once for all nets */ \
+                constexpr int net = decltype(nn)::value;                                        \
+                const float wa = W_[net].template get<(H_), (CIN == 4 ? 0 : (J_))>(), wb = W_[net].template get<(H_), 1>(); \
+                conv6_diags<CIN, CLS, 0, 3>(acc + net * NA, r0, wa, wb);                        \
+                if (dl > 4) conv6_diags<CIN, CLS, 4, 5>(acc + net * NA, r0, wa, wb);            \
+                if (dl > 6) conv6_diags<CIN, CLS, 6, 8>(acc + net * NA, r0, wa, wb);            \
+            });                                                                                 \
         }                                                                                       \
     }
 #define DC6_HALF(H_, W_) DC6_SUB(H_, 0, W_) DC6_SUB(H_, 1, W_) DC6_SUB(H_, 2, W_) DC6_SUB(H_, 3, W_)
@@ -661,13 +703,15 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
         int tcw_new = 0;                                                                        \
         const char *pw_new = nullptr;                                                           \
         DC6_HALF(0, W_)                                                                         \
+        if constexpr (NETS > 1) issue_wh(pw_one, IC<0>{}, W_);                                  \
         DC6_T(2);                                                                               \
         D6_STAGE_MID(XA_, XB_)                                                                  \
         DC6_T(3);                                                                               \
         DC6_HALF(1, W_)                                                                         \
         D6_STAGE_END(XA_, XB_)                                                                  \
         DC6_T(4);                                                                               \
-        issue_w2(pw_next, tcw_next, W_);                                                        \
+        if constexpr (NETS > 1) { issue_wh(pw_one, IC<1>{}, W_); pw_one = pw_next; }            \
+        else issue_w2(pw_next, tcw_next, W_);                                                   \
         if constexpr (NB == 2) { pw_next = pw_next2; tcw_next = tcw_next2; pw_next2 = pw_new; tcw_next2 = tcw_new; } \
         else { pw_next = pw_new; tcw_next = tcw_new; }                                          \
         tc += 2 * TCS;                                                                          \
@@ -685,8 +729,13 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
     bool done = false;
     do {
         if constexpr (NB == 2) {
-            DC6_SUBSTEP(xa0, xb0, w0)                                   // double step = 0 (mod 2): stage double step + 2 = x set 0
-            DC6_SUBSTEP(xa1, xb1, w1)
+            if constexpr (NETS == 1) {
+                DC6_SUBSTEP(xa0, xb0, w0)                               // double step = 0 (mod 2): stage double step + 2 = x set 0
+                DC6_SUBSTEP(xa1, xb1, w1)
+            } else {
+                DC6_SUBSTEP(xa0, xb0, w0)                               // (one weight set: see the weight ring)
+                DC6_SUBSTEP(xa1, xb1, w0)
+            }
         } else {
             DC6_SUBSTEP(xa1, xb1, w0)                                   // double step = 0 (mod 2): stage double step + 1 = x set 1
             DC6_SUBSTEP(xa0, xb0, w1)
@@ -705,26 +754,26 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
 #undef DC6_SUBSTEP
 }
 
-template <int CIN, bool SEG, bool LAT, bool TAPE, bool LIST = false>
+template <int CIN, bool SEG, bool LAT, bool TAPE, bool LIST = false, int NETS = 1>
 __device__ __forceinline__ void dc6_kernel(const Dc3Packed &p, const Dc3Tape *tape, const uint4 *list = nullptr, const int *lcnt = nullptr) {
     __shared__ float xs[4 * D6_NB * D6_XFL(CIN)];
-    __shared__ float comb[2 * C4_COMB_FLOATS];                           // (two: task parity, see epilogue)
+    __shared__ float comb[(NETS > 1 ? NETS : 2) * C4_COMB_FLOATS];       // (two: task parity; three nets per task: one per net -- see epilogue)
     __shared__ int trec[8][16];
     const Dc3Args a = dc6_unpack(p);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), ps = wave >> 2, cls = wave & 3;
     switch (cls) {
-        case 0: dc6_body<CIN, 0, SEG, LAT, TAPE, LIST>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
-        case 1: dc6_body<CIN, 1, SEG, LAT, TAPE, LIST>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
-        case 2: dc6_body<CIN, 2, SEG, LAT, TAPE, LIST>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
-        default: dc6_body<CIN, 3, SEG, LAT, TAPE, LIST>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
+        case 0: dc6_body<CIN, 0, SEG, LAT, TAPE, LIST, NETS>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
+        case 1: dc6_body<CIN, 1, SEG, LAT, TAPE, LIST, NETS>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
+        case 2: dc6_body<CIN, 2, SEG, LAT, TAPE, LIST, NETS>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
+        default: dc6_body<CIN, 3, SEG, LAT, TAPE, LIST, NETS>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
     }
 }
-template <int CIN, bool SEG, bool LAT = false>
-__global__ __launch_bounds__(C4_THREADS) void k_cconv4v6(Dc3Packed p) { dc6_kernel<CIN, SEG, LAT, false>(p, nullptr); }
+template <int CIN, bool SEG, bool LAT = false, int NETS = 1>
+__global__ __launch_bounds__(C4_THREADS) void k_cconv4v6(Dc3Packed p) { dc6_kernel<CIN, SEG, LAT, false, false, NETS>(p, nullptr); }
 // the taped launches (throughput mode, H <= 64): 64 more bytes of arguments and the lane -> piece code only where a plane tapes
-template <int CIN>
-__global__ __launch_bounds__(C4_THREADS) void k_cconv4v6t(Dc3Packed p, Dc3Tape tape) { dc6_kernel<CIN, false, false, true>(p, &tape); }
+template <int CIN, int NETS = 1>
+__global__ __launch_bounds__(C4_THREADS) void k_cconv4v6t(Dc3Packed p, Dc3Tape tape) { dc6_kernel<CIN, false, false, true, false, NETS>(p, &tape); }
 // the list launches (dead-cone skip, need.h): 16 more bytes of arguments; p.tape_total = records per XCD the list has room for
 template <int CIN>
 __global__ __launch_bounds__(C4_THREADS) void k_cconv4v6l(Dc3Packed p, const uint4 *list, const int *lcnt) { dc6_kernel<CIN, false, false, true, true>(p, nullptr, list, lcnt); }
@@ -819,19 +868,36 @@ static bool dc6_schedule(Dc3Args &a, Dc3Tape &tape, int ngroup, int cin, int cou
     return true;
 }
 
+// The schedule of a launch.  The FIRST layer of three stacked nets over one input (cin = 1, nb = 3, x_mod * nb == n: sample i of every net reads image
+// i), in throughput mode on images of at most 64 rows, is scheduled over its n / 3 IMAGES -- per-XCD lists, tapes, records to produce -- and every task
+// runs the three nets (*nets = 3, dc6_body); the kernel then sees a one-net launch of n / 3 samples.  Whether a launch is a throughput-mode launch is
+// decided on its n samples, as for every other layer.  no_nets: keep one net per task (the A/B switch LIC360_DC_NONETS).
+static bool dc6_schedule_nets(Dc3Args &a, Dc3Tape &tape, int ngroup, int cin, int cout, int constrain, int n, int h, int w, int nb, int psum, int x_mod, bool nopack,
+                              int gstep_mode, bool no_nets, int *nets) {
+    *nets = 1;
+    if (!dc6_schedule(a, tape, ngroup, cin, cout, constrain, n, h, w, nb, psum, x_mod, nopack, gstep_mode)) return false;
+    if (no_nets || cin != 1 || nb != 3 || (long)x_mod * nb != n || a.gstep != C4_PS || a.nseg != 1) return true;
+    *nets = 3;
+    return dc6_schedule(a, tape, ngroup, cin, cout, constrain, n / nb, h, w, 1, psum, x_mod, nopack, 3);
+}
+
 static int launch_cconv4v6_dc(hipStream_t stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
                               const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod, bool nopack,
-                              int gstep_mode) {
+                              int gstep_mode, bool no_nets) {
     Dc3Args a;
     a.x = x; a.packed = packed4; a.wblk = conv4_wblk(p); a.bias = bias; a.act = act; a.residual = residual; a.out = out;
     // the packed tasks add per-lane 32-bit byte offsets of up to 16 samples to the task's base pointer (issue_setup)
     ARG_CHECK(16.0 * p->ngroup * p->cin * (double)D3_SP(h, w) * D3_HP(h) * 4.0 < 4294967296.0);
     ARG_CHECK(h < 32768 && w < 32768 && D6_NSEG(h) <= 15 && p->ngroup <= 127 && p->cout <= 7 && psum >= 0 && psum < 65536);   // the packed argument words (Dc3Packed)
     Dc3Tape tape;
-    if (!dc6_schedule(a, tape, p->ngroup, p->cin, p->cout, p->constrain, n, h, w, nb, psum, x_mod, nopack, gstep_mode)) return 0;
+    int nets;
+    if (!dc6_schedule_nets(a, tape, p->ngroup, p->cin, p->cout, p->constrain, n, h, w, nb, psum, x_mod, nopack, gstep_mode, no_nets, &nets)) return 0;
     const int gs = a.gstep;
     const Dc3Packed pk = dc6_pack(a);
-    if (a.nseg > 1) {
+    if (nets == 3) {                                                    // first layer, three nets per task
+        if (a.tape_c) hipLaunchKernelGGL((k_cconv4v6t<1, 3>), dim3(D6_GRID), dim3(C4_THREADS), 0, stream, pk, tape);
+        else hipLaunchKernelGGL((k_cconv4v6<1, false, false, 3>), dim3(D6_GRID), dim3(C4_THREADS), 0, stream, pk);
+    } else if (a.nseg > 1) {
         if (p->cin == 4) hipLaunchKernelGGL((k_cconv4v6<4, true>), dim3(D6_GRID), dim3(C4_THREADS), 0, stream, pk);
         else hipLaunchKernelGGL((k_cconv4v6<1, true>), dim3(D6_GRID), dim3(C4_THREADS), 0, stream, pk);
     } else if (a.tape_c) {
@@ -869,14 +935,16 @@ static int launch_cconv4v6_dc_list(hipStream_t stream, const lic360_conv_plan *p
 // Host-only view of the tape packing of one plane (no GPU work): what launch_cconv4v6_dc would put into the kernel's arguments for a layer of `ngroup`
 // groups (cin = 4: hidden / last layers, 1: first layer) over n samples of nb nets on plane psum.  *tape_c: samples per tape (0: the launch does not
 // tape); blocks[j] = first group of group block j (launch order, heaviest first), nwaves[j] = tasks per tape of block j, windows[(j * 6 + t) * 3 + i] =
-// piece i of wave t: k | slo << 3 | shi << 9 | a0 << 15 | 1 << 21 (0 = none).  Arrays of 24 / 24 / 24 * 6 * 3 entries: a bound for ngroup <= 64 (22 three-group blocks), independent of D6_TAPE_BLOCKS (a launch that would need more than
+// piece i of wave t: k | slo << 3 | shi << 9 | a0 << 15 | 1 << 21 (0 = none).  A first-layer launch that runs its three nets per task (cin = 1, nb = 3,
+// x_mod * 3 == n, throughput mode; dc6_schedule_nets) reports the schedule over its n / 3 images.  Arrays of 24 / 24 / 24 * 6 * 3 entries: a bound for ngroup <= 64 (22 three-group blocks), independent of D6_TAPE_BLOCKS (a launch that would need more than
 // D6_TAPE_BLOCKS = 16 blocks is not taped); *n_blocks <= 24.
 LIC360_API int lic360_dc4_tape_layout(int ngroup, int cin, int n, int nb, int h, int w, int psum, int x_mod, int *tape_c, int *n_blocks, int *blocks, int *nwaves, unsigned *windows) {
     ARG_CHECK(tape_c && n_blocks && blocks && nwaves && windows && ngroup > 0 && ngroup <= 64 && (cin == 1 || cin == 4) && n > 0 && nb > 0 && n % nb == 0 && h > 0 && w > 0 && x_mod > 0);
     Dc3Args a;
     *tape_c = 0; *n_blocks = 0;
     Dc3Tape tape;
-    if (!dc6_schedule(a, tape, ngroup, cin, 4, cin == 4 ? 6 : 5, n, h, w, nb, psum, x_mod, false, 0)) return 0;
+    int nets;                                                           // (a first-layer launch of three nets over one input: the schedule over its images)
+    if (!dc6_schedule_nets(a, tape, ngroup, cin, 4, cin == 4 ? 6 : 5, n, h, w, nb, psum, x_mod, false, 0, false, &nets)) return 0;
     *n_blocks = a.n_gbv < 24 ? a.n_gbv : 24;                            // (the arrays hold 24 entries; latency-mode schedules of ngroup > 24 one-group blocks are clamped)
     *tape_c = a.tape_c;
     for (int j = 0; j < 24 * 6 * 3; ++j) windows[j] = 0u;

@@ -1753,8 +1753,8 @@ LIC360_API int lic360_codec_debug_lists(lic360_codec *c, int which, void *host_o
 // to a row only if every kernel that entry names is listed here for the row's class (tests/test_abi.py checks each base name against the library's symbols)
 LIC360_API const char *lic360_codec_kernel_names(void) {
     return "ec_first=k_cconv16<1, false>;ec_hidden=k_cconv16s+k_cconv16<4, false>;ec_last=k_cconv16<4, true>;"
-           "dc_first=k_cconv4v6<1, false, false>+k_cconv4v6t<1>;"
-           "dc_hidden=k_cconv4v6l<4>+k_cconv4v6t<4>+k_cconv4v6<4, false, false>+k_cconv4v6<4, false, true>;"
-           "dc_last=k_cconv4v6l<4>+k_cconv4v6t<4>+k_cconv4v6<4, false, false>+k_cconv4v6<4, false, true>;"
+           "dc_first=k_cconv4v6t<1, 3>+k_cconv4v6<1, false, false, 3>+k_cconv4v6<1, false, false, 1>;"   // three nets per task; few images (latency mode): one
+           "dc_hidden=k_cconv4v6l<4>+k_cconv4v6t<4, 1>+k_cconv4v6<4, false, false, 1>+k_cconv4v6<4, false, true, 1>;"
+           "dc_last=k_cconv4v6l<4>+k_cconv4v6t<4, 1>+k_cconv4v6<4, false, false, 1>+k_cconv4v6<4, false, true, 1>;"
            "imp_ec=k_cconv144<1, false, 2>;imp_dc=k_cconv144<1, true, 2>+k_cconv144<1, true, 1>";
 }

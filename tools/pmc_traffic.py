@@ -10,9 +10,9 @@ import json
 import sys
 
 # (since round 5 the decode-order kernel has two names per layer type: k_cconv4v6t = the launches that tape-pack their samples, k_cconv4v6 = the others;
-#  a class sums over its kernels)
+#  a class sums over its kernels; both carry a trailing NETS template argument since the first layer runs its three nets per task: <1, 3>)
 # round 6: with the dead-cone lists (batches of >= 16 images) every cin = 4 decode-order launch is k_cconv4v6l<4>
-CLASSES = [("k_cconv4v6<4, false", "dc_hidden"), ("k_cconv4v6t<4>", "dc_hidden"), ("k_cconv4v6l<4>", "dc_hidden"), ("k_cconv4v6<1, false", "dc_first"), ("k_cconv4v6t<1>", "dc_first"),
+CLASSES = [("k_cconv4v6<4, false", "dc_hidden"), ("k_cconv4v6t<4", "dc_hidden"), ("k_cconv4v6l<4>", "dc_hidden"), ("k_cconv4v6<1, false", "dc_first"), ("k_cconv4v6t<1", "dc_first"),
            ("k_cconv16s", "ec_hidden"), ("k_cconv16<4, false>", "ec_hidden"),
            ("k_cconv16<4, true>", "ec_last"), ("k_cconv16<1, false>", "ec_first"), ("k_cconv144<1, true", "imp_dc"), ("k_cconv144<1, false", "imp_ec"), ("k_imp_dc_map", "imp_dc_fused")]
 out_json, images = sys.argv[1], int(sys.argv[2])
