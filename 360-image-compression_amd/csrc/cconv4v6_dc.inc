@@ -210,6 +210,9 @@ struct W8 {
 // rows outside the image (first segment, and the last one where it ends with the image).
 #define D6_SEG_STEP 60
 #define D6_NSEG(h) ((h) <= 64 ? 1 : 1 + ((h) - 62 + D6_SEG_STEP - 1) / D6_SEG_STEP)
+// rows of a piece word (need.h): six bits each, and a seventh at bits 25 / 26 on latents taller than a wave (TALL)
+template <bool TALL> __device__ __forceinline__ int dc6_piece_slo(unsigned wd) { if constexpr (TALL) return dcl_piece_slo(wd); else return (wd >> 3) & 63; }
+template <bool TALL> __device__ __forceinline__ int dc6_piece_shi(unsigned wd) { if constexpr (TALL) return dcl_piece_shi(wd); else return (wd >> 9) & 63; }
 #ifdef DC6_STAMP
 // diagnostic build only (tools/dc6_stamp.sh): cycles per phase of the decode-order hidden-layer instantiation, summed per wave over the launches
 __device__ unsigned long long dc6_stamps[256 * 12 * 10];
@@ -232,10 +235,20 @@ LIC360_API int lic360_dc6_stamps(unsigned long long *host_out, int clear) {
 // images) carries all three: the band is fetched, staged and read from LDS once, the MFMAs, the tree and the epilogue run once per net, on that net's
 // accumulators (3 x 7) with that net's weights.  The launch then counts IMAGES: a.N = a.npb = a.x_mod = images, net k's weights / bias / slopes lie k nets
 // behind net 0's, its outputs k * a.npb samples behind.  Per accumulator the arithmetic is the one-net kernel's, in the same order.
-template <int CIN, int CLS, bool SEG, bool LAT = false, bool TAPE = false, bool LIST = false, int NETS = 1>
+// TALL (LIST only; latents of 65..128 rows): the list's pieces carry seven-bit rows (need.h: dcl_piece) and every record is packed.  Nothing else differs
+// from the list kernel of the short latents: a piece already sits at a lane of its own (a0) and fetches the 68-column window of the padded rows that
+// starts at its own row base (band column c <- padded column slo + c - a0), and HP = H + 4 = 132 is only the row pitch of that fetch.
+// The shifts.  A stored lane li of a piece (a0 <= li <= a0 + shi - slo) takes the partial sum of tap kh from source lane li + sh, sh = kh - k0 in
+// [-2, 2], which read band column li + sh + k0 with -sh <= k0 <= 4 - sh: columns li .. li + 4, all inside the piece's own a0 .. a0 + rows + 3, which
+// issue_setup fetches from the piece's own sample whole -- the two rows on either side of a cut included (the next wave's piece fetches them again).
+// The source lane itself must exist in the wave: a0 >= 2 unless the piece starts with image row 0, last lane <= 61 unless it ends with row H - 1 (what
+// would come from lanes -2, -1, 64, 65 there are products with the zero rows around the image).  A piece cut in mid-image has real rows on both sides
+// and therefore always keeps lanes 0, 1 / 62, 63 free: dcl_wave_pieces cuts at lane 61 and restarts at lane 2 whatever the image's height.
+template <int CIN, int CLS, bool SEG, bool LAT = false, bool TAPE = false, bool LIST = false, int NETS = 1, bool TALL = false>
 __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, const uint4 *__restrict__ list, const int *__restrict__ lcnt, float *xs, float *comb,
                                          int (*trec)[16], int tid, int lane, int ps) {
-    static_assert(!LIST || (TAPE && !SEG && !LAT), "list launches are throughput-mode launches of images of at most 64 rows");
+    static_assert(!LIST || (TAPE && !SEG && !LAT), "list launches are throughput-mode launches whose lanes are placed by their records, not by row segments");
+    static_assert(!TALL || (LIST && CIN == 4 && NETS == 1), "seven-bit rows: the list kernel of the hidden / last layers");
     static_assert(NETS == 1 || (NETS == 3 && CIN == 1 && !SEG && !LAT && !LIST), "three nets per task: the first layer in throughput mode");
     constexpr int NA = NAcc<CIN>::value;
     constexpr int XQ = D6_XQ(CIN), XFL = D6_XFL(CIN);
@@ -316,7 +329,7 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
             n = (int)(r.x >> 10);
             s0 = a.psum - g0;
             seg = 0;
-            if ((r.x >> 7) & 7u) { seg = (int)(r.y & 0x3fffffu); nb2 = (int)r.z; prb = (int)r.w; packed = 4; }
+            if ((r.x >> 7) & 7u) { seg = (int)(r.y & (TALL ? 0xfe3fffffu : 0x3fffffu)); nb2 = (int)r.z; prb = (int)r.w; packed = 4; }   // (without the live-group bits)
             packed |= (int)((r.y >> 22) & 7u) << 4;                         // bits 4..6: which of the block's three groups are live somewhere in the record's rows
         } else if constexpr (!SEG) {
             int j = 0, rem = u;
@@ -441,7 +454,7 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
 #pragma unroll
                 for (int wi = 0; wi < 3; ++wi) {
                     const unsigned wd = (unsigned)(wi == 0 ? iseg : (wi == 1 ? inb : iprb));
-                    const int k = wd & 7, slo = (wd >> 3) & 63, shi = (wd >> 9) & 63, a0 = (wd >> 15) & 63;
+                    const int k = wd & 7, slo = dc6_piece_slo<TALL>(wd), shi = dc6_piece_shi<TALL>(wd), a0 = (wd >> 15) & 63;
                     const bool in = (wd >> 21) != 0 && 4 * qc + 3 >= a0 && 4 * qc <= a0 + (shi - slo) + 4;   // lanes a0 .. a0 + rows - 1 read columns up to lane + 4
                     if (in) { sh = (unsigned)k * stride8 + (unsigned)((slo - a0) * 4); cov = true; }
                 }
@@ -582,7 +595,7 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
 #pragma unroll
             for (int wi = 0; wi < 3; ++wi) {
                 const unsigned wd = (unsigned)(wi == 0 ? seg : (wi == 1 ? nb2 : prb));
-                const int k = wd & 7, slo = (wd >> 3) & 63, shi = (wd >> 9) & 63, a0 = (wd >> 15) & 63;
+                const int k = wd & 7, slo = dc6_piece_slo<TALL>(wd), shi = dc6_piece_shi<TALL>(wd), a0 = (wd >> 15) & 63;
                 if ((wd >> 21) != 0 && lane >= a0 && lane <= a0 + (shi - slo)) { half_ok = true; row = slo + lane - a0; n_lane = n + 8 * k; }
             }
         } else if (SEG && PACK && packed) {                             // lanes 0..27: sample n, lanes 36..63: sample nb2
@@ -754,7 +767,7 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
 #undef DC6_SUBSTEP
 }
 
-template <int CIN, bool SEG, bool LAT, bool TAPE, bool LIST = false, int NETS = 1>
+template <int CIN, bool SEG, bool LAT, bool TAPE, bool LIST = false, int NETS = 1, bool TALL = false>
 __device__ __forceinline__ void dc6_kernel(const Dc3Packed &p, const Dc3Tape *tape, const uint4 *list = nullptr, const int *lcnt = nullptr) {
     __shared__ float xs[4 * D6_NB * D6_XFL(CIN)];
     __shared__ float comb[(NETS > 1 ? NETS : 2) * C4_COMB_FLOATS];       // (two: task parity; three nets per task: one per net -- see epilogue)
@@ -763,10 +776,10 @@ __device__ __forceinline__ void dc6_kernel(const Dc3Packed &p, const Dc3Tape *ta
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), ps = wave >> 2, cls = wave & 3;
     switch (cls) {
-        case 0: dc6_body<CIN, 0, SEG, LAT, TAPE, LIST, NETS>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
-        case 1: dc6_body<CIN, 1, SEG, LAT, TAPE, LIST, NETS>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
-        case 2: dc6_body<CIN, 2, SEG, LAT, TAPE, LIST, NETS>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
-        default: dc6_body<CIN, 3, SEG, LAT, TAPE, LIST, NETS>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
+        case 0: dc6_body<CIN, 0, SEG, LAT, TAPE, LIST, NETS, TALL>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
+        case 1: dc6_body<CIN, 1, SEG, LAT, TAPE, LIST, NETS, TALL>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
+        case 2: dc6_body<CIN, 2, SEG, LAT, TAPE, LIST, NETS, TALL>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
+        default: dc6_body<CIN, 3, SEG, LAT, TAPE, LIST, NETS, TALL>(a, tape, list, lcnt, xs, comb, trec, tid, lane, ps); break;
     }
 }
 template <int CIN, bool SEG, bool LAT = false, int NETS = 1>
@@ -777,6 +790,9 @@ __global__ __launch_bounds__(C4_THREADS) void k_cconv4v6t(Dc3Packed p, Dc3Tape t
 // the list launches (dead-cone skip, need.h): 16 more bytes of arguments; p.tape_total = records per XCD the list has room for
 template <int CIN>
 __global__ __launch_bounds__(C4_THREADS) void k_cconv4v6l(Dc3Packed p, const uint4 *list, const int *lcnt) { dc6_kernel<CIN, false, false, true, true>(p, nullptr, list, lcnt); }
+// ... of latents of 65..128 rows (TALL: seven-bit rows in the pieces, every record packed)
+template <int CIN>
+__global__ __launch_bounds__(C4_THREADS) void k_cconv4v6lt(Dc3Packed p, const uint4 *list, const int *lcnt) { dc6_kernel<CIN, false, false, true, true, 1, true>(p, nullptr, list, lcnt); }
 
 // TAPE packing (see Dc3Args), host side: per group block of the launch, the row windows of tape_c consecutive samples of an XCD's list laid end to
 // end over as few waves as the kernel's rules allow -- a window piece stores rows slo..shi in lanes a0.. with (a0 - slo) % 4 == 0 (16-byte aligned band
@@ -911,7 +927,7 @@ static int launch_cconv4v6_dc(hipStream_t stream, const lic360_conv_plan *p, con
 }
 
 // The same plane over a device-built task list (lic360_dc_lists_build: [8][cap] records + [8] counts of THIS layer and plane).  Throughput-mode launches
-// of images of at most 64 rows only (the list's records are three-group tasks with tape pieces); cin = 4.
+// of images of at most DCL_MAX_H = 128 rows only (the list's records are three-group tasks with tape pieces; taller than a wave: k_cconv4v6lt); cin = 4.
 static int launch_cconv4v6_dc_list(hipStream_t stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
                                    const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod,
                                    const uint4 *list, const int *lcnt, int cap) {
@@ -919,15 +935,17 @@ static int launch_cconv4v6_dc_list(hipStream_t stream, const lic360_conv_plan *p
     a.x = x; a.packed = packed4; a.wblk = conv4_wblk(p); a.bias = bias; a.act = act; a.residual = residual; a.out = out;
     // a record's pieces add per-lane 32-bit byte offsets of up to 8 * (DCL_CHUNK - 1) samples to the task's base pointer (issue_setup)
     ARG_CHECK(64.0 * p->ngroup * p->cin * (double)D3_SP(h, w) * D3_HP(h) * 4.0 < 4294967296.0);
-    ARG_CHECK(h <= 64 && w < 32768 && p->ngroup <= 127 && p->cout <= 7 && psum >= 0 && psum < 65536 && p->cin == 4 && list && lcnt && cap > 0);
+    ARG_CHECK(h <= DCL_MAX_H && w < 32768 && p->ngroup <= 127 && p->cout <= 7 && psum >= 0 && psum < 65536 && p->cin == 4 && list && lcnt && cap > 0);
     ARG_CHECK(n % 8 == 0 && (n / nb) % 8 == 0 && x_mod == n);           // XCD lists hold whole nets' samples; the samples of a record are 8 apart and never wrap
     Dc3Tape tape;
     if (!dc6_schedule(a, tape, p->ngroup, p->cin, p->cout, p->constrain, n, h, w, nb, psum, x_mod, true, 3)) return 0;
-    ARG_CHECK(a.gstep == C4_PS && a.nseg == 1);
+    ARG_CHECK(a.gstep == C4_PS && a.nseg == D6_NSEG(h));
+    a.nseg = 1;                                                         // (a list kernel knows no row segments: its records place every lane)
     a.tape_c = 1;                                                       // (a taped kernel: any non-zero value)
     a.tape_total = cap;
     const Dc3Packed pk = dc6_pack(a);
-    hipLaunchKernelGGL((k_cconv4v6l<4>), dim3(D6_GRID), dim3(C4_THREADS), 0, stream, pk, list, lcnt);
+    if (h > 64) hipLaunchKernelGGL((k_cconv4v6lt<4>), dim3(D6_GRID), dim3(C4_THREADS), 0, stream, pk, list, lcnt);
+    else hipLaunchKernelGGL((k_cconv4v6l<4>), dim3(D6_GRID), dim3(C4_THREADS), 0, stream, pk, list, lcnt);
     LAUNCH_CHECK();
     return 0;
 }

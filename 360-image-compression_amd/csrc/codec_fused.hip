@@ -145,8 +145,9 @@ struct lic360_codec {
     int tab_pitch = 0;
     // Dead-cone skip (round 6, need.h): outputs no coded symbol can observe are not computed -- per-layer need maps from the mask, compacted task lists
     // for the encode-order kernels (layers 1..11), per-plane task records for the decode-order kernel (layers 1..11; batches of >= 16 images with
-    // 8 | batch on images of at most 64 rows -- below that a list could only drop whole three-group tasks, which almost never happens, and the decode
-    // would have to wait for the whole importance map instead of running behind it).  LIC360_NOSKIP=1 (read at create) turns it off.
+    // 8 | batch on images of at most 128 rows -- below that a list could only drop whole three-group tasks, which almost never happens, and the decode
+    // would have to wait for the whole importance map instead of running behind it).  LIC360_NOSKIP=1 (read at create) turns it off;
+    // LIC360_DC_NOTALL=1 keeps the decode-order lists to images of at most 64 rows.
     bool skip = false;
     DevBuf<signed char> need, need_d, tmax;
     lic360_ec_lists ecl;                       // views of ecl_list / ecl_cnt and dcl_list / dcl_cnt for the launchers
@@ -969,9 +970,12 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
         if ((size_t)c->ecl.cap < cap11) c->ecl.cap = (int)cap11;
         if (c->ecl_list.alloc((size_t)NEED_LAYERS * 8 * c->ecl.cap) || c->ecl_cnt.alloc((size_t)NEED_LAYERS * 8)) return 1;
         c->ecl.list = c->ecl_list; c->ecl.cnt = c->ecl_cnt;
-        if (h <= 64 && max_batch % 8 == 0 && max_batch >= 16 && max_batch <= 512 && ngroup <= 72) {
+        // decode-order lists: latents of at most 128 rows (taller than a wave: up to three records per sample, need.h; LIC360_DC_NOTALL=1, read here,
+        // keeps those on the row-segment kernels -- the A/B switch of the tall lists)
+        const int h_max = getenv("LIC360_DC_NOTALL") ? 64 : DCL_MAX_H;
+        if (h <= h_max && max_batch % 8 == 0 && max_batch >= 16 && max_batch <= 512 && ngroup <= 72) {
             c->dcl.P = c->P;
-            c->dcl.cap = (int)(((G + 2) / 3) * 3 * (B / 8));
+            c->dcl.cap = (int)(((G + 2) / 3) * 3 * (B / 8) * DCL_WAVES_PER_WINDOW(h));
             if (c->dcl_list.alloc((size_t)NEED_LAYERS * c->P * 8 * c->dcl.cap) || c->dcl_cnt.alloc((size_t)NEED_LAYERS * c->P * 8)) return 1;
             c->dcl.list = c->dcl_list; c->dcl.cnt = c->dcl_cnt;
         }

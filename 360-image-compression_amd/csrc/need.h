@@ -20,7 +20,22 @@
 // record = uint4: x = g0 | packed << 7 | n << 10   (packed 4: up to three pieces y / z / w, sample n + 8 k each; packed 0: sample n, whole diagonals);
 //                 bits 22..24 of y: which of the block's three groups g0, g0 + 1, g0 + 2 are live on some row of the record (the others' wave sets idle)
 // piece  = k | slo << 3 | shi << 9 | a0 << 15 | 1 << 21   (rows slo..shi of sample k of the chunk in lanes a0.., as the tape's pieces)
+// Latents of 65..128 rows ("tall"): a row has seven bits.  The six low bits stay where they are, bit 6 of slo is bit 25 of the piece word, bit 6 of shi
+// bit 26 -- a piece of a latent of at most 64 rows is the word it always was, and the kernel of those latents decodes it with the instructions it always
+// had.  Every live block of a tall latent is packed (a whole image does not fit a wave, so there is no plain record); a window of up to 128 rows is cut
+// over two or three waves by the same rule that cuts a 64-row window over two.
 #define DCL_CHUNK 8                        // samples per packing chunk (k has 3 bits)
+#define DCL_MAX_H 128                      // tallest latent the lists pack
+__host__ __device__ inline unsigned dcl_piece(int k, int slo, int shi, int a0) {
+    return (unsigned)k | (unsigned)(slo & 63) << 3 | (unsigned)(shi & 63) << 9 | (unsigned)a0 << 15 | 1u << 21 | (unsigned)(slo >> 6) << 25 | (unsigned)(shi >> 6) << 26;
+}
+__host__ __device__ inline int dcl_piece_slo(unsigned w) { return (int)((w >> 3) & 63u) | (int)((w >> 25) & 1u) << 6; }
+__host__ __device__ inline int dcl_piece_shi(unsigned w) { return (int)((w >> 9) & 63u) | (int)((w >> 26) & 1u) << 6; }
+// Waves that can START with a piece of one window of an image of h rows: a wave's first piece begins at lane a0 <= 5 and, unless it ends its window,
+// is cut at lane 61 -- it holds at least 57 rows.  So a window of r rows is the first piece of at most 1 + (r - 1) / 57 waves, every wave has exactly
+// one first piece, and the waves of a chunk of c windows number at most c times that: the records a list must have room for, per sample.
+// (At most 64 rows: a block whose packing needs more waves than it has live samples keeps one plain record per sample instead.)
+#define DCL_WAVES_PER_WINDOW(h) ((h) <= 64 ? 1 : 1 + ((h) - 1) / 57)
 
 // The pieces of ONE wave: cconv4v6_dc.inc's dc6_wave_pieces with a row window PER SAMPLE (lo[k]..hi[k], hi < lo: nothing of that sample
 // is live on this plane).  Same rules: (a0 - slo) % 4 == 0; the next piece starts in the quad behind this piece's last band column (last lane + 4);
@@ -38,7 +53,7 @@ __host__ __device__ inline int dcl_wave_pieces(const int *lo, const int *hi, int
         int shi = hi[k];
         if (a0 + (hi[k] - slo) > top) shi = slo + (61 - a0);               // cut
         if (a0 > 61 || (shi < hi[k] && (a0 > 57 || shi - slo + 1 < 4))) break;   // no room (for a useful piece of a cut window)
-        out[nwin++] = (unsigned)k | (unsigned)slo << 3 | (unsigned)shi << 9 | (unsigned)a0 << 15 | 1u << 21;
+        out[nwin++] = dcl_piece(k, slo, shi, a0);
         pos = ((a0 + (shi - slo) + 4) / 4 + 1) * 4;
         slo = shi + 1;
         if (slo > hi[k]) { ++k; if (k < c) slo = lo[k]; }

@@ -263,8 +263,8 @@ __global__ __launch_bounds__(128) void k_dc_tasks(const DcListArgs a) {
             unsigned pc[3];
             while (k < c && dcl_wave_pieces(lo, hi, H, c, k, slo, pc) > 0) ++packed;
         }
-        plain[j] = packed >= live;
-        nrec[j] = packed < live ? packed : live;
+        plain[j] = H <= 64 ? packed >= live : live == 0;                    // (taller than a wave: no whole-image task, every live block is packed)
+        nrec[j] = plain[j] ? live : packed;
     }
     __syncthreads();
     if (tid == 0) {
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(128) void k_dc_tasks(const DcListArgs a) {
                     for (int i = 0; i < 3; ++i) if (pc[i]) gm |= wgm[j][c0 + (pc[i] & 7)];
                     if (o < a.cap) out[o] = make_uint4((unsigned)g0 | 4u << 7 | (unsigned)nb << 10, pc[0] | gm << 22, pc[1], pc[2]);
                     ++o;
-                    for (int i = 0; i < 3; ++i) if (pc[i]) count((pc[i] >> 3) & 63, (pc[i] >> 9) & 63, (int)gm);
+                    for (int i = 0; i < 3; ++i) if (pc[i]) count(dcl_piece_slo(pc[i]), dcl_piece_shi(pc[i]), (int)gm);
                 }
             }
         }
@@ -359,8 +359,8 @@ __global__ __launch_bounds__(64) void k_dc_balance(const DcListArgs a) {
 
 // layers 1..11 (cin = 4: hidden and last layers; the first layer keeps its full task list)
 int lic360_dc_lists_build(void *stream, const signed char *need_d, int B, int G, int H, int W, const lic360_dc_lists &l, unsigned long long *stats) {
-    ARG_CHECK(need_d && l.list && l.cnt && B > 0 && B % 8 == 0 && B / 8 <= DCL_MAXM && H <= 64 && G <= 3 * DCL_MAXB && l.P == H + W + G - 2);
-    ARG_CHECK(l.cap >= ((G + 2) / 3 < DCL_MAXB ? (G + 2) / 3 : DCL_MAXB) * 3 * (B / 8) && 3L * B < (1L << 22));
+    ARG_CHECK(need_d && l.list && l.cnt && B > 0 && B % 8 == 0 && B / 8 <= DCL_MAXM && H <= DCL_MAX_H && G <= 3 * DCL_MAXB && l.P == H + W + G - 2);
+    ARG_CHECK(l.cap >= ((G + 2) / 3 < DCL_MAXB ? (G + 2) / 3 : DCL_MAXB) * 3 * (B / 8) * DCL_WAVES_PER_WINDOW(H) && 3L * B < (1L << 22));
     DcListArgs a;
     a.need_d = need_d; a.list = l.list; a.cnt = l.cnt; a.stats = stats; a.cap = l.cap; a.l0 = 1; a.npb = B; a.G = G; a.H = H; a.W = W; a.P = l.P;
     hipLaunchKernelGGL(k_dc_tasks, dim3(8, l.P, NEED_LAYERS - 1), dim3(128), 0, (hipStream_t)stream, a);
@@ -387,15 +387,16 @@ LIC360_API int lic360_need_maps(void *stream, const float *mask, int B, int G, i
 }
 
 // Host-only view of the list packing (no GPU work): the waves into which dcl_wave_pieces lays the row windows lo[k]..hi[k] (k < c <= 8; hi < lo: sample k
-// has no live row) of ONE chunk of samples on an image of h rows; pieces[3 w + i] = piece i of wave w (k | slo << 3 | shi << 9 | a0 << 15 | 1 << 21, 0 = none),
-// room for 3 * 2 * c words; *n_waves = waves used.  For tests of the packing rules on the CPU (tests/test_dcl_pack.py).
+// has no live row) of ONE chunk of samples on an image of h <= 128 rows; pieces[3 w + i] = piece i of wave w (need.h: dcl_piece, 0 = none), room for
+// 3 * 2 * c words (h <= 64) or 3 * 3 * c words (taller: DCL_WAVES_PER_WINDOW waves per sample); *n_waves = waves used.  For tests of the packing rules
+// on the CPU (tests/test_dcl_pack.py, tests/test_dc_tall_cpu.py).
 LIC360_API int lic360_dcl_pack_layout(int h, int c, const int *lo, const int *hi, unsigned *pieces, int *n_waves) {
-    ARG_CHECK(h > 0 && h <= 64 && c > 0 && c <= DCL_CHUNK && lo && hi && pieces && n_waves);
+    ARG_CHECK(h > 0 && h <= DCL_MAX_H && c > 0 && c <= DCL_CHUNK && lo && hi && pieces && n_waves);
     for (int k = 0; k < c; ++k) ARG_CHECK(hi[k] < lo[k] || (lo[k] >= 0 && hi[k] < h));
     int k = 0, slo = lo[0], nw = 0;
     unsigned pc[3];
     while (k < c && dcl_wave_pieces(lo, hi, h, c, k, slo, pc) > 0) {
-        ARG_CHECK(nw < 2 * c);
+        ARG_CHECK(nw < (h <= 64 ? 2 : DCL_WAVES_PER_WINDOW(h)) * c);
         for (int i = 0; i < 3; ++i) pieces[3 * nw + i] = pc[i];
         ++nw;
     }

@@ -149,7 +149,8 @@ class FusedCodec(_FusedBase):
     # ---- dead-cone skip (csrc/need.h): statistics and test hooks ---------------------------------------
     def skip_active(self):
         """0: this codec computes every output (generic kernels or LIC360_NOSKIP); 1: the encode-order launches skip dead (tile, group block)
-        pairs; 2: the decode-order launches of batches of >= 16 images (8 | batch) skip dead rows as well"""
+        pairs; 2: the decode-order launches of batches of >= 16 images (8 | batch) skip dead rows as well -- latents of at most 128 rows (a codec
+        created under LIC360_DC_NOTALL=1: at most 64; taller ones then decode on the row-segment kernels and report 1)"""
         act = C.c_int(0)
         _chk(_lib.lic360_codec_skip_stats(self._h, -1, None, C.byref(act)))
         return act.value

@@ -426,13 +426,14 @@ int lic360_codec_set_coder(lic360_codec *codec, int mode);
  * Bitstreams and decoded symbols are unchanged.  lic360_need_maps: masks [b, g, h, w] -> need [b][12][h][w] int8 (device), the kernel the codec runs. */
 int lic360_need_maps(void *stream, const float *mask, int b, int g, int h, int w, signed char *need_out);
 /* Host-only (no GPU work): how the decode-order task lists pack the live row windows lo[k]..hi[k] (k < c <= 8 samples of one chunk; hi < lo: none) of an
- * image of h <= 64 rows into waves -- round 5's tape rules with a window per sample; pieces[3 w + i] = piece i of wave w
- * (k | slo << 3 | shi << 9 | a0 << 15 | 1 << 21, 0 = none; room for 6 c words), *n_waves = waves used.  tests/test_dcl_pack.py. */
+ * image of h <= 128 rows into waves -- round 5's tape rules with a window per sample; pieces[3 w + i] = piece i of wave w
+ * (k | (slo & 63) << 3 | (shi & 63) << 9 | a0 << 15 | 1 << 21 | (slo >> 6) << 25 | (shi >> 6) << 26, 0 = none; room for 6 c words, 9 c words where
+ * h > 64: a window taller than a wave is cut over up to three), *n_waves = waves used.  tests/test_dcl_pack.py, tests/test_dc_tall_cpu.py. */
 int lic360_dcl_pack_layout(int h, int c, const int *lo, const int *hi, unsigned *pieces, int *n_waves);
 /* enable > 0: the following encodes / decodes count what they execute (0: stop; < 0: leave as it is).  out (host, 2 * 12 * 64 values, may be NULL; reading clears):
  * [0][layer][group block] live (tile, group block) pairs of the encode-order launches (64 positions x the block's groups, per sample),
  * [1][layer][group] cells the decode-order launches stored.  *skip_active_out (may be NULL): 0 the codec does not skip (generic kernels or
- * LIC360_NOSKIP), 1 encode order only, 2 both orders (decode order: batches of >= 16 images, 8 | batch, h <= 64). */
+ * LIC360_NOSKIP), 1 encode order only, 2 both orders (decode order: batches of >= 16 images, 8 | batch, h <= 128; LIC360_DC_NOTALL=1 at create: h <= 64). */
 int lic360_codec_skip_stats(lic360_codec *codec, int enable, unsigned long long *out, int *skip_active_out);
 /* test hooks: every interior cell of the codec's activation buffers <- value (finite); what the last encode / decode scheduled
  * (which 0: need maps, 1 / 2: encode-order list counts / entries, 3 / 4: decode-order list counts / records; see csrc/codec_fused.hip) */
