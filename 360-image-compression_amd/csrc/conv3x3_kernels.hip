@@ -19,7 +19,7 @@
 // packed in exactly this order, one pair ahead) for 9 RW MFMAs: 0.26 operand fetches per MFMA.  LDS plane pitch 336 = 16 (mod 64)
 // banks: the four k-planes of a B read fall on disjoint bank quarters.
 //
-// Stride 2 (k_sconv3x3s2, fp32 form only; lic360_sconv3x3s2 / lic360_sconv1x1s2).  Replaces SpherePad(2) + nn.Conv2d(c, c', 3, 2, 3) + nn.PReLU + SphereTrim of
+// Stride 2 (k_sconv3x3s2, the fp32 form; lic360_sconv3x3s2 / lic360_sconv1x1s2).  Replaces SpherePad(2) + nn.Conv2d(c, c', 3, 2, 3) + nn.PReLU + SphereTrim of
 // test/model_zoo.py:64-106 (ResidualBlockDown.conv1, SphereConv2) and nn.Conv2d(c, c', 1, 2, 2) + the block's add (ResidualBlockDown.short_cut).  A tile is
 // 16 x 16 cells of the OUTPUT's interior; the output has its own grid, and the residual has the output's geometry.  3x3: the halo is 33 x 33 cells per
 // channel (output (r, col) at tap (kh, kw) reads halo cell (2 r + kh, 2 col + kw)), 2 RW + 1 B operands per pair for the same 72 MFMAs.  Decisions:
@@ -31,6 +31,8 @@
 //            would put every plane on the even banks.)
 //   1x1      the loader fetches the even / even cells only: LDS image, reads and waits are the stride-1 1x1's.
 // The weight packs are the stride-1 ones.  The stride-1 instantiations compile to the instructions they had before the stride parameter existed.
+// The single-pass bf16 form of the pair (k_sconv_b1s2; lic360_sconv3x3s2_bf16x1 / lic360_sconv1x1s2_bf16x1, opt-in): the 1x1 is b3_body<.., 1, 1, 2> on the same
+// even / even loader; the 3x3 has a loader of its own -- through registers into a double-buffered bf16 image -- in sconv_b1s2.inc.  Tile decode and launch are shared.
 //
 // Three arithmetic forms, one of everything else.  s3_body (here) is the fp32 form, b3_body (sconv_bf16x3.inc, opt-in) the split-bf16 form ("bf16x3") and,
 // with its lo parts left out, the single-pass bf16 form ("bf16x1"); they differ in their chunk loop, LDS layout and weight pack.  What decides which cells a convolution reads and writes exists once and serves both:
@@ -109,10 +111,10 @@ __device__ __forceinline__ unsigned s3_cell_offset(const S3Args &a, int tr0, int
 // same loop out in place: inlined from here, its kernels recompute the map's extents for every cell (1 - 3 % more instructions, all ahead of
 // the first DMA, 0.2 - 0.6 % of the run time of the large shapes), written in place they hoist them as they always did.  b3_body's kernels
 // are the other way round: through this call they keep the code they had, with the loop in place their register allocation moves.
-template <int NDMA, int CK, int PL, int XR, int XC, int KS>
+template <int NDMA, int CK, int PL, int XR, int XC, int KS, int ST = 1>
 __device__ __forceinline__ void s3_cell_offsets(const S3Args &a, int tr0, int tc0, int wave, int lane, long PLg, unsigned (&voff)[NDMA]) {
 #pragma unroll
-    for (int i = 0; i < NDMA; ++i) voff[i] = s3_cell_offset<CK, PL, XR, XC, KS>(a, tr0, tc0, (i * 8 + wave) * 64 + lane, PLg);
+    for (int i = 0; i < NDMA; ++i) voff[i] = s3_cell_offset<CK, PL, XR, XC, KS, ST>(a, tr0, tc0, (i * 8 + wave) * 64 + lane, PLg);
 }
 
 // bias, PReLU, residual, store.  Accumulator m, row r, register v: channel co0 + 16 m + 4 kq + v (co0 = the wave's first output channel),
@@ -310,6 +312,7 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
 }
 
 #include "sconv_bf16x3.inc"          // b3_body: the split-bf16 and single-pass bf16 forms of s3_body (arithmetic, pack kernel); everything around the bodies is below
+#include "sconv_b1s2.inc"            // b1s2_body: the single-pass bf16 form of the 3x3 at stride 2 (a register-path loader into a double-buffered bf16 image)
 
 // ---- one workgroup wrapper, one launch for all forms.  NT = bf16 MFMAs per product: 0 the fp32 body, 3 the split-bf16 body, 1 its single-pass form.
 template <int NT, int NQ, int RW, int KS>
@@ -331,15 +334,24 @@ __device__ __forceinline__ void sconv_workgroup(const S3Args &a) {
     }
     sconv_body<NT, NQ, RW, KS>(a, lds, ty, tx, img);
 }
-// the stride-2 workgroup (fp32 form): no tall last tile row -- (2 (TR + NR) + 1) x 33 halos do not fit LDS twice -- a remainder takes an ordinary tile row
-template <int NQ, int RW, int KS>
+// the stride-2 workgroup (NT = 0: the fp32 form, 1: the single-pass bf16 form): no tall last tile row -- (2 (TR + NR) + 1) x 33 halos do not fit LDS twice -- a
+// remainder takes an ordinary tile row
+template <int NQ, int RW, int KS, int NT = 0>
 __device__ __forceinline__ void sconv_s2_workgroup(const S3Args &a) {
-    __shared__ __attribute__((aligned(16))) float lds[s3_lds_st(8 / NQ * RW, KS, 2)];
+    __shared__ __attribute__((aligned(16))) float lds[NT == 0 ? s3_lds_st(8 / NQ * RW, KS, 2) : KS == 3 ? b1s2_lds() : b3_lds(8 / NQ * RW, 1, 1)];
     static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
     const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
-    s3_body<NQ, RW, KS, 2>(a, lds, ty, tx, img);
+    if constexpr (NT == 0) s3_body<NQ, RW, KS, 2>(a, lds, ty, tx, img);
+    else if constexpr (KS == 3) b1s2_body<NQ, RW>(a, lds, ty, tx, img);
+    else b3_body<NQ, RW, 1, 1, 2>(a, lds, ty, tx, img);
 }
 template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3s2(S3Args a) { sconv_s2_workgroup<NQ, RW, KS>(a); }
+template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv_b1s2(S3Args a) { sconv_s2_workgroup<NQ, RW, KS, 1>(a); }
+template <int NT, int NQ, int RW, int KS>
+static auto sconv_s2_kernel() {
+    if constexpr (NT == 1) return &k_sconv_b1s2<NQ, RW, KS>;
+    else return &k_sconv3x3s2<NQ, RW, KS>;
+}
 // (a kernel name per form, so that a profile tells the forms apart)
 template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3(S3Args a) { sconv_workgroup<0, NQ, RW, KS>(a); }
 template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv_b3(S3Args a) { sconv_workgroup<3, NQ, RW, KS>(a); }
@@ -405,15 +417,18 @@ static int sconv_launch(void *stream, const float *x, const void *packed, const 
 
 // the stride-2 forms: x [n][cin][hp][wp] with a `pad` apron and an even interior H x W; out / residual [n][cout][H / 2 + 2 oring][W / 2 + 2 oring], whose
 // interior window is written.  S3Args: hp / wp / pad / sphere are the input's, ohp / owp / ring / ringw the output's grid and window.
-static int sconv_s2_launch(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
+// NT = 0: the fp32 form on the stride-1 fp32 pack; NT = 1: the single-pass bf16 form on the stride-1 single-pass pack (32-channel chunks, a 16-byte aligned pack).
+template <int NT>
+static int sconv_s2_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                            int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring, int ks) {
-    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(0, cin, cout, ks) && pad >= 0 && oring >= 0 && hp > 2 * pad && wp > 2 * pad && sphere >= 0 && sphere <= 1);
+    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(NT, cin, cout, ks) && pad >= 0 && oring >= 0 && hp > 2 * pad && wp > 2 * pad && sphere >= 0 && sphere <= 1);
     ARG_CHECK((hp - 2 * pad) % 2 == 0 && (wp - 2 * pad) % 2 == 0);           // even interiors: the last tap row / column is the interior's last
     ARG_CHECK(ks == 1 || pad >= 1);                                         // the 3x3 taps reach one apron row above / column left of the interior
     ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
-    ARG_CHECK((double)s3_ck(ks) * hp * wp * 4.0 < 4294967296.0 && ((uintptr_t)bias & 15) == 0 && (!slope || ((uintptr_t)slope & 15) == 0));
+    ARG_CHECK((double)sconv_ck(NT, ks) * hp * wp * 4.0 < 4294967296.0 && (!NT || ((uintptr_t)packed & 15) == 0) && ((uintptr_t)bias & 15) == 0 &&
+              (!slope || ((uintptr_t)slope & 15) == 0));
     S3Args a;
-    a.x = x; a.w = packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
+    a.x = x; a.w = (const float *)packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
     a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = oring; a.ringw = oring;
     const int oh = (hp - 2 * pad) / 2, ow = (wp - 2 * pad) / 2;
     ARG_CHECK((long)oh + 2L * oring < (1L << 30) && (long)ow + 2L * oring < (1L << 30));
@@ -424,10 +439,10 @@ static int sconv_s2_launch(void *stream, const float *x, const float *packed, co
     const long tiles = (long)n * a.tiles_x * a.tiles_y;
     ARG_CHECK(tiles < (1L << 31));
     const dim3 grid((unsigned)tiles, nq == 4 ? cout / 192 : 1);
-    if (ks == 3 && nq == 4) hipLaunchKernelGGL((k_sconv3x3s2<4, 8, 3>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (ks == 3) hipLaunchKernelGGL((k_sconv3x3s2<2, 4, 3>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (nq == 4) hipLaunchKernelGGL((k_sconv3x3s2<4, 8, 1>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_sconv3x3s2<2, 4, 1>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    if (ks == 3 && nq == 4) hipLaunchKernelGGL((sconv_s2_kernel<NT, 4, 8, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else if (ks == 3) hipLaunchKernelGGL((sconv_s2_kernel<NT, 2, 4, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else if (nq == 4) hipLaunchKernelGGL((sconv_s2_kernel<NT, 4, 8, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((sconv_s2_kernel<NT, 2, 4, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK();
     return 0;
 }
@@ -481,10 +496,21 @@ LIC360_API int lic360_sconv1x1_bf16x1(void *stream, const float *x, const void *
 LIC360_API int lic360_sconv3x3s2_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 3) ? 1 : 0; }
 LIC360_API int lic360_sconv3x3s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                  int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring) {
-    return sconv_s2_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, oring, 3);
+    return sconv_s2_launch<0>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, oring, 3);
 }
 LIC360_API int lic360_sconv1x1s2_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 1) ? 1 : 0; }
 LIC360_API int lic360_sconv1x1s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                  int n, int cin, int cout, int hp, int wp, int pad, int oring) {
-    return sconv_s2_launch(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, 0, oring, 1);
+    return sconv_s2_launch<0>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, 0, oring, 1);
+}
+// the single-pass bf16 forms of the stride-2 pair (opt-in: lic360_models.set_conv_precision(.., stride2="bf16x1")); they read the stride-1 single-pass packs
+LIC360_API int lic360_sconv3x3s2_bf16x1_supported(int cin, int cout) { return sconv_ok(1, cin, cout, 3) ? 1 : 0; }
+LIC360_API int lic360_sconv3x3s2_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                        int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring) {
+    return sconv_s2_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, oring, 3);
+}
+LIC360_API int lic360_sconv1x1s2_bf16x1_supported(int cin, int cout) { return sconv_ok(1, cin, cout, 1) ? 1 : 0; }
+LIC360_API int lic360_sconv1x1s2_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                                        int n, int cin, int cout, int hp, int wp, int pad, int oring) {
+    return sconv_s2_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, 0, oring, 1);
 }

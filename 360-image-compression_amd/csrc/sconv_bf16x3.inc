@@ -77,23 +77,25 @@ __global__ void k_sconv_b3_pack(const float *__restrict__ w, b3_u4 *__restrict__
     }
 }
 
-// NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, NT bf16 MFMAs per product: 3 = the split form, 1 = single pass (hi parts only)
-template <int NQ, int RW, int KS, int NT = 3>
+// NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, NT bf16 MFMAs per product: 3 = the split form, 1 = single pass (hi parts only);
+// ST = 2: the 1x1 at stride 2 (tile and window in the OUTPUT's grid, even / even source cells: s3_cell_offset; the 3x3 at stride 2 is sconv_b1s2.inc)
+template <int NQ, int RW, int KS, int NT = 3, int ST = 1>
 __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int tx, int img) {
     constexpr int NR = 8 / NQ, TR = NR * RW, XR = TR + KS - 1, XC = S3_T + KS - 1, NCELL = XR * XC;
     constexpr int NDMA = b3_ndma(NCELL), BUF = 8 * NDMA * 64, PS = b3_ps(NCELL), NSTEP = KS * KS;
     constexpr int NA = NT == 3 ? 6 : 3;                                     // A operands of a K step: (row tile, hi | lo), or the row tiles' hi parts
     static_assert(NT == 3 || NT == 1, "split (hi + lo) or single pass (hi)");
+    static_assert(ST == 1 || (ST == 2 && KS == 1), "the stride-2 1x1 has the stride-1 image");
     static_assert(NDMA <= 63, "s_waitcnt vmcnt takes at most 63 on gfx950");
     float (*xs)[BUF] = (float (*)[BUF])lds;
     b3_u4 *sp = (b3_u4 *)(lds + 2 * BUF);                                   // split image [hl][kq][PS] (NT = 1: [kq][PS])
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), mq = wave % NQ, nh = wave / NQ;
-    const int tr0 = a.ring + ty * (NR * a.rw), tc0 = a.ringw + tx * S3_T;
+    const int tr0 = (ST == 1 ? a.ring : 0) + ty * (NR * a.rw), tc0 = (ST == 1 ? a.ringw : 0) + tx * S3_T;
     const int blk = blockIdx.y;
     const long PLg = (long)a.hp * a.wp;
     unsigned voff[NDMA];
-    s3_cell_offsets<NDMA, B3_CK, NCELL, XR, XC, KS>(a, tr0, tc0, wave, lane, PLg, voff);
+    s3_cell_offsets<NDMA, B3_CK, NCELL, XR, XC, KS, ST>(a, tr0, tc0, wave, lane, PLg, voff);
     const float *xb = a.x + (long)img * a.cin * PLg;
     const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) const float *)&xs[0][0];
     auto issue_dma = [&](const float *sb0, int buf) __attribute__((always_inline)) {
@@ -186,5 +188,6 @@ __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int
         if (ck + 1 < nck) chunk(ck + 1, std::integral_constant<int, 1>{});
     }
 #undef B3_WAIT_A
-    s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
+    if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
+    else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
 }

@@ -9,7 +9,9 @@ on this package's own kernel (csrc/conv3x3_kernels.hip, `lic360.sconv3x3`): fp32
 the blocks' 1x1 layers ride on the same body (`lic360.sconv1x1`), and so do the down-sampling layers of the analysis transform: the 3x3
 stride-2 convolutions and the 1x1 stride-2 shortcuts of the hidden stages (`lic360.sconv3x3s2` / `sconv1x1s2`, the body's stride-2 forms).
 set_conv_precision(model, "bf16x3") moves the stride-1 fused layers to their split-bf16 forms (csrc/sconv_bf16x3.inc), "bf16x1" to their
-single-pass bf16 forms (operands rounded once, one MFMA per product), per module.
+single-pass bf16 forms (operands rounded once, one MFMA per product), per module.  The stride-2 layers stay fp32 in every such mode unless the
+setter's keyword asks otherwise: set_conv_precision(model, precision, stride2="bf16x1") moves them to their own single-pass bf16 forms
+(`lic360.sconv3x3s2_bf16x1` / `sconv1x1s2_bf16x1`, csrc/sconv_b1s2.inc), independently of `precision`.
 The first stage's stride-2 layers (3 input channels: no 16-channel chunk, and bound by their output, not by MFMAs), convolutions off the fused
 shapes, small maps and every recording (training) pass are library work (torch -> MIOpen); native around them:
 sphere pad / trim / cut-edge / pixel-shuffle / importance map / quantiser kernels and the one-pass GDN (csrc/gdn_kernels.hip)."""
@@ -72,21 +74,32 @@ def _fusable_s2(conv, x, mod=None):
 
 
 CONV_PRECISIONS = ("fp32", "bf16x3", "bf16x1")
+STRIDE2_PRECISIONS = ("fp32", "bf16x1")
+S2_BF16X1_1X1_MAX_CELLS = 132 * 260  # lic360.sconv1x1s2_bf16x1 is taken on input maps of up to this many cells: the largest on which it beat the fp32 stride-2 kernel by more
+                                     # than the repeats' spreads (batch 8: 0.076 against 0.093 ms).  On the 260 x 516 map the shortcut moves 0.8 GB per launch and both forms take
+                                     # what the memory takes (0.348 against 0.359 ms, inside the spreads): that shape, and any unmeasured one above the bound, stays on fp32.
+                                     # The 3x3 form passed on every production shape (3.7 - 6.4 x) and has no such bound.  tools/conv3x3_probe.py --s2 --precision bf16x1,
+                                     # profiles/sconv_s2_bf16x1_probe.json, DESIGN §7c‴.
 
 
-def set_conv_precision(module, precision):
+def set_conv_precision(module, precision, stride2="fp32"):
     """arithmetic of the fused convolutions of every block under `module` (module.modules()): "fp32" (the default: lic360.sconv3x3 / sconv1x1),
     "bf16x3" (their split-bf16 forms wherever those take the layer's shape, the fp32 kernel elsewhere; about 2^-16 relative error per product) or
     "bf16x1" (their single-pass bf16 forms under the same shape rule: every input value and weight rounded once to bf16, one MFMA per product, fp32
     accumulation, bias / PReLU / residual in fp32; about 2^-8 relative per operand -- reduced-precision inference: a latent from any mode codes
     bit-exactly, only decoded pixels depend on the decoder's mode).
-    The stride-2 layers have no bf16 form: in "bf16x3" and "bf16x1" mode they stay on the fp32 stride-2 kernel (lic360.sconv3x3s2 / sconv1x1s2).
+    The stride-2 layers do not follow `precision`: in every mode they stay on the fp32 stride-2 kernel (lic360.sconv3x3s2 / sconv1x1s2) unless
+    stride2="bf16x1" moves them to their single-pass bf16 forms (lic360.sconv3x3s2_bf16x1 / sconv1x1s2_bf16x1: the bf16x1 contract, wherever those take the
+    layer's shape); a later call without the keyword returns them to fp32.
     A per-module setting, not a global: several copies of the networks may run side by side in different modes.  Library layers, small maps and
     recording passes are the same in either mode.  Returns `module`."""
     if precision not in CONV_PRECISIONS:
         raise ValueError("conv precision must be one of %s, got %r" % (CONV_PRECISIONS, precision))
+    if stride2 not in STRIDE2_PRECISIONS:
+        raise ValueError("stride-2 conv precision must be one of %s, got %r" % (STRIDE2_PRECISIONS, stride2))
     for m in module.modules():
         m._conv_precision = precision
+        m._stride2_precision = stride2
     return module
 
 
@@ -123,11 +136,17 @@ def _packed(conv, precision, pack):
     return packs[precision][1]
 
 
-def _sconv_s2(conv, x, slope, residual, out):
-    """the stride-2 convolution `conv` (3x3 or the 1x1 shortcut) of a 2-cell-apron map on lic360.sconv3x3s2 / sconv1x1s2: fp32 in every precision
-    mode of the block (there is no bf16 stride-2 form), on the stride-1 fp32 pack of the weight"""
+def _sconv_s2(mod, conv, x, slope, residual, out):
+    """the stride-2 convolution `conv` (3x3 or the 1x1 shortcut) of block `mod` on a 2-cell-apron map: lic360.sconv3x3s2 / sconv1x1s2 (fp32, on the stride-1
+    fp32 pack of the weight) whatever the block's _conv_precision, or -- when the block's _stride2_precision is "bf16x1", their shape predicate takes
+    the layer and the layer is not one the measurement routes to fp32 (S2_BF16X1_1X1_MAX_CELLS: the 1x1 shortcut on maps above 132 x 260) --
+    lic360.sconv3x3s2_bf16x1 / sconv1x1s2_bf16x1 on the stride-1 bf16x1 pack (the one the stride-1 form caches)"""
     ks = conv.kernel_size[0]
+    cout, cin = conv.weight.shape[:2]
     fn, pack, _ = _SCONV[ks, "fp32"]
+    if (getattr(mod, "_stride2_precision", "fp32") == "bf16x1" and getattr(lic360, fn + "s2_bf16x1_supported")(cin, cout)
+            and (ks == 3 or x.shape[2] * x.shape[3] <= S2_BF16X1_1X1_MAX_CELLS)):
+        return getattr(lic360, fn + "s2_bf16x1")(x, _packed(conv, "bf16x1", _SCONV[ks, "bf16x1"][1]), conv.bias, slope, residual, out, pad=2, oring=2)
     return getattr(lic360, fn + "s2")(x, _packed(conv, "fp32", pack), conv.bias, slope, residual, out, pad=2, oring=2)
 
 
@@ -232,9 +251,9 @@ class ResidualBlockDown(nn.Module):
             if _fusable(self.conv2, y, 2, mod=self):                        # (the whole block goes one way: FUSED_MIN_WORKGROUPS rules its stride-2 layers too)
                 # conv1 reads x's apron by index (no pad1: x is not modified), conv2 reads conv1's likewise, GDN is pointwise, the shortcut reads the interior
                 # only and adds the GDN output in its epilogue; every apron cell on the way is scratch, the final trim zeroes the output's
-                _sconv_s2(self.conv1, x, self.relu1.weight, None, y)
+                _sconv_s2(self, self.conv1, x, self.relu1.weight, None, y)
                 y = self.relu2(_sconv(self, self.conv2, y, None, None, _scratch(shape, x), pad=2, sphere=True, ring=2))
-                return self.trim(_sconv_s2(self.short_cut, x, None, y, _scratch(shape, x)))
+                return self.trim(_sconv_s2(self, self.short_cut, x, None, y, _scratch(shape, x)))
         if self.hidden:
             skip = self.short_cut(x)                                        # before pad1 refreshes the apron in place
             y = self.pad1(x)
@@ -264,7 +283,7 @@ class SphereConv2(nn.Module):
     def forward(self, x):
         c = self.conv
         if (c.kernel_size, c.stride, c.padding) == ((3, 3), (2, 2), (3, 3)) and type(self) is SphereConv2 and _fusable_s2(c, x, self):
-            return _sconv_s2(c, x, None, None, None)                        # pad, convolution and trim: the interior window of a zero-filled map
+            return _sconv_s2(self, c, x, None, None, None)                        # pad, convolution and trim: the interior window of a zero-filled map
         return self.trim(self.conv(self.pad(x)))
 
 

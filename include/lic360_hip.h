@@ -398,6 +398,20 @@ int lic360_sconv3x3s2(void *stream, const float *x, const float *packed, const f
 int lic360_sconv1x1s2_supported(int cin, int cout);
 int lic360_sconv1x1s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                       int n, int cin, int cout, int hp, int wp, int pad, int oring);
+/* ---- the single-pass bf16 ("bf16x1") forms of the stride-2 pair (kernels k_sconv_b1s2; the 3x3: csrc/sconv_b1s2.inc, the 1x1: csrc/sconv_bf16x3.inc at
+ * stride 2), opt-in.  lic360_sconv3x3s2_bf16x1 replaces what lic360_sconv3x3s2 replaces (SpherePad(2) + nn.Conv2d(cin, c, 3, 2, 3) + nn.PReLU + SphereTrim
+ * of test/model_zoo.py:64-106), lic360_sconv1x1s2_bf16x1 what lic360_sconv1x1s2 replaces (nn.Conv2d(cin, c, 1, 2, 2) + the add of
+ * ResidualBlockDown.short_cut): the same operation, argument lists, shapes of x / out / residual and output window.  Arithmetic: the bf16x1 contract -- every
+ * input value and every weight rounded ONCE to bf16 (nearest even), one v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation, bias / PReLU / residual
+ * in fp32: the fp32-accumulated stride-2 convolution of the rounded operands.  Inference only; NaN and infinity are outside the contract.
+ * packed = the STRIDE-1 single-pass packs (lic360_sconv3x3_bf16x1_pack, lic360_sconv1x1_bf16x1_pack; 16-byte aligned) -- not an fp32 pack; the shape
+ * predicates are the stride-1 single-pass ones (cin % 32 == 0, cout = 96 or a multiple of 192); bias / slope 16-byte aligned. */
+int lic360_sconv3x3s2_bf16x1_supported(int cin, int cout);   /* == lic360_sconv3x3_bf16x1_supported */
+int lic360_sconv3x3s2_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                             int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring);
+int lic360_sconv1x1s2_bf16x1_supported(int cin, int cout);   /* == lic360_sconv1x1_bf16x1_supported */
+int lic360_sconv1x1s2_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                             int n, int cin, int cout, int hp, int wp, int pad, int oring);
 /* apron of dst <- sphere-wrapped interior of src (src == dst: lic360_sphere_pad_inplace); [nc][hp][wp] planes      sphere_pad_cuda.cu:48-65 */
 int lic360_sphere_apron_from(void *stream, const float *src, float *dst, int nc, int hp, int wp, int pad);
 

@@ -6,7 +6,10 @@ fused kernel absorbs (in-place apron refresh, PReLU, trim) and without.  VERDICT
 run (median, min, max of 5 repeats of 10 launches), and --json FILE keeps that table.
 --s2: the stride-2 forms instead (lic360_sconv3x3s2 / sconv1x1s2) on the analysis transform's three down-sampling shapes and two shortcuts, batches
 1, 2, 4, 8, 32, each next to the library form of the same work (in-place SpherePad + conv2d(stride 2) + PReLU; shortcut conv2d + add + trim): median
-of alternating repeats with the spread, and the smallest tile count from which the native form is not slower on any shape; --json FILE keeps the table."""
+of alternating repeats with the spread, and the smallest tile count from which the native form is not slower on any shape; --json FILE keeps the table.
+--s2 --precision bf16x1: the single-pass bf16 stride-2 forms (lic360_sconv3x3s2_bf16x1 / sconv1x1s2_bf16x1) next to the fp32 stride-2 kernel on the five
+production shapes at batch 8, launches alternating in one process (median, min, max of 5 repeats of 10 launches), and the rule for a form per shape: the
+bf16x1 median lies below the fp32 median by more than the two min-max spreads added; --json FILE keeps the table."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "360-image-compression_amd"))
@@ -109,9 +112,54 @@ def s2_probe():
                            threshold_tiles=thr, rows=rows), f, indent=1)
 
 
+def s2_bf16x1_probe():
+    rows, n, c = [], int(os.environ.get("S3_N", "8")), 192
+    for ks, hp, wp, what in ((3, 260, 516, "stage-2 conv1"), (3, 132, 260, "stage-3 conv1"), (3, 68, 132, "SphereConv2"),
+                             (1, 260, 516, "stage-2 shortcut"), (1, 132, 260, "stage-3 shortcut")):
+        oh, ow = (hp - 4) // 2, (wp - 4) // 2
+        x = torch.randn(n, c, hp, wp, device=dev)
+        w = torch.randn(c, c, ks, ks, device=dev) * 0.05
+        b, sl = torch.randn(c, device=dev), torch.rand(c, device=dev) * 0.5
+        res = torch.randn(n, c, oh + 4, ow + 4, device=dev)
+        outs = {f: torch.zeros(n, c, oh + 4, ow + 4, device=dev) for f in ("fp32", "bf16x1")}
+        if ks == 3:
+            slope = None if what == "SphereConv2" else sl
+            pk, pb = lic360.sconv3x3_pack(w), lic360.sconv3x3_bf16x1_pack(w)
+            fns = {"fp32": lambda: lic360.sconv3x3s2(x, pk, b, slope, None, outs["fp32"], pad=2, sphere=True, oring=2),
+                   "bf16x1": lambda: lic360.sconv3x3s2_bf16x1(x, pb, b, slope, None, outs["bf16x1"], pad=2, sphere=True, oring=2)}
+        else:
+            pk, pb = lic360.sconv1x1_pack(w), lic360.sconv1x1_bf16x1_pack(w)
+            fns = {"fp32": lambda: lic360.sconv1x1s2(x, pk, b, None, res, outs["fp32"], pad=2, oring=2),
+                   "bf16x1": lambda: lic360.sconv1x1s2_bf16x1(x, pb, b, None, res, outs["bf16x1"], pad=2, oring=2)}
+        err = (fns["bf16x1"]() - fns["fp32"]()).abs().max().item()
+        t = {f: [] for f in fns}
+        for _ in range(5):                                                  # alternating repeats
+            for f in fns:
+                t[f].append(timed(fns[f]))
+        row = dict(layer=what, ks=ks, n=n, hp=hp, wp=wp, tiles=n * ((oh + 15) // 16) * ((ow + 15) // 16), max_abs_diff_to_fp32=err)
+        for f in fns:
+            row.update({f + "_ms": sorted(t[f])[2], f + "_min": min(t[f]), f + "_max": max(t[f])})
+        spreads = (row["fp32_max"] - row["fp32_min"]) + (row["bf16x1_max"] - row["bf16x1_min"])
+        row.update(speedup=row["fp32_ms"] / row["bf16x1_ms"], spreads_added=spreads, passes=bool(row["fp32_ms"] - row["bf16x1_ms"] > spreads))
+        rows.append(row)
+        print("s2 %dx%d %-16s @%dx%d x%d (%4d tiles): max|bf16x1 - fp32| %.2e | fp32 %.3f ms (%.3f .. %.3f) | bf16x1 %.3f ms (%.3f .. %.3f) | fp32 / bf16x1 = %.2f | "
+              "median gap %.3f ms vs spreads %.3f ms: %s" % (ks, ks, what, hp, wp, n, row["tiles"], err, row["fp32_ms"], row["fp32_min"], row["fp32_max"], row["bf16x1_ms"],
+                                                           row["bf16x1_min"], row["bf16x1_max"], row["speedup"], row["fp32_ms"] - row["bf16x1_ms"], spreads,
+                                                           "passes" if row["passes"] else "DOES NOT PASS"), flush=True)
+        del x, res, outs
+    if ARGS.json:
+        with open(ARGS.json, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), forms=["fp32", "bf16x1"],
+                           repeats="median of 5 repeats of 10 launches, each after 3 warm-up launches, the two forms alternating within a repeat; ms per launch",
+                           rule="a shape passes when fp32_ms - bf16x1_ms > (fp32_max - fp32_min) + (bf16x1_max - bf16x1_min)", rows=rows), f, indent=1)
+
+
 if ARGS.s2:
     torch.manual_seed(0)
-    s2_probe()
+    if ARGS.precision == "bf16x1":
+        s2_bf16x1_probe()
+    else:
+        s2_probe()
     sys.exit(0)
 
 torch.manual_seed(0)
