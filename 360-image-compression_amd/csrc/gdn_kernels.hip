@@ -10,6 +10,9 @@
 //     and leaves row-wise, 16 bytes per lane;
 //   * the sum over j runs in ascending j for every output (a fixed order; torch's conv sums in its own, so parity is to 1e-5).
 // C in {16, 32, 48, 64, 96, 128, 192} (the transforms use 192 and 96); 60 KB of LDS at C = 192.
+// The split-bf16 form (k_gdn_b3, lic360_gdn_bf16x3; opt-in): gdn_bf16x3.inc, included at the end of this file -- the same contract with the sum on
+// v_mfma_f32_16x16x32_bf16 (x^2 and gamma as hi + lo bf16 parts, three MFMAs per product, fp32 accumulation and epilogue): 2^-15 relative per element
+// against the float64 GDN for gamma >= 0.  Its arithmetic, error analysis and mapping are in that file's header.
 #include "common.h"
 
 #define GDN_PT 64                                   // positions per workgroup: 16 per wave
@@ -115,3 +118,5 @@ LIC360_API int lic360_gdn(void *stream, const float *x, const float *gamma, cons
     LAUNCH_CHECK();
     return 0;
 }
+
+#include "gdn_bf16x3.inc"

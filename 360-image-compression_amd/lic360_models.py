@@ -82,7 +82,10 @@ S2_BF16X1_1X1_MAX_CELLS = 132 * 260  # lic360.sconv1x1s2_bf16x1 is taken on inpu
                                      # profiles/sconv_s2_bf16x1_probe.json, DESIGN §7c‴.
 
 
-def set_conv_precision(module, precision, stride2="fp32"):
+GDN_PRECISIONS = ("fp32", "bf16x3")
+
+
+def set_conv_precision(module, precision, stride2="fp32", gdn="fp32"):
     """arithmetic of the fused convolutions of every block under `module` (module.modules()): "fp32" (the default: lic360.sconv3x3 / sconv1x1),
     "bf16x3" (their split-bf16 forms wherever those take the layer's shape, the fp32 kernel elsewhere; about 2^-16 relative error per product) or
     "bf16x1" (their single-pass bf16 forms under the same shape rule: every input value and weight rounded once to bf16, one MFMA per product, fp32
@@ -91,15 +94,21 @@ def set_conv_precision(module, precision, stride2="fp32"):
     The stride-2 layers do not follow `precision`: in every mode they stay on the fp32 stride-2 kernel (lic360.sconv3x3s2 / sconv1x1s2) unless
     stride2="bf16x1" moves them to their single-pass bf16 forms (lic360.sconv3x3s2_bf16x1 / sconv1x1s2_bf16x1: the bf16x1 contract, wherever those take the
     layer's shape); a later call without the keyword returns them to fp32.
+    The GDNs do not follow `precision` either: they stay on the fp32 one-pass kernel (lic360.gdn_forward) unless gdn="bf16x3" moves those of a supported
+    channel count to the split-bf16 form (lic360.gdn_bf16x3_forward, csrc/gdn_bf16x3.inc: 2^-15 relative per element against the float64 GDN); a later
+    call without the keyword returns them to fp32.
     A per-module setting, not a global: several copies of the networks may run side by side in different modes.  Library layers, small maps and
     recording passes are the same in either mode.  Returns `module`."""
     if precision not in CONV_PRECISIONS:
         raise ValueError("conv precision must be one of %s, got %r" % (CONV_PRECISIONS, precision))
     if stride2 not in STRIDE2_PRECISIONS:
         raise ValueError("stride-2 conv precision must be one of %s, got %r" % (STRIDE2_PRECISIONS, stride2))
+    if gdn not in GDN_PRECISIONS:
+        raise ValueError("GDN precision must be one of %s, got %r" % (GDN_PRECISIONS, gdn))
     for m in module.modules():
         m._conv_precision = precision
         m._stride2_precision = stride2
+        m._gdn_precision = gdn
     return module
 
 

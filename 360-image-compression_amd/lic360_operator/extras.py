@@ -56,11 +56,20 @@ class GDN(nn.Module):
         gamma = _FloorSTE.apply(self.gamma.to(x.device), self.gamma_bound) ** 2 - self.pedestal
         if not (torch.is_grad_enabled() and (x.requires_grad or self.beta.requires_grad)) and x.is_cuda and x.dtype == torch.float32:
             import lic360
+            if getattr(self, "_gdn_precision", "fp32") == "bf16x3" and lic360.gdn_bf16x3_supported(ch):
+                return lic360.gdn_bf16x3_forward(x.contiguous(), self._gdn_b3_pack(lic360, gamma.detach()), beta.detach(), self.inverse).reshape(shape)
             if lic360.gdn_supported(ch):                                    # one fused pass instead of four torch kernels
                 return lic360.gdn_forward(x.contiguous(), gamma.detach(), beta.detach(), self.inverse).reshape(shape)
         norm = torch.sqrt(F.conv2d(x * x, gamma.view(ch, ch, 1, 1), beta))
         y = x * norm if self.inverse else x / norm
         return y.reshape(shape)
+
+    def _gdn_b3_pack(self, lic360, gamma):
+        """the effective gamma in the split-bf16 kernel's operand order, repacked when the parameter was written (its version counter) or moved"""
+        key = (self.gamma.data_ptr(), self.gamma._version, gamma.device)
+        if getattr(self, "_gdn_b3_packed", (None, None))[0] != key:
+            self._gdn_b3_packed = (key, lic360.gdn_bf16x3_pack(gamma))
+        return self._gdn_b3_packed[1]
 
 
 class _GradGate(torch.autograd.Function):

@@ -320,6 +320,17 @@ int lic360_viewport_xy(void *stream, const float *theta_phi_next, const float *r
  * out[n,i,p] = x / sqrt(beta[i] + sum_j gamma[i,j] x[n,j,p]^2)   (inverse != 0: x * sqrt(...)); x / out [n][c][p] contiguous,
  * gamma [c][c] and beta [c] are the effective (reparametrised) parameters; c in {16,32,48,64,96,128,192}; j summed in ascending order */
 int lic360_gdn(void *stream, const float *x, const float *gamma, const float *beta, float *out, int n, int c, long p, int inverse);
+/* ---- the split-bf16 ("bf16x3") form of lic360_gdn (csrc/gdn_bf16x3.inc, kernel k_gdn_b3), opt-in: the same operation, operands and output contract
+ * (x / out [n][c][p] contiguous on 4-byte boundaries, any p, nothing outside out written).  sq = x * x in fp32; sq and the effective gamma are each split
+ * into hi = bf16(v) and lo = bf16(v - hi) (round to nearest even); each product is g_hi sq_hi + g_hi sq_lo + g_lo sq_hi on v_mfma_f32_16x16x32_bf16 with
+ * fp32 accumulation; sqrtf, the division (or product) and beta stay fp32 on the unrounded x.  2^-15 relative per element against the float64 GDN for
+ * gamma >= 0 (a negative gamma: relative to sum |gamma| x^2); NaN, infinity and squares that overflow fp32 are outside the contract.  c in
+ * {32,64,96,128,192}; packed = lic360_gdn_bf16x3_pack of the effective gamma [c][c] (packed_bytes = 4 c c bytes, 16-byte aligned: hi and lo bf16
+ * parts in the waves' A-operand order).  Refused before any launch: null operands, n <= 0, n > 65535, p <= 0, an unsupported c, a misaligned pack. */
+int lic360_gdn_bf16x3_supported(int c);
+long lic360_gdn_bf16x3_packed_bytes(int c);
+int lic360_gdn_bf16x3_pack(void *stream, const float *gamma, void *packed, int c);
+int lic360_gdn_bf16x3(void *stream, const float *x, const void *packed, const float *beta, float *out, int n, int c, long p, int inverse);
 
 /* ---- f1 3x3 stride-1 convolution on sphere-apron maps with the apron read BY INDEX in the tile loader and bias + PReLU + residual in the
  * epilogue (csrc/conv3x3_kernels.hip): replaces, per layer, nn.Conv2d(c, c', 3, 1, 1 | 0) + the in-place SpherePad in front of it + the
