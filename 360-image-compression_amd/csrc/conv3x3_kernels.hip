@@ -38,7 +38,14 @@
 // with its lo parts left out, the single-pass bf16 form ("bf16x1"); they differ in their chunk loop, LDS layout and weight pack.  What decides which cells a convolution reads and writes exists once and serves both:
 // s3_cell_offset (the source cell of a loader's LDS cell), s3_epilogue (bias, PReLU, residual, window test, store), the kernel wrapper sconv_workgroup<NT, ..>
 // (tile decode, tall last tile row) and the host's sconv_launch<NT> (shape predicate, argument contract, tile geometry, grid).
+//
+// The gate of the attention blocks (k_gate_sconv / k_gate_sconv_b3 / k_gate_sconv_b1; lic360_sconv1x1_gate / _bf16x3 / _bf16x1, opt-in:
+// lic360_models.set_conv_precision(.., gate="fused")).  Replaces the tail of AttentionBlock, test/model_zoo.py:25-46: nn.Conv2d(c, c, 1) + nn.Sigmoid + the `*` with
+// the trunk + the `+` with the input.  The 1x1 stride-1 bodies of the three forms with a compile-time variant of the epilogue (s3_epilogue<RW, 1, 1>):
+// out = residual + trunk * (1 / (1 + lic360_expf(-(acc + bias)))), one fp32 rounding per operation.  The trunk pointer travels in S3GateArgs, beside S3Args.
+// (The names do not carry the k_sconv prefix: the kernels of that prefix are counted by tests/test_asm_load_hazards.py.)
 #include "common.h"
+#include "lic360_exact_math.h"
 #include <cstdint>
 
 typedef float s3_f4 __attribute__((ext_vector_type(4)));
@@ -120,10 +127,47 @@ __device__ __forceinline__ void s3_cell_offsets(const S3Args &a, int tr0, int tc
 // bias, PReLU, residual, store.  Accumulator m, row r, register v: channel co0 + 16 m + 4 kq + v (co0 = the wave's first output channel),
 // position (tr0 + nh * RW + r, tc0 + col) of the input grid (col = lane & 15, kq = lane >> 4, PLg = hp * wp); cells outside the window are not written.
 // ST = 2: the position is a cell of the OUTPUT's own grid (ohp x owp, window [ring, ohp - ring) x [ringw, owp - ringw)), and so is the residual's.
-template <int RW, int ST = 1>
+// GT = 1 (the attention blocks' gate, k_gate_sconv*: stride 1, no PReLU, crop or shuffle): out = residual + trunk * sigmoid(acc + bias), with
+// sigmoid(y) = 1 / (1 + lic360_expf(-y)) -- host / device bit-identical -- and one fp32 rounding per operation (the unit is built without contraction);
+// `trunk` has the residual's geometry, and both are required.  A compile-time variant: the GT = 0 instantiations are the code they were.
+template <int RW, int ST = 1, int GT = 0>
 __device__ __forceinline__ void s3_epilogue(const S3Args &a, const s3_f4 (&acc)[3][RW], int img, int tr0, int tc0, int co0, int nh, int col, int kq,
-                                            long PLg) {
+                                            long PLg, const float *trunk = nullptr) {
     const int pw = tc0 + col;
+    if constexpr (GT) {
+        static_assert(ST == 1, "the gate is a stride-1 epilogue");
+        const float *__restrict__ resp = a.res, *__restrict__ trkp = trunk;
+        float *__restrict__ outp = a.out;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            const int co = co0 + 16 * m + 4 * kq;
+            const s3_f4 bs = *(const s3_f4 *)(a.bias + co);
+            s3_f4 rv[RW], tv[RW];
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {                                  // all trunk and residual loads of the row tile in flight before its first store
+                const int ph = tr0 + nh * RW + r;
+                const bool ok = ph < a.hp - a.ring && pw < a.wp - a.ringw;
+                const long ri = ((long)img * a.cout + co) * PLg + (long)(ok ? ph : a.ring) * a.wp + (ok ? pw : a.ringw);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) { tv[r][v] = trkp[ri + v * PLg]; rv[r][v] = resp[ri + v * PLg]; }
+            }
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                const int ph = tr0 + nh * RW + r;
+                if (ph < a.hp - a.ring && pw < a.wp - a.ringw) {
+                    const long o = ((long)img * a.cout + co) * PLg + (long)ph * a.wp + pw;
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const float y = acc[m][r][v] + bs[v];
+                        const float g = 1.0f / (1.0f + lic360_expf(-y));
+                        const float tg = tv[r][v] * g;
+                        outp[o + v * PLg] = rv[r][v] + tg;
+                    }
+                }
+            }
+        }
+        return;
+    }
     const long oPL = (long)a.ohp * a.owp;
     const int wh = ST == 1 ? a.hp : a.ohp, ww = ST == 1 ? a.wp : a.owp;    // the grid the window is a window of
     const float *__restrict__ resp = a.res;
@@ -210,8 +254,8 @@ constexpr int s3_xc(int ks, int st) { return st == 2 && ks == 3 ? 2 * S3_T + 1 :
 constexpr int s3_pitch_st(int tr, int ks, int st) { return st == 2 && ks == 3 ? (s3_xr(tr, ks, st) * s3_xc(ks, st)) | 1 : s3_pitch(tr, ks); }
 constexpr int s3_ndma_st(int tr, int ks, int st) { return (s3_ck(ks) * s3_pitch_st(tr, ks, st) + 511) / 512; }
 constexpr int s3_lds_st(int tr, int ks, int st) { return 2 * 8 * s3_ndma_st(tr, ks, st) * 64; }
-template <int NQ, int RW, int KS, int ST = 1>                               // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, stride ST
-__device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int tx, int img) {
+template <int NQ, int RW, int KS, int ST = 1, int GT = 0>                   // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, stride ST; GT: the gate epilogue
+__device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int tx, int img, const float *trunk = nullptr) {
     constexpr int PD = KS == 3 ? 1 : 3;                                     // A operands PD pairs ahead: a 1x1 pair is 24 MFMAs (768 cycles), its operand is fetched three pairs ahead
     constexpr int NR = 8 / NQ, TR = NR * RW;                                // row groups per workgroup, tile rows
     constexpr int S3_CK = s3_ck(KS), NPAIR = S3_CK / 4 * KS, NA4 = s3_na4(KS), S3_XC = s3_xc(KS, ST);
@@ -307,7 +351,8 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
         __syncthreads();
     }
 #undef S3_WAIT_A
-    if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
+    if constexpr (GT) s3_epilogue<RW, 1, 1>(a, acc, img, tr0, tc0, blk * cblk + 48 * mq, nh, col, kq, PLg, trunk);
+    else if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
     else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
 }
 
@@ -362,6 +407,30 @@ static auto sconv_kernel() {
     else if constexpr (NT == 1) return &k_sconv_b1<NQ, RW, KS>;
     else return &k_sconv3x3<NQ, RW, KS>;
 }
+// ---- the gate of the attention blocks (k_gate_sconv*): the 1x1 stride-1 bodies of the three forms with the gate epilogue (s3_epilogue<RW, 1, 1>).  The
+// trunk pointer travels beside S3Args, in an argument struct of the gate kernels' own: the other kernels keep their argument bytes.
+struct S3GateArgs {
+    S3Args a;
+    const float *trunk;                              // [n][cout][hp][wp], as a.res and a.out
+};
+template <int NT, int NQ, int RW>
+__device__ __forceinline__ void sconv_gate_workgroup(const S3GateArgs &g) {
+    const S3Args &a = g.a;
+    __shared__ __attribute__((aligned(16))) float lds[NT ? b3_lds(8 / NQ * RW, 1, NT) : s3_lds(8 / NQ * RW, 1)];
+    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
+    const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
+    if constexpr (NT == 0) s3_body<NQ, RW, 1, 1, 1>(a, lds, ty, tx, img, g.trunk);
+    else b3_body<NQ, RW, 1, NT, 1, 1>(a, lds, ty, tx, img, g.trunk);
+}
+template <int NQ, int RW> __global__ __launch_bounds__(S3_THREADS) void k_gate_sconv(S3GateArgs g) { sconv_gate_workgroup<0, NQ, RW>(g); }
+template <int NQ, int RW> __global__ __launch_bounds__(S3_THREADS) void k_gate_sconv_b3(S3GateArgs g) { sconv_gate_workgroup<3, NQ, RW>(g); }
+template <int NQ, int RW> __global__ __launch_bounds__(S3_THREADS) void k_gate_sconv_b1(S3GateArgs g) { sconv_gate_workgroup<1, NQ, RW>(g); }
+template <int NT, int NQ, int RW>
+static auto sconv_gate_kernel() {
+    if constexpr (NT == 3) return &k_gate_sconv_b3<NQ, RW>;
+    else if constexpr (NT == 1) return &k_gate_sconv_b1<NQ, RW>;
+    else return &k_gate_sconv<NQ, RW>;
+}
 
 // the forms differ in their chunk of input channels (and so in the shapes they take), in the pack, and in the body
 static inline int sconv_ck(int nt, int ks) { return nt ? B3_CK : s3_ck(ks); }
@@ -385,9 +454,10 @@ static int b3_pack(int nt, void *stream, const float *weight, void *packed, int 
     LAUNCH_CHECK();
     return 0;
 }
+// the argument contract, tile geometry and grid of a stride-1 launch (sconv_launch, and sconv_gate_launch with ks = 1, crop = 0, shuffle = 0)
 template <int NT>
-static int sconv_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                        int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle) {
+static int sconv_plan(const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle, S3Args &a, dim3 &grid) {
     ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(NT, cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w &&
               out_crop >= 0 && out_crop <= ring && sphere >= 0 && sphere <= 2);
     ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
@@ -395,7 +465,6 @@ static int sconv_launch(void *stream, const float *x, const void *packed, const 
               (!slope || ((uintptr_t)slope & 15) == 0));                    // a chunk's cells at 32-bit byte offsets; 16-byte operand loads
     ARG_CHECK(!residual || out_crop == 0 || shuffle);                       // the residual has the input's geometry -- or, shuffled, the output's
     ARG_CHECK(!shuffle || (((uintptr_t)out & 7) == 0 && ((uintptr_t)residual & 7) == 0));   // the shuffled store / residual load move aligned pairs
-    S3Args a;
     a.x = x; a.w = (const float *)packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
     a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = ring; a.ringw = ring_w;
     a.ooff = out_crop; a.ohp = hp - 2 * out_crop; a.owp = wp - 2 * out_crop; a.shuffle = shuffle;
@@ -406,11 +475,34 @@ static int sconv_launch(void *stream, const float *x, const void *packed, const 
     a.tiles_y = a.tall_last ? full : (nr + S3_T - 1) / S3_T;
     const long tiles = (long)n * a.tiles_x * a.tiles_y;
     ARG_CHECK(tiles < (1L << 31));
-    const dim3 grid((unsigned)tiles, nq == 4 ? cout / 192 : 1);
+    grid = dim3((unsigned)tiles, nq == 4 ? cout / 192 : 1);
+    return 0;
+}
+template <int NT>
+static int sconv_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                        int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle) {
+    S3Args a;
+    dim3 grid;
+    if (const int rc = sconv_plan<NT>(x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, ks, shuffle, a, grid)) return rc;
+    const int nq = cout % 192 == 0 ? 4 : 2;
     if (ks == 3 && nq == 4) hipLaunchKernelGGL((sconv_kernel<NT, 4, 8, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
     else if (ks == 3) hipLaunchKernelGGL((sconv_kernel<NT, 2, 4, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
     else if (nq == 4) hipLaunchKernelGGL((sconv_kernel<NT, 4, 8, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((sconv_kernel<NT, 2, 4, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+    LAUNCH_CHECK();
+    return 0;
+}
+// the gate: the shapes and refusals of the 1x1 launch; trunk and residual are required
+template <int NT>
+static int sconv_gate_launch(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
+                             int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
+    ARG_CHECK(trunk && residual);
+    S3GateArgs g;
+    dim3 grid;
+    if (const int rc = sconv_plan<NT>(x, packed, bias, nullptr, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, 0, 1, 0, g.a, grid)) return rc;
+    g.trunk = trunk;
+    if (cout % 192 == 0) hipLaunchKernelGGL((sconv_gate_kernel<NT, 4, 8>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((sconv_gate_kernel<NT, 2, 4>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
     LAUNCH_CHECK();
     return 0;
 }
@@ -491,6 +583,19 @@ LIC360_API int lic360_sconv1x1_bf16x1_pack(void *stream, const float *weight, vo
 LIC360_API int lic360_sconv1x1_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                       int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
     return sconv_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+}
+// the attention blocks' gate in the three forms: out = residual + trunk * sigmoid(conv1x1(x) + bias) on the window, one launch; they read the stride-1 1x1 packs
+LIC360_API int lic360_sconv1x1_gate(void *stream, const float *x, const float *packed, const float *bias, const float *trunk, const float *residual, float *out,
+                                    int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
+    return sconv_gate_launch<0>(stream, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
+}
+LIC360_API int lic360_sconv1x1_gate_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
+                                           int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
+    return sconv_gate_launch<3>(stream, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
+}
+LIC360_API int lic360_sconv1x1_gate_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
+                                           int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
+    return sconv_gate_launch<1>(stream, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
 }
 // the stride-2 forms of the fp32 pair (the analysis transform's down-sampling layers); they read the stride-1 packs
 LIC360_API int lic360_sconv3x3s2_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 3) ? 1 : 0; }

@@ -79,8 +79,8 @@ __global__ void k_sconv_b3_pack(const float *__restrict__ w, b3_u4 *__restrict__
 
 // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, NT bf16 MFMAs per product: 3 = the split form, 1 = single pass (hi parts only);
 // ST = 2: the 1x1 at stride 2 (tile and window in the OUTPUT's grid, even / even source cells: s3_cell_offset; the 3x3 at stride 2 is sconv_b1s2.inc)
-template <int NQ, int RW, int KS, int NT = 3, int ST = 1>
-__device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int tx, int img) {
+template <int NQ, int RW, int KS, int NT = 3, int ST = 1, int GT = 0>      // GT: the gate epilogue (s3_epilogue<RW, 1, 1>, the 1x1 at stride 1)
+__device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int tx, int img, const float *trunk = nullptr) {
     constexpr int NR = 8 / NQ, TR = NR * RW, XR = TR + KS - 1, XC = S3_T + KS - 1, NCELL = XR * XC;
     constexpr int NDMA = b3_ndma(NCELL), BUF = 8 * NDMA * 64, PS = b3_ps(NCELL), NSTEP = KS * KS;
     constexpr int NA = NT == 3 ? 6 : 3;                                     // A operands of a K step: (row tile, hi | lo), or the row tiles' hi parts
@@ -188,6 +188,7 @@ __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int
         if (ck + 1 < nck) chunk(ck + 1, std::integral_constant<int, 1>{});
     }
 #undef B3_WAIT_A
-    if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
+    if constexpr (GT) s3_epilogue<RW, 1, 1>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg, trunk);
+    else if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
     else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
 }

@@ -12,6 +12,8 @@ set_conv_precision(model, "bf16x3") moves the stride-1 fused layers to their spl
 single-pass bf16 forms (operands rounded once, one MFMA per product), per module.  The stride-2 layers stay fp32 in every such mode unless the
 setter's keyword asks otherwise: set_conv_precision(model, precision, stride2="bf16x1") moves them to their own single-pass bf16 forms
 (`lic360.sconv3x3s2_bf16x1` / `sconv1x1s2_bf16x1`, csrc/sconv_b1s2.inc), independently of `precision`.
+set_conv_precision(model, precision, gate="fused") runs the tail of the attention blocks -- the gate's 1x1 convolution, sigmoid, product and sum -- as one launch
+of `lic360.sconv1x1_gate` in the block's precision (csrc/conv3x3_kernels.hip, the gate epilogue); the default, "library", leaves it to torch.
 The first stage's stride-2 layers (3 input channels: no 16-channel chunk, and bound by their output, not by MFMAs), convolutions off the fused
 shapes, small maps and every recording (training) pass are library work (torch -> MIOpen); native around them:
 sphere pad / trim / cut-edge / pixel-shuffle / importance map / quantiser kernels and the one-pass GDN (csrc/gdn_kernels.hip)."""
@@ -85,7 +87,10 @@ S2_BF16X1_1X1_MAX_CELLS = 132 * 260  # lic360.sconv1x1s2_bf16x1 is taken on inpu
 GDN_PRECISIONS = ("fp32", "bf16x3")
 
 
-def set_conv_precision(module, precision, stride2="fp32", gdn="fp32"):
+GATE_MODES = ("library", "fused")
+
+
+def set_conv_precision(module, precision, stride2="fp32", gdn="fp32", gate="library"):
     """arithmetic of the fused convolutions of every block under `module` (module.modules()): "fp32" (the default: lic360.sconv3x3 / sconv1x1),
     "bf16x3" (their split-bf16 forms wherever those take the layer's shape, the fp32 kernel elsewhere; about 2^-16 relative error per product) or
     "bf16x1" (their single-pass bf16 forms under the same shape rule: every input value and weight rounded once to bf16, one MFMA per product, fp32
@@ -97,6 +102,9 @@ def set_conv_precision(module, precision, stride2="fp32", gdn="fp32"):
     The GDNs do not follow `precision` either: they stay on the fp32 one-pass kernel (lic360.gdn_forward) unless gdn="bf16x3" moves those of a supported
     channel count to the split-bf16 form (lic360.gdn_bf16x3_forward, csrc/gdn_bf16x3.inc: 2^-15 relative per element against the float64 GDN); a later
     call without the keyword returns them to fp32.
+    The gate of the attention blocks -- its 1x1 convolution, the sigmoid, the product with the trunk and the sum with the input -- stays on the library
+    (MIOpen / rocBLAS + three elementwise kernels) unless gate="fused" moves it to one launch of lic360.sconv1x1_gate (or its bf16x3 / bf16x1 form, following
+    `precision`) wherever the block is on its fused path; a later call without the keyword returns it to "library".
     A per-module setting, not a global: several copies of the networks may run side by side in different modes.  Library layers, small maps and
     recording passes are the same in either mode.  Returns `module`."""
     if precision not in CONV_PRECISIONS:
@@ -105,10 +113,13 @@ def set_conv_precision(module, precision, stride2="fp32", gdn="fp32"):
         raise ValueError("stride-2 conv precision must be one of %s, got %r" % (STRIDE2_PRECISIONS, stride2))
     if gdn not in GDN_PRECISIONS:
         raise ValueError("GDN precision must be one of %s, got %r" % (GDN_PRECISIONS, gdn))
+    if gate not in GATE_MODES:
+        raise ValueError("gate mode must be one of %s, got %r" % (GATE_MODES, gate))
     for m in module.modules():
         m._conv_precision = precision
         m._stride2_precision = stride2
         m._gdn_precision = gdn
+        m._gate_mode = gate
     return module
 
 
@@ -133,6 +144,17 @@ def _sconv(mod, conv, x, slope, residual, out, **kw):
         precision = "fp32"
     fn, pack, _ = _SCONV[ks, precision]
     return getattr(lic360, fn)(x, _packed(conv, precision, pack), conv.bias, slope, residual, out, **kw)
+
+
+def _sconv_gate(mod, conv, x, trunk, residual, out, **kw):
+    """the gate launch of block `mod` on its 1x1 convolution `conv`, in the block's precision under _sconv's rule (the form's predicate, else fp32): the 1x1
+    names of _SCONV with `_gate` behind `sconv1x1`, on the pack the 1x1 form of that precision caches"""
+    precision = getattr(mod, "_conv_precision", "fp32")
+    cout, cin = conv.weight.shape[:2]
+    if precision != "fp32" and not getattr(lic360, _SCONV[1, precision][2])(cin, cout):
+        precision = "fp32"
+    fn, pack, _ = _SCONV[1, precision]
+    return getattr(lic360, fn.replace("sconv1x1", "sconv1x1_gate"))(x, _packed(conv, precision, pack), conv.bias, trunk, residual, out, **kw)
 
 
 def _packed(conv, precision, pack):
@@ -212,8 +234,26 @@ class AttentionBlock(nn.Module):
 
     def forward(self, x):
         if _fusable(self.trunk[0].conv2, x, 2, mod=self.trunk[0]):
+            fused_tail = getattr(self, "_gate_mode", "library") == "fused" and self._gate_fusable(x)
             x = self.trunk[0].pad(x)                                       # the reference's first ResidualBlock refreshes x's apron in place: `x + ...` below carries it
+            if fused_tail:
+                # the tail in one launch: out = x + trunk * sigmoid(conv1x1(a) + bias) on the interior.  On the library path trunk(x) is trimmed to zero, so
+                # the output's apron is x's refreshed apron: sphere_apron_from writes the same values.
+                t, a = self.trunk(x), self.attention[2](self.attention[1](self.attention[0](x)))
+                out = torch.empty_like(x)
+                _sconv_gate(self, self.attention[3], a, t, x, out, ring=2)
+                return lic360.sphere_apron_from(x, out, 2)
         return x + self.trunk(x) * self.attention(x)
+
+    def _gate_fusable(self, x):
+        """may the tail run on lic360.sconv1x1_gate?  (behind _fusable of the first bottleneck: a GPU fp32 map large enough, no gradient for x or that block) --
+        x contiguous as it arrives (its bottlenecks are then on their fused paths too), no gradient recorded for any parameter of the whole block, a gate
+        convolution with a bias and a shape the 1x1 kernel takes"""
+        conv = self.attention[3]
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        cout, cin = conv.weight.shape[:2]
+        return x.is_contiguous() and conv.bias is not None and lic360.sconv1x1_supported(cin, cout)
 
 
 class ResidualBlockV2(nn.Module):

@@ -423,6 +423,21 @@ int lic360_sconv3x3s2_bf16x1(void *stream, const float *x, const void *packed, c
 int lic360_sconv1x1s2_bf16x1_supported(int cin, int cout);   /* == lic360_sconv1x1_bf16x1_supported */
 int lic360_sconv1x1s2_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                              int n, int cin, int cout, int hp, int wp, int pad, int oring);
+/* ---- the gate of the attention blocks in one launch (kernels k_gate_sconv / k_gate_sconv_b3 / k_gate_sconv_b1: the 1x1 stride-1 bodies of the three forms with
+ * a gate epilogue, csrc/conv3x3_kernels.hip), opt-in: replaces the tail of AttentionBlock, test/model_zoo.py:25-46 -- the gate's nn.Conv2d(c, c, 1) + nn.Sigmoid +
+ * the `*` with the trunk + the `+` with the input.  x [n][cin][hp][wp] (the attention branch's last bottleneck output); trunk, residual and out
+ * [n][cout][hp][wp]; on rows [ring, hp - ring) x columns [ring_w, wp - ring_w):
+ *     y = conv1x1(x) + bias (the form's own accumulation);  g = 1.0f / (1.0f + lic360_expf(-y));  out = residual + trunk * g
+ * with one fp32 rounding per operation and no fused multiply-add (lic360_expf: csrc/lic360_exact_math.h, host / device bit-identical, so the epilogue is
+ * reproducible on the CPU bit for bit; g == 1 for y >= 32, g == 0 for y <= -89; NaN and infinity are outside the contract).  The other cells of out are NOT touched.
+ * No PReLU, crop or shuffle.  packed = the form's stride-1 1x1 pack (lic360_sconv1x1_pack / _bf16x3_pack / _bf16x1_pack); shapes, alignments (bias, a bf16
+ * pack: 16 bytes) and refusals are those of lic360_sconv1x1 / _bf16x3 / _bf16x1; trunk and residual are required (a null pointer is refused). */
+int lic360_sconv1x1_gate(void *stream, const float *x, const float *packed, const float *bias, const float *trunk, const float *residual, float *out,
+                         int n, int cin, int cout, int hp, int wp, int ring, int ring_w);
+int lic360_sconv1x1_gate_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
+                                int n, int cin, int cout, int hp, int wp, int ring, int ring_w);
+int lic360_sconv1x1_gate_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
+                                int n, int cin, int cout, int hp, int wp, int ring, int ring_w);
 /* apron of dst <- sphere-wrapped interior of src (src == dst: lic360_sphere_pad_inplace); [nc][hp][wp] planes      sphere_pad_cuda.cu:48-65 */
 int lic360_sphere_apron_from(void *stream, const float *src, float *dst, int nc, int hp, int wp, int pad);
 

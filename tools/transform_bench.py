@@ -3,8 +3,8 @@ TFLOP/s (library convolutions through MIOpen + this package's sphere / shuffle /
 its four-kernel torch form.  Seeded random weights.  Writes one JSON document to stdout.
 --precision {fp32,bf16x3,bf16x1}: the mode of the fused convolutions (lic360_models.set_conv_precision) for every row; --ab: only the analysis and
 synthesis transforms, ms per image in all three modes, in "bf16x1" with the stride-2 layers in single-pass bf16 too (stride2="bf16x1": the row
-"bf16x1+s2") and in that mode with the GDNs in split bf16 as well (gdn="bf16x3": the row "bf16x1+s2+gdn"), alternating in one run (one JSON line per
-repeat and a summary)."""
+"bf16x1+s2"), in that mode with the GDNs in split bf16 as well (gdn="bf16x3": the row "bf16x1+s2+gdn") and in that mode with the attention blocks' gate in
+one launch (gate="fused": the row "bf16x1+s2+gdn+gate"), alternating in one run (one JSON line per repeat and a summary)."""
 import json
 import os
 import sys
@@ -200,24 +200,26 @@ def whole_codec_streams(enc, dec, device, batch=48, reps=2, nstreams=2):
 
 
 def ab_transforms(batch=8, device=0, reps=3, repeats=5):
-    """analysis and synthesis ms per image, the fp32, bf16x3 and bf16x1 modes, bf16x1 with stride2="bf16x1" and that mode with gdn="bf16x3" alternating on the
-    same networks and inputs (the synthesis transform has no stride-2 layer: its fourth row is the control for drift; the fifth row against the fourth is the
-    split-bf16 GDN against the fp32 one-pass GDN under the same convolutions)"""
+    """analysis and synthesis ms per image, the fp32, bf16x3 and bf16x1 modes, bf16x1 with stride2="bf16x1", that mode with gdn="bf16x3" and that mode with
+    gate="fused" alternating on the same networks and inputs (the synthesis transform has no stride-2 layer: its fourth row is the control for drift; the fifth
+    row against the fourth is the split-bf16 GDN against the fp32 one-pass GDN under the same convolutions; the sixth against the fifth is the attention blocks'
+    fused gate against their library tail)"""
     import lic360_models as lm
     dev = "cuda:%d" % device
     torch.manual_seed(0)
     enc, dec = lm.CMP_Encoder(gpu_id=device).to(dev).eval(), lm.CMP_Decoder(gpu_id=device).to(dev).eval()
-    modes = [(p, p, "fp32", "fp32") for p in lm.CONV_PRECISIONS] + [("bf16x1+s2", "bf16x1", "bf16x1", "fp32"),
-                                                                      ("bf16x1+s2+gdn", "bf16x1", "bf16x1", "bf16x3")]      # row name, precision, stride2, gdn
-    t = {(m, k): [] for m, _, _, _ in modes for k in ("analysis", "synthesis")}
+    modes = [(p, p, "fp32", "fp32", "library") for p in lm.CONV_PRECISIONS] + [("bf16x1+s2", "bf16x1", "bf16x1", "fp32", "library"),
+                                                                                 ("bf16x1+s2+gdn", "bf16x1", "bf16x1", "bf16x3", "library"),
+                                                                                 ("bf16x1+s2+gdn+gate", "bf16x1", "bf16x1", "bf16x3", "fused")]      # row name, precision, stride2, gdn, gate
+    t = {(m, k): [] for m, _, _, _, _ in modes for k in ("analysis", "synthesis")}
     with torch.no_grad():
         img = torch.rand((batch, 3, 512, 1024), device=dev)
         code, mask, _ = enc(img)
         for i in range(repeats):
-            for m, p, s2, g in modes:
-                lm.set_conv_precision(enc, p, stride2=s2, gdn=g)
-                lm.set_conv_precision(dec, p, stride2=s2, gdn=g)
-                row = {"repeat": i, "precision": p, "stride2": s2, "gdn": g, "batch": batch}
+            for m, p, s2, g, gt in modes:
+                lm.set_conv_precision(enc, p, stride2=s2, gdn=g, gate=gt)
+                lm.set_conv_precision(dec, p, stride2=s2, gdn=g, gate=gt)
+                row = {"repeat": i, "precision": p, "stride2": s2, "gdn": g, "gate": gt, "batch": batch}
                 for k, fn in (("analysis", lambda: enc(img)), ("synthesis", lambda: dec(code, mask))):
                     row[k + "_ms_per_image"] = timed(fn, reps) / batch * 1e3
                     t[(m, k)].append(row[k + "_ms_per_image"])
