@@ -254,9 +254,14 @@ constexpr int s3_xc(int ks, int st) { return st == 2 && ks == 3 ? 2 * S3_T + 1 :
 constexpr int s3_pitch_st(int tr, int ks, int st) { return st == 2 && ks == 3 ? (s3_xr(tr, ks, st) * s3_xc(ks, st)) | 1 : s3_pitch(tr, ks); }
 constexpr int s3_ndma_st(int tr, int ks, int st) { return (s3_ck(ks) * s3_pitch_st(tr, ks, st) + 511) / 512; }
 constexpr int s3_lds_st(int tr, int ks, int st) { return 2 * 8 * s3_ndma_st(tr, ks, st) * 64; }
-template <int NQ, int RW, int KS, int ST = 1, int GT = 0>                   // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, stride ST; GT: the gate epilogue
+// PQ: the NQ of the weight pack's channel blocks.  PQ > NQ is a "narrow" workgroup (k_narrow_conv / k_narrow_gate below): blockIdx.y counts blocks of NQ * 48
+// channels, PQ / NQ of them per pack block; the workgroup reads the pack as it is, its waves at mq slots (blockIdx.y % (PQ / NQ)) * NQ + mq of pack block blockIdx.y / (PQ / NQ)
+template <int NQ, int RW, int KS, int ST = 1, int GT = 0, int PQ = NQ>      // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, stride ST; GT: the gate epilogue
 __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int tx, int img, const float *trunk = nullptr) {
-    constexpr int PD = KS == 3 ? 1 : 3;                                     // A operands PD pairs ahead: a 1x1 pair is 24 MFMAs (768 cycles), its operand is fetched three pairs ahead
+    constexpr int PD = KS == 3 && RW > 3 ? 1 : 3;                           // A operands PD pairs ahead: a 1x1 pair is 24 MFMAs (768 cycles), its operand is fetched three pairs ahead;
+                                                                            // so is that of the 3x3 at RW = 2 / 3 (the narrow NQ = 1 form: 18 / 27 MFMAs per pair) -- by
+                                                                            // that MFMA count alone: the depth of those bodies has not been measured against one pair
+    static_assert(PQ % NQ == 0 && PQ >= NQ, "a narrow workgroup takes a whole fraction of a pack block");
     constexpr int NR = 8 / NQ, TR = NR * RW;                                // row groups per workgroup, tile rows
     constexpr int S3_CK = s3_ck(KS), NPAIR = S3_CK / 4 * KS, NA4 = s3_na4(KS), S3_XC = s3_xc(KS, ST);
     constexpr int S3_PL = s3_pitch_st(TR, KS, ST), S3_NDMA = s3_ndma_st(TR, KS, ST), S3_BUF = 8 * S3_NDMA * 64, S3_XR = s3_xr(TR, KS, ST);
@@ -269,7 +274,7 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), mq = wave % NQ, nh = wave / NQ;
     // input-grid cell of the tile's first output (a.rw: rows per wave of the ordinary tile rows); ST = 2: its interior coordinates in the output
     const int tr0 = (ST == 1 ? a.ring : 0) + ty * (NR * a.rw), tc0 = (ST == 1 ? a.ringw : 0) + tx * S3_T;
-    const int blk = blockIdx.y, cblk = NQ * 48;
+    const int blk = PQ == NQ ? blockIdx.y : blockIdx.y / (PQ / NQ), pmq = PQ == NQ ? mq : (int)(blockIdx.y % (PQ / NQ)) * NQ + mq, cblk = PQ * 48;   // pack block, mq slot in it
     const long PLg = (long)a.hp * a.wp;
     unsigned voff[S3_NDMA];
 #pragma unroll                                                              // (s3_cell_offsets' loop, in place: see there)
@@ -287,9 +292,9 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
     // L2 latency exposed twice per pair; here the three 16-byte loads of pair it + 1 are issued at the top of pair it and waited for at the
     // top of pair it + 1).  In-order counter: a chunk's 11 DMAs are issued BEHIND the A loads of its first pair, so `vmcnt(11)` at the second
     // pair waits for the operands only and the DMAs have two pairs (~9000 cycles) before a `vmcnt(0)` asks for them.
-    const char *wl = (const char *)((const s3_f4 *)a.w + ((long)blk * (a.cin / 4) * KS * NQ + mq) * NA4 * 64 + lane);   // + it * NQ * NA4 KB per (cg, kw) pair
+    const char *wl = (const char *)((const s3_f4 *)a.w + ((long)blk * (a.cin / 4) * KS * PQ + pmq) * NA4 * 64 + lane);   // + it * PQ * NA4 KB per (cg, kw) pair
     auto load_a = [&](int it, s3_f4 (&A)[3]) __attribute__((always_inline)) {
-        const char *p = wl + (long)it * (NQ * NA4 * 1024);
+        const char *p = wl + (long)it * (PQ * NA4 * 1024);
         if constexpr (NA4 == 3)
             asm volatile("global_load_dwordx4 %0, %3, off\n\tglobal_load_dwordx4 %1, %3, off offset:1024\n\tglobal_load_dwordx4 %2, %3, off offset:2048"
                          : "=&v"(A[0]), "=&v"(A[1]), "=&v"(A[2]) : "v"(p));
@@ -307,8 +312,8 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
 #pragma unroll
         for (int r = 0; r < RW; ++r) acc[m][r] = (s3_f4){0.f, 0.f, 0.f, 0.f};
     issue_dma(0);
-    // operand ring: PD + 1 sets, pair `it` in set it % (PD + 1).  The wide tiles run one pair ahead (a pair is 72 MFMAs = 2304 cycles per wave);
-    // the 2-row remainder tiles have 9 MFMAs per pair and would wait a full L2 round trip per pair: they run five ahead.
+    // operand ring: PD + 1 sets, pair `it` in set it % (PD + 1).  The 3x3 tiles of RW >= 4 run one pair ahead (a pair is 72 MFMAs = 2304 cycles per wave at RW = 8);
+    // the 1x1 and the 3x3 at RW = 2 / 3 run three ahead (PD above).
     s3_f4 A[PD + 1][3];
 #pragma unroll
     for (int d = 0; d < PD; ++d) load_a(d < niter ? d : niter - 1, A[d]);
@@ -351,33 +356,35 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
         __syncthreads();
     }
 #undef S3_WAIT_A
-    if constexpr (GT) s3_epilogue<RW, 1, 1>(a, acc, img, tr0, tc0, blk * cblk + 48 * mq, nh, col, kq, PLg, trunk);
-    else if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
-    else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * cblk + 48 * mq, nh, col, kq, PLg);
+    if constexpr (GT) s3_epilogue<RW, 1, 1>(a, acc, img, tr0, tc0, blk * cblk + 48 * pmq, nh, col, kq, PLg, trunk);
+    else if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * cblk + 48 * pmq, nh, col, kq, PLg);
+    else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * cblk + 48 * pmq, nh, col, kq, PLg);
 }
 
 #include "sconv_bf16x3.inc"          // b3_body: the split-bf16 and single-pass bf16 forms of s3_body (arithmetic, pack kernel); everything around the bodies is below
 #include "sconv_b1s2.inc"            // b1s2_body: the single-pass bf16 form of the 3x3 at stride 2 (a register-path loader into a double-buffered bf16 image)
 
 // ---- one workgroup wrapper, one launch for all forms.  NT = bf16 MFMAs per product: 0 the fp32 body, 3 the split-bf16 body, 1 its single-pass form.
-template <int NT, int NQ, int RW, int KS>
+template <int NT, int NQ, int RW, int KS, int PQ = NQ>
 __device__ __forceinline__ void sconv_body(const S3Args &a, float *lds, int ty, int tx, int img) {
-    if constexpr (NT == 3) b3_body<NQ, RW, KS>(a, lds, ty, tx, img);
-    else if constexpr (NT == 1) b3_body<NQ, RW, KS, 1>(a, lds, ty, tx, img);
-    else s3_body<NQ, RW, KS>(a, lds, ty, tx, img);
+    if constexpr (NT == 3) b3_body<NQ, RW, KS, 3, 1, 0, PQ>(a, lds, ty, tx, img);
+    else if constexpr (NT == 1) b3_body<NQ, RW, KS, 1, 1, 0, PQ>(a, lds, ty, tx, img);
+    else s3_body<NQ, RW, KS, 1, 0, PQ>(a, lds, ty, tx, img);
 }
+// the tall last tile row exists where its LDS fits: not in the split-bf16 form at NQ = 1, whose 24-row tile would need 183 KB (sconv_plan leaves tall_last 0 there)
+constexpr bool sconv_tall(int nt, int nq, int ks) { return ks == 3 && !(nt == 3 && nq == 1); }
 // A window of 16 k + 2 rows (every 1-ring window of these maps) would need a seventeenth tile row with 14 dead rows; instead its LAST tile row
 // runs one more row per wave (18 rows at 192 channels, 20 at 96): the workgroup picks its body by its tile row (uniform per workgroup).
-template <int NT, int NQ, int RW, int KS>
+template <int NT, int NQ, int RW, int KS, int PQ = NQ>
 __device__ __forceinline__ void sconv_workgroup(const S3Args &a) {
-    constexpr int TR = 8 / NQ * (RW + (KS == 3 ? 1 : 0));                   // rows of the tallest tile
+    constexpr int TR = 8 / NQ * (RW + (sconv_tall(NT, NQ, KS) ? 1 : 0));    // rows of the tallest tile
     __shared__ __attribute__((aligned(16))) float lds[NT ? b3_lds(TR, KS, NT) : s3_lds(TR, KS)];
     static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
     const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
-    if constexpr (KS == 3) {
-        if (a.tall_last && ty == a.tiles_y - 1) { sconv_body<NT, NQ, RW + 1, 3>(a, lds, ty, tx, img); return; }
+    if constexpr (sconv_tall(NT, NQ, KS)) {
+        if (a.tall_last && ty == a.tiles_y - 1) { sconv_body<NT, NQ, RW + 1, 3, PQ>(a, lds, ty, tx, img); return; }
     }
-    sconv_body<NT, NQ, RW, KS>(a, lds, ty, tx, img);
+    sconv_body<NT, NQ, RW, KS, PQ>(a, lds, ty, tx, img);
 }
 // the stride-2 workgroup (NT = 0: the fp32 form, 1: the single-pass bf16 form): no tall last tile row -- (2 (TR + NR) + 1) x 33 halos do not fit LDS twice -- a
 // remainder takes an ordinary tile row
@@ -413,14 +420,14 @@ struct S3GateArgs {
     S3Args a;
     const float *trunk;                              // [n][cout][hp][wp], as a.res and a.out
 };
-template <int NT, int NQ, int RW>
+template <int NT, int NQ, int RW, int PQ = NQ>
 __device__ __forceinline__ void sconv_gate_workgroup(const S3GateArgs &g) {
     const S3Args &a = g.a;
     __shared__ __attribute__((aligned(16))) float lds[NT ? b3_lds(8 / NQ * RW, 1, NT) : s3_lds(8 / NQ * RW, 1)];
     static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
     const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
-    if constexpr (NT == 0) s3_body<NQ, RW, 1, 1, 1>(a, lds, ty, tx, img, g.trunk);
-    else b3_body<NQ, RW, 1, NT, 1, 1>(a, lds, ty, tx, img, g.trunk);
+    if constexpr (NT == 0) s3_body<NQ, RW, 1, 1, 1, PQ>(a, lds, ty, tx, img, g.trunk);
+    else b3_body<NQ, RW, 1, NT, 1, 1, PQ>(a, lds, ty, tx, img, g.trunk);
 }
 template <int NQ, int RW> __global__ __launch_bounds__(S3_THREADS) void k_gate_sconv(S3GateArgs g) { sconv_gate_workgroup<0, NQ, RW>(g); }
 template <int NQ, int RW> __global__ __launch_bounds__(S3_THREADS) void k_gate_sconv_b3(S3GateArgs g) { sconv_gate_workgroup<3, NQ, RW>(g); }
@@ -431,6 +438,18 @@ static auto sconv_gate_kernel() {
     else if constexpr (NT == 1) return &k_gate_sconv_b1<NQ, RW>;
     else return &k_gate_sconv<NQ, RW>;
 }
+// ---- the narrow workgroups (k_narrow_conv / k_narrow_gate; lic360_sconv_narrow / lic360_sconv1x1_gate_narrow, opt-in: lic360_models.set_conv_precision(.., small="narrow")).
+// A workgroup of the kernels above takes a whole pack block of output channels (192, or 96 at cout = 96), so a launch has as many workgroups as tiles: 128 on a
+// 132 x 260 map, 8 on a 36 x 68 one.  A narrow workgroup takes `cpw` = 96 or 48 of them -- the stride-1 bodies at NQ = 2, RW = 4 resp. NQ = 1, RW = 2 (8 row
+// groups; the tall last tile row: RW = 3, 24 rows) with PQ = the pack's NQ -- and the launch has cout / cpw times as many; each re-reads the tile's input (it fits L2)
+// and, in the bf16 forms, repeats the chunk's conversion pass.  Same packs, loaders, epilogues, sphere rule, crop and shuffled store: an output's sequence of K steps
+// is that of the wide kernel, so the results are bit-identical to it.  The argument struct is S3Args in a wrapper of the kernels' own: tests/test_asm_gate_kernels.py
+// counts the kernels whose argument type is S3Args itself, tests/test_asm_load_hazards.py those of the k_sconv prefix.
+struct S3NarrowArgs {
+    S3Args a;
+};
+template <int NT, int NQ, int RW, int KS, int PQ> __global__ __launch_bounds__(S3_THREADS) void k_narrow_conv(S3NarrowArgs g) { sconv_workgroup<NT, NQ, RW, KS, PQ>(g.a); }
+template <int NT, int NQ, int RW, int PQ> __global__ __launch_bounds__(S3_THREADS) void k_narrow_gate(S3GateArgs g) { sconv_gate_workgroup<NT, NQ, RW, PQ>(g); }
 
 // the forms differ in their chunk of input channels (and so in the shapes they take), in the pack, and in the body
 static inline int sconv_ck(int nt, int ks) { return nt ? B3_CK : s3_ck(ks); }
@@ -457,7 +476,8 @@ static int b3_pack(int nt, void *stream, const float *weight, void *packed, int 
 // the argument contract, tile geometry and grid of a stride-1 launch (sconv_launch, and sconv_gate_launch with ks = 1, crop = 0, shuffle = 0)
 template <int NT>
 static int sconv_plan(const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle, S3Args &a, dim3 &grid) {
+                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle, S3Args &a, dim3 &grid,
+                      int cpw = 0) {                                        // != 0: a narrow launch, `cpw` channels per workgroup (sconv_narrow_ok holds)
     ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(NT, cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w &&
               out_crop >= 0 && out_crop <= ring && sphere >= 0 && sphere <= 2);
     ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
@@ -469,13 +489,13 @@ static int sconv_plan(const float *x, const void *packed, const float *bias, con
     a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = ring; a.ringw = ring_w;
     a.ooff = out_crop; a.ohp = hp - 2 * out_crop; a.owp = wp - 2 * out_crop; a.shuffle = shuffle;
     a.tiles_x = (wp - 2 * ring_w + S3_T - 1) / S3_T;
-    const int nq = cout % 192 == 0 ? 4 : 2, nrg = 8 / nq, nr = hp - 2 * ring, full = nr / S3_T, rem = nr - full * S3_T;
+    const int nq = cpw ? cpw / 48 : cout % 192 == 0 ? 4 : 2, nrg = 8 / nq, nr = hp - 2 * ring, full = nr / S3_T, rem = nr - full * S3_T;
     a.rw = S3_T / nrg;
-    a.tall_last = ks == 3 && rem > 0 && rem <= nrg && full > 0;             // the remainder fits one more row per wave of the last tile row
+    a.tall_last = sconv_tall(NT, nq, ks) && rem > 0 && rem <= nrg && full > 0;   // the remainder fits one more row per wave of the last tile row
     a.tiles_y = a.tall_last ? full : (nr + S3_T - 1) / S3_T;
     const long tiles = (long)n * a.tiles_x * a.tiles_y;
-    ARG_CHECK(tiles < (1L << 31));
-    grid = dim3((unsigned)tiles, nq == 4 ? cout / 192 : 1);
+    ARG_CHECK(tiles < (1L << 31) && (!cpw || cout / cpw < 65536));
+    grid = dim3((unsigned)tiles, cpw ? cout / cpw : nq == 4 ? cout / 192 : 1);
     return 0;
 }
 template <int NT>
@@ -503,6 +523,35 @@ static int sconv_gate_launch(void *stream, const float *x, const void *packed, c
     g.trunk = trunk;
     if (cout % 192 == 0) hipLaunchKernelGGL((sconv_gate_kernel<NT, 4, 8>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
     else hipLaunchKernelGGL((sconv_gate_kernel<NT, 2, 4>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
+    LAUNCH_CHECK();
+    return 0;
+}
+// the narrow launches: a form the three bodies have, 48 or 96 channels per workgroup and fewer than the pack's block (192 where cout is a multiple of 192, else 96)
+static inline bool sconv_narrow_ok(int form, int ks, int cin, int cout, int cpw) {
+    return (form == 0 || form == 3 || form == 1) && (cpw == 48 || cpw == 96) && sconv_ok(form, cin, cout, ks) && cpw < (cout % 192 == 0 ? 192 : 96);
+}
+template <int NT, int KS>
+static int sconv_narrow_launch(void *stream, int cpw, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
+                               int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
+    S3NarrowArgs g;
+    dim3 grid;
+    if (const int rc = sconv_plan<NT>(x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, KS, shuffle, g.a, grid, cpw)) return rc;
+    if (cpw == 96) hipLaunchKernelGGL((k_narrow_conv<NT, 2, 4, KS, 4>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
+    else if (cout % 192 == 0) hipLaunchKernelGGL((k_narrow_conv<NT, 1, 2, KS, 4>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((k_narrow_conv<NT, 1, 2, KS, 2>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
+    LAUNCH_CHECK();
+    return 0;
+}
+template <int NT>
+static int sconv_gate_narrow_launch(void *stream, int cpw, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
+                                    int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
+    ARG_CHECK(trunk && residual);
+    S3GateArgs g;
+    dim3 grid;
+    if (const int rc = sconv_plan<NT>(x, packed, bias, nullptr, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, 0, 1, 0, g.a, grid, cpw)) return rc;
+    g.trunk = trunk;
+    if (cpw == 96) hipLaunchKernelGGL((k_narrow_gate<NT, 2, 4, 4>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((k_narrow_gate<NT, 1, 2, 4>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
     LAUNCH_CHECK();
     return 0;
 }
@@ -618,4 +667,23 @@ LIC360_API int lic360_sconv1x1s2_bf16x1_supported(int cin, int cout) { return sc
 LIC360_API int lic360_sconv1x1s2_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                         int n, int cin, int cout, int hp, int wp, int pad, int oring) {
     return sconv_s2_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, 0, oring, 1);
+}
+// the narrow workgroups (above: "the narrow workgroups"): one entry point for the stride-1 convolutions of every form and kernel size, one for the gate.  form: 0 fp32,
+// 3 split-bf16, 1 single-pass bf16; `packed` is the form's ordinary pack of that kernel size; ks = 1 takes pad = 0, sphere = 0.  Refusals precede any launch.
+LIC360_API int lic360_sconv_narrow_supported(int form, int ks, int cin, int cout, int cpw) { return sconv_narrow_ok(form, ks, cin, cout, cpw) ? 1 : 0; }
+LIC360_API int lic360_sconv_narrow(void *stream, int form, int ks, int cpw, const float *x, const void *packed, const float *bias, const float *slope, const float *residual,
+                                   float *out, int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
+    ARG_CHECK(sconv_narrow_ok(form, ks, cin, cout, cpw) && (ks == 3 || (pad == 0 && sphere == 0)));
+#define NARROW_CASE(NT, KS) \
+    if (form == NT && ks == KS) return sconv_narrow_launch<NT, KS>(stream, cpw, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, shuffle)
+    NARROW_CASE(0, 3); NARROW_CASE(0, 1); NARROW_CASE(3, 3); NARROW_CASE(3, 1); NARROW_CASE(1, 3);
+#undef NARROW_CASE
+    return sconv_narrow_launch<1, 1>(stream, cpw, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, shuffle);
+}
+LIC360_API int lic360_sconv1x1_gate_narrow(void *stream, int form, int cpw, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual,
+                                           float *out, int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
+    ARG_CHECK(sconv_narrow_ok(form, 1, cin, cout, cpw) && cout % 192 == 0);
+    if (form == 0) return sconv_gate_narrow_launch<0>(stream, cpw, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
+    if (form == 3) return sconv_gate_narrow_launch<3>(stream, cpw, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
+    return sconv_gate_narrow_launch<1>(stream, cpw, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
 }

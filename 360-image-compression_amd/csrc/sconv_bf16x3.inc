@@ -79,7 +79,7 @@ __global__ void k_sconv_b3_pack(const float *__restrict__ w, b3_u4 *__restrict__
 
 // NQ * 48 output channels per workgroup, RW rows per wave, KS x KS taps, NT bf16 MFMAs per product: 3 = the split form, 1 = single pass (hi parts only);
 // ST = 2: the 1x1 at stride 2 (tile and window in the OUTPUT's grid, even / even source cells: s3_cell_offset; the 3x3 at stride 2 is sconv_b1s2.inc)
-template <int NQ, int RW, int KS, int NT = 3, int ST = 1, int GT = 0>      // GT: the gate epilogue (s3_epilogue<RW, 1, 1>, the 1x1 at stride 1)
+template <int NQ, int RW, int KS, int NT = 3, int ST = 1, int GT = 0, int PQ = NQ>   // GT: the gate epilogue (s3_epilogue<RW, 1, 1>, the 1x1 at stride 1); PQ: the pack's NQ (s3_body)
 __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int tx, int img, const float *trunk = nullptr) {
     constexpr int NR = 8 / NQ, TR = NR * RW, XR = TR + KS - 1, XC = S3_T + KS - 1, NCELL = XR * XC;
     constexpr int NDMA = b3_ndma(NCELL), BUF = 8 * NDMA * 64, PS = b3_ps(NCELL), NSTEP = KS * KS;
@@ -92,24 +92,32 @@ __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), mq = wave % NQ, nh = wave / NQ;
     const int tr0 = (ST == 1 ? a.ring : 0) + ty * (NR * a.rw), tc0 = (ST == 1 ? a.ringw : 0) + tx * S3_T;
-    const int blk = blockIdx.y;
+    const int blk = PQ == NQ ? blockIdx.y : blockIdx.y / (PQ / NQ), pmq = PQ == NQ ? mq : (int)(blockIdx.y % (PQ / NQ)) * NQ + mq;   // pack block, mq slot in it
     const long PLg = (long)a.hp * a.wp;
     unsigned voff[NDMA];
-    s3_cell_offsets<NDMA, B3_CK, NCELL, XR, XC, KS, ST>(a, tr0, tc0, wave, lane, PLg, voff);
+    if constexpr (PQ == NQ) s3_cell_offsets<NDMA, B3_CK, NCELL, XR, XC, KS, ST>(a, tr0, tc0, wave, lane, PLg, voff);
+    else {                                                                  // (narrow: one offset finished before the next begins -- the 30 of the 24-row tile otherwise keep their lane masks in scalars)
+#pragma unroll
+        for (int i = 0; i < NDMA; ++i) {
+            voff[i] = s3_cell_offset<B3_CK, NCELL, XR, XC, KS, ST>(a, tr0, tc0, (i * 8 + wave) * 64 + lane, PLg);
+            asm volatile("" : "+v"(voff[i]));
+        }
+    }
     const float *xb = a.x + (long)img * a.cin * PLg;
     const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) const float *)&xs[0][0];
     auto issue_dma = [&](const float *sb0, int buf) __attribute__((always_inline)) {
         const float *sb = s3_uniform(sb0);
-        const unsigned lb = lds0 + (unsigned)(buf * BUF + wave * 64) * 4u;
+        unsigned lb = lds0 + (unsigned)(buf * BUF + wave * 64) * 4u;
+        if constexpr (PQ != NQ) asm volatile("" : "+s"(lb));               // (narrow: the NDMA LDS addresses are made per call, not kept in as many scalar registers across the chunk loop)
 #pragma unroll
         for (int i = 0; i < NDMA; ++i) s3_dma(voff[i], sb, lb + (unsigned)(i * 8 * 64 * 4));
     };
     const int nck = a.cin / B3_CK, niter = nck * NSTEP;
     // A operands: six 16-byte loads per lane and K step (two address registers: the offset field stops at 4 KiB; NT = 1: three loads, one register), one
     // step ahead, waited for by counted vmcnt as in the fp32 body: the chunk's DMAs are issued behind the loads of its second step, so the wait at step 1 skips them
-    const char *wl = (const char *)a.w + (((long)blk * niter * NQ + mq) * NA * 64 + lane) * 16;   // + it * NQ * NA KiB per K step
+    const char *wl = (const char *)a.w + (((long)blk * niter * PQ + pmq) * NA * 64 + lane) * 16;   // + it * PQ * NA KiB per K step
     auto load_a = [&](int it, b3_u4 (&A)[NA]) __attribute__((always_inline)) {
-        const char *p = wl + (long)it * (NQ * NA * 1024);
+        const char *p = wl + (long)it * (PQ * NA * 1024);
         if constexpr (NA == 6) {
             const char *q = p + 3072;
             asm volatile("global_load_dwordx4 %0, %6, off\n\tglobal_load_dwordx4 %1, %6, off offset:1024\n\tglobal_load_dwordx4 %2, %6, off offset:2048\n\t"
@@ -188,7 +196,7 @@ __device__ __forceinline__ void b3_body(const S3Args &a, float *lds, int ty, int
         if (ck + 1 < nck) chunk(ck + 1, std::integral_constant<int, 1>{});
     }
 #undef B3_WAIT_A
-    if constexpr (GT) s3_epilogue<RW, 1, 1>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg, trunk);
-    else if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
-    else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * NQ * 48 + 48 * mq, nh, col, kq, PLg);
+    if constexpr (GT) s3_epilogue<RW, 1, 1>(a, acc, img, tr0, tc0, blk * PQ * 48 + 48 * pmq, nh, col, kq, PLg, trunk);
+    else if constexpr (ST == 1) s3_epilogue<RW>(a, acc, img, tr0, tc0, blk * PQ * 48 + 48 * pmq, nh, col, kq, PLg);
+    else s3_epilogue<RW, ST>(a, acc, img, a.ring + tr0, a.ringw + tc0, blk * PQ * 48 + 48 * pmq, nh, col, kq, PLg);
 }

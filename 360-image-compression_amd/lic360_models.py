@@ -53,7 +53,50 @@ def _fusable(conv, x, ring, ring_w=None, mod=None):
     nr, nc = hp - 2 * ring, wp - 2 * (ring if ring_w is None else ring_w)
     rows = nr // 16 if 0 < nr % 16 <= (2 if cout % 192 == 0 else 4) and nr >= 16 else (nr + 15) // 16      # (a short remainder rides on the last tile row)
     tiles = n * rows * ((nc + 15) // 16) * (cout // 192 if cout % 192 == 0 else 1)
-    return tiles >= FUSED_MIN_WORKGROUPS and tiles >= FUSED_MIN_FILL * 256 * ((tiles + 255) // 256)
+    if tiles >= FUSED_MIN_WORKGROUPS and tiles >= FUSED_MIN_FILL * 256 * ((tiles + 255) // 256):
+        return True
+    # refused for its workgroup count alone: with small="narrow" the layer is retried on narrow workgroups (_narrow_cpw)
+    return getattr(mod, "_small_mode", "library") == "narrow" and _narrow_cpw(mod, 3, cin, cout, n, nr, nc) is not None
+
+
+SMALL_MODES = ("library", "narrow")
+NARROW_CPWS = (96, 48)              # output channels per workgroup of lic360.sconv3x3_narrow / sconv1x1_narrow / sconv1x1_gate_narrow, widest first
+NARROW_MIN_WORKGROUPS = 256         # the count rule of the narrow launches is _fusable's (FUSED_MIN_WORKGROUPS, FUSED_MIN_FILL).  A floor of 128 was measured and not taken
+                                    # (tools/conv3x3_probe.py --narrow, profiles/sconv_narrow_probe.json; median ms, narrow against library): at batch 1 on 68 x 132 the fp32 3x3
+                                    # layers lose at 128 workgroups (cpw 48: V2 conv1 0.137 against 0.092, conv2 0.099 / 0.097, GDN conv2 0.098 / 0.086) while bf16x3 / bf16x1
+                                    # win (0.047 / 0.039 against 0.092); the bottleneck at 36 x 68, batch 8, wins in every form (3x3 fp32 0.053 against 0.061).  A per-form floor
+                                    # is a lead; one rule for all forms keeps 256.
+NARROW_ROUTED_BACK = {("fp32", 3, 96, True)}    # (precision, kernel size, cpw, tall last tile row?) that the count rule admits and the measurement routes back to the
+                                    # library: the fp32 3x3 at cpw 96 with a 20-row last tile row -- ResidualBlockV2.conv1 on 132 x 260 at batch 1 -- ran 0.218 ms (0.218 - 0.228)
+                                    # against the library's 0.254 (0.252 - 0.290): 0.036 apart, inside the spreads added (0.048).  Without the tall row (conv2, GDN conv2: 0.194 /
+                                    # 0.181 against 0.264 / 0.242) and in bf16x3 / bf16x1 (0.072 / 0.045) the same layer passes.  A routed-back layer is not retried narrower
+                                    # (cpw 48 there: 0.268); ResidualBlockV2 asks _fusable for its conv1, so in fp32 that block stays on the library at that shape.
+
+
+def _narrow_cpw(mod, ks, cin, cout, n, nr, nc):
+    """the channels per workgroup at which a stride-1 layer (ks x ks, cin -> cout, a window of nr x nc cells on n images) of block `mod` runs on narrow workgroups, or
+    None: the block asks for them (set_conv_precision(.., small="narrow")), the wide launch fails the count rule of _fusable (a map the wide kernel takes makes no
+    narrow call), and `cpw` is the widest of NARROW_CPWS that the narrow form of the block's precision (else fp32: _sconv's rule) takes and whose workgroup count --
+    tiles x cout / cpw, the tall last tile row by the narrow form's own rule -- passes the same count rule (NARROW_MIN_WORKGROUPS), unless the measurement routed that
+    (precision, ks, cpw, tall) back (NARROW_ROUTED_BACK).  A block goes one way on _fusable's question about ONE of its 3x3 layers; each of its layers then asks for
+    itself, with its own kernel size and window.  A sibling whose own narrow count fails where the asked layer's passed would run the wide kernel below the count
+    rule; no production block has such a sibling (their layers share one window up to the 1-ring, and the counts above are taken per 16-row tile)."""
+    if getattr(mod, "_small_mode", "library") != "narrow" or nr <= 0 or nc <= 0:
+        return None
+    wide_ok = lambda wg: wg >= FUSED_MIN_WORKGROUPS and wg >= FUSED_MIN_FILL * 256 * ((wg + 255) // 256)
+    count_ok = lambda wg: wg >= NARROW_MIN_WORKGROUPS and wg >= FUSED_MIN_FILL * 256 * ((wg + 255) // 256)
+    is_tall = lambda nrg, tall: bool(tall and 0 < nr % 16 <= nrg and nr >= 16)
+    tiles = lambda nrg, tall: n * (nr // 16 if is_tall(nrg, tall) else (nr + 15) // 16) * ((nc + 15) // 16)
+    if wide_ok(tiles(2 if cout % 192 == 0 else 4, ks == 3) * (cout // 192 if cout % 192 == 0 else 1)):
+        return None
+    precision = getattr(mod, "_conv_precision", "fp32")
+    if precision != "fp32" and not getattr(lic360, _SCONV[ks, precision][2])(cin, cout):
+        precision = "fp32"
+    for cpw in NARROW_CPWS:
+        nrg, tall = 8 // (cpw // 48), ks == 3 and not (precision == "bf16x3" and cpw == 48)
+        if lic360.sconv_narrow_supported(precision, ks, cin, cout, cpw) and count_ok(tiles(nrg, tall) * (cout // cpw)):
+            return None if (precision, ks, cpw, is_tall(nrg, tall)) in NARROW_ROUTED_BACK else cpw
+    return None
 
 
 def _fusable_s2(conv, x, mod=None):
@@ -90,7 +133,7 @@ GDN_PRECISIONS = ("fp32", "bf16x3")
 GATE_MODES = ("library", "fused")
 
 
-def set_conv_precision(module, precision, stride2="fp32", gdn="fp32", gate="library"):
+def set_conv_precision(module, precision, stride2="fp32", gdn="fp32", gate="library", small="library"):
     """arithmetic of the fused convolutions of every block under `module` (module.modules()): "fp32" (the default: lic360.sconv3x3 / sconv1x1),
     "bf16x3" (their split-bf16 forms wherever those take the layer's shape, the fp32 kernel elsewhere; about 2^-16 relative error per product) or
     "bf16x1" (their single-pass bf16 forms under the same shape rule: every input value and weight rounded once to bf16, one MFMA per product, fp32
@@ -105,6 +148,10 @@ def set_conv_precision(module, precision, stride2="fp32", gdn="fp32", gate="libr
     The gate of the attention blocks -- its 1x1 convolution, the sigmoid, the product with the trunk and the sum with the input -- stays on the library
     (MIOpen / rocBLAS + three elementwise kernels) unless gate="fused" moves it to one launch of lic360.sconv1x1_gate (or its bf16x3 / bf16x1 form, following
     `precision`) wherever the block is on its fused path; a later call without the keyword returns it to "library".
+    Layers whose launch would have too few workgroups -- one per 16 x 16 tile and 192 (96) output channels: below FUSED_MIN_WORKGROUPS on a 132 x 260 map at batch 1, on
+    36 x 68 maps at batch 8 -- stay on the library unless small="narrow" retries them on narrow workgroups (lic360.sconv3x3_narrow / sconv1x1_narrow /
+    sconv1x1_gate_narrow: 96 or 48 output channels per workgroup, the widest whose count passes the same rule; the arithmetic of `precision`, bit for bit the wide
+    kernel's result); every other condition of the fused path is unchanged, and a later call without the keyword returns them to the library.
     A per-module setting, not a global: several copies of the networks may run side by side in different modes.  Library layers, small maps and
     recording passes are the same in either mode.  Returns `module`."""
     if precision not in CONV_PRECISIONS:
@@ -115,11 +162,14 @@ def set_conv_precision(module, precision, stride2="fp32", gdn="fp32", gate="libr
         raise ValueError("GDN precision must be one of %s, got %r" % (GDN_PRECISIONS, gdn))
     if gate not in GATE_MODES:
         raise ValueError("gate mode must be one of %s, got %r" % (GATE_MODES, gate))
+    if small not in SMALL_MODES:
+        raise ValueError("small-launch mode must be one of %s, got %r" % (SMALL_MODES, small))
     for m in module.modules():
         m._conv_precision = precision
         m._stride2_precision = stride2
         m._gdn_precision = gdn
         m._gate_mode = gate
+        m._small_mode = small
     return module
 
 
@@ -143,6 +193,11 @@ def _sconv(mod, conv, x, slope, residual, out, **kw):
     if precision != "fp32" and not getattr(lic360, _SCONV[ks, precision][2])(cin, cout):
         precision = "fp32"
     fn, pack, _ = _SCONV[ks, precision]
+    ring = kw.get("ring", 1 if ks == 3 else 2)
+    ring_w = kw.get("ring_w") or ring
+    cpw = _narrow_cpw(mod, ks, cin, cout, x.shape[0], x.shape[2] - 2 * ring, x.shape[3] - 2 * ring_w)
+    if cpw is not None:                                                     # the same pack on narrow workgroups
+        return getattr(lic360, "sconv%dx%d_narrow" % (ks, ks))(x, _packed(conv, precision, pack), conv.bias, slope, residual, out, form=precision, cpw=cpw, **kw)
     return getattr(lic360, fn)(x, _packed(conv, precision, pack), conv.bias, slope, residual, out, **kw)
 
 
@@ -154,6 +209,10 @@ def _sconv_gate(mod, conv, x, trunk, residual, out, **kw):
     if precision != "fp32" and not getattr(lic360, _SCONV[1, precision][2])(cin, cout):
         precision = "fp32"
     fn, pack, _ = _SCONV[1, precision]
+    ring = kw.get("ring", 2)
+    cpw = _narrow_cpw(mod, 1, cin, cout, x.shape[0], x.shape[2] - 2 * ring, x.shape[3] - 2 * (kw.get("ring_w") or ring)) if cout % 192 == 0 else None
+    if cpw is not None:
+        return lic360.sconv1x1_gate_narrow(x, _packed(conv, precision, pack), conv.bias, trunk, residual, out, form=precision, cpw=cpw, **kw)
     return getattr(lic360, fn.replace("sconv1x1", "sconv1x1_gate"))(x, _packed(conv, precision, pack), conv.bias, trunk, residual, out, **kw)
 
 

@@ -438,6 +438,17 @@ int lic360_sconv1x1_gate_bf16x3(void *stream, const float *x, const void *packed
                                 int n, int cin, int cout, int hp, int wp, int ring, int ring_w);
 int lic360_sconv1x1_gate_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
                                 int n, int cin, int cout, int hp, int wp, int ring, int ring_w);
+/* ---- narrow workgroups for small launches (kernels k_narrow_conv / k_narrow_gate, csrc/conv3x3_kernels.hip), opt-in.  The stride-1 convolutions and the gate above
+ * with `cpw` = 96 or 48 output channels per workgroup instead of a whole pack block (192 where cout is a multiple of 192, else 96): cout / cpw times as many
+ * workgroups, for maps with too few 16 x 16 tiles to fill the chip.  Results are bit-identical to the wide calls; packs, shapes, alignments, window, crop and shuffle
+ * are theirs.  form: 0 = fp32, 3 = split-bf16, 1 = single-pass bf16 (packed = that form's stride-1 pack of kernel size ks); ks: 3 or 1 (ks = 1: pad = 0, sphere = 0).
+ * Refused before any launch: an unknown form, cpw outside {48, 96}, cpw not below the pack's block, and whatever the wide call refuses; the gate takes cout % 192 == 0.
+ * Tall last tile row: a remainder of up to 8 / (cpw / 48) rows, except in the split-bf16 form at cpw = 48, where a remainder takes a tile row of its own. */
+int lic360_sconv_narrow_supported(int form, int ks, int cin, int cout, int cpw);
+int lic360_sconv_narrow(void *stream, int form, int ks, int cpw, const float *x, const void *packed, const float *bias, const float *slope, const float *residual,
+                        float *out, int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle);
+int lic360_sconv1x1_gate_narrow(void *stream, int form, int cpw, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual,
+                                float *out, int n, int cin, int cout, int hp, int wp, int ring, int ring_w);
 /* apron of dst <- sphere-wrapped interior of src (src == dst: lic360_sphere_pad_inplace); [nc][hp][wp] planes      sphere_pad_cuda.cu:48-65 */
 int lic360_sphere_apron_from(void *stream, const float *src, float *dst, int nc, int hp, int wp, int pad);
 

@@ -9,7 +9,12 @@ run (median, min, max of 5 repeats of 10 launches), and --json FILE keeps that t
 of alternating repeats with the spread, and the smallest tile count from which the native form is not slower on any shape; --json FILE keeps the table.
 --s2 --precision bf16x1: the single-pass bf16 stride-2 forms (lic360_sconv3x3s2_bf16x1 / sconv1x1s2_bf16x1) next to the fp32 stride-2 kernel on the five
 production shapes at batch 8, launches alternating in one process (median, min, max of 5 repeats of 10 launches), and the rule for a form per shape: the
-bf16x1 median lies below the fp32 median by more than the two min-max spreads added; --json FILE keeps the table."""
+bf16x1 median lies below the fp32 median by more than the two min-max spreads added; --json FILE keeps the table.
+--narrow: the narrow-workgroup forms (lic360.sconv3x3_narrow / sconv1x1_narrow / sconv1x1_gate_narrow, cpw 96 and 48, in fp32, bf16x3 and bf16x1) on the layers
+whose wide launch has too few workgroups -- the 132 x 260 and 68 x 132 layers at batch 1, the 36 x 68 layers at batch 8 -- each next to the LIBRARY form of the
+same layer (fp32 torch: what the models run there without small="narrow") and to the wide kernel, launches alternating in one process (median, min, max of 5
+repeats of 10 launches); the rule per (layer, form, cpw): the narrow median lies below the library median by more than the two min-max spreads added;
+--json FILE (default profiles/sconv_narrow_probe.json) keeps the table."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "360-image-compression_amd"))
@@ -21,6 +26,7 @@ dev = "cuda:0"
 ap = argparse.ArgumentParser()
 ap.add_argument("--precision", choices=("fp32", "bf16x3", "bf16x1"), default="fp32")
 ap.add_argument("--s2", action="store_true")
+ap.add_argument("--narrow", action="store_true")
 ap.add_argument("--json", default=None)
 ARGS = ap.parse_args()
 B3 = ARGS.precision != "fp32"                                             # a bf16 form is "ours", timed alternating with the forms before it in FORMS
@@ -153,6 +159,94 @@ def s2_bf16x1_probe():
                            repeats="median of 5 repeats of 10 launches, each after 3 warm-up launches, the two forms alternating within a repeat; ms per launch",
                            rule="a shape passes when fp32_ms - bf16x1_ms > (fp32_max - fp32_min) + (bf16x1_max - bf16x1_min)", rows=rows), f, indent=1)
 
+
+def narrow_probe():
+    c, rows = 192, []
+    pad_op, trims = lic360.SpherePadOp(2, True, 0, False), {r: lic360.SphereTrimOp(r, 0, False) for r in (1, 2)}
+    # (name, ks, cin, cout, ring, ring_w, sphere, prelu, residual, crop / shuffle, gate)
+    layers = [("V2 conv1", 3, c, c, 1, 2, 1, True, False, False, False), ("V2 conv2", 3, c, c, 2, 2, 2, True, True, False, False),
+              ("GDN conv2", 3, c, c, 2, 2, 1, False, False, False, False), ("bottleneck 1x1 in", 1, c, c // 2, 2, 2, 0, True, False, False, False),
+              ("bottleneck 3x3", 3, c // 2, c // 2, 2, 2, 1, True, False, False, False), ("bottleneck 1x1 out", 1, c // 2, c, 2, 2, 0, False, True, False, False),
+              ("gate", 1, c, c, 2, 2, 0, False, True, False, True), ("Up conv1", 3, c, 4 * c, 2, 2, 1, True, False, True, False),
+              ("Up shortcut", 1, c, 4 * c, 2, 2, 0, False, True, True, False)]
+    maps = [(1, 132, 260, layers[:7]), (1, 68, 132, layers[:3] + layers[7:]), (8, 36, 68, layers)]
+    for n, hp, wp, ls in maps:
+        for name, ks, cin, cout, ring, ring_w, sphere, prelu, has_res, up, gate in ls:
+            x = torch.randn(n, cin, hp, wp, device=dev)
+            w = torch.randn(cout, cin, ks, ks, device=dev) * 0.05
+            b, sl = torch.randn(cout, device=dev), (torch.rand(cout, device=dev) * 0.5 if prelu else None)
+            crop = 1 if up else 0
+            oshape = (n, cout // 4, 2 * (hp - 2), 2 * (wp - 2)) if up else (n, cout, hp, wp)
+            res = torch.randn(oshape, device=dev) if has_res else None
+            trunk = torch.randn(oshape, device=dev) if gate else None
+            kw = dict(ring=ring, ring_w=ring_w, crop=crop, shuffle=up)
+            if ks == 3:
+                kw.update(pad=2, sphere=sphere)
+            if gate:
+                kw = dict(ring=ring)
+            sfx = lambda f: "" if f == "fp32" else "_" + f
+            packs = {f: getattr(lic360, "sconv%dx%d%s_pack" % (ks, ks, sfx(f)))(w) for f in ("fp32", "bf16x3", "bf16x1")}
+            outs = {}
+            def out_of(key):
+                if key not in outs:
+                    outs[key] = torch.zeros(oshape, device=dev)
+                return outs[key]
+            dt = lic360.DtowOp(2, True, 0, False) if up else None
+            def lib():                                                      # the library form of the layer with the launches the kernel absorbs
+                if gate:
+                    return res + trunk * torch.sigmoid(F.conv2d(x, w, b))
+                y = F.conv2d(pad_op.forward(x)[0], w, b, 1, 1) if ks == 3 and not up else (F.conv2d(pad_op.forward(x)[0], w, b) if up and ks == 3 else F.conv2d(x[:, :, 1:-1, 1:-1] if up else x, w, b))
+                if sl is not None:
+                    y = F.prelu(y, sl)
+                if up:
+                    y = dt.forward(y)[0]
+                    return trims[2].forward(y + res if res is not None else y)[0]
+                y = trims[ring].forward(y)[0]
+                return y + res if res is not None else y
+            def wide(f):
+                if gate:
+                    return lambda: getattr(lic360, "sconv1x1_gate" + sfx(f))(x, packs[f], b, trunk, res, out_of(("wide", f)), **kw)
+                return lambda: getattr(lic360, "sconv%dx%d%s" % (ks, ks, sfx(f)))(x, packs[f], b, sl, res, out_of(("wide", f)), **kw)
+            def narrow(f, cpw):
+                if gate:
+                    return lambda: lic360.sconv1x1_gate_narrow(x, packs[f], b, trunk, res, out_of((cpw, f)), form=f, cpw=cpw, **kw)
+                return lambda: getattr(lic360, "sconv%dx%d_narrow" % (ks, ks))(x, packs[f], b, sl, res, out_of((cpw, f)), form=f, cpw=cpw, **kw)
+            fns = {"library": lib}
+            for f in ("fp32", "bf16x3", "bf16x1"):
+                fns["wide " + f] = wide(f)
+                for cpw in (96, 48):
+                    if lic360.sconv_narrow_supported(f, ks, cin, cout, cpw):
+                        fns["cpw%d %s" % (cpw, f)] = narrow(f, cpw)
+            same = all(torch.equal(fns["cpw%d %s" % (cpw, f)](), fns["wide " + f]()) for f in ("fp32", "bf16x3", "bf16x1") for cpw in (96, 48) if "cpw%d %s" % (cpw, f) in fns)
+            t = {k: [] for k in fns}
+            for _ in range(5):
+                for k in fns:
+                    t[k].append(timed(fns[k]))
+            nr, nc = hp - 2 * ring, wp - 2 * ring_w
+            row = dict(layer=name, ks=ks, cin=cin, cout=cout, n=n, hp=hp, wp=wp, tiles=n * ((nr + 15) // 16 if nr % 16 > 8 or nr % 16 == 0 else nr // 16) * ((nc + 15) // 16),
+                       narrow_equals_wide=bool(same))
+            for k in fns:
+                key = k.replace(" ", "_")
+                row.update({key + "_ms": sorted(t[k])[2], key + "_min": min(t[k]), key + "_max": max(t[k])})
+                if k.startswith("cpw"):
+                    spreads = (max(t[k]) - min(t[k])) + (max(t["library"]) - min(t["library"]))
+                    row[key + "_passes"] = bool(sorted(t["library"])[2] - sorted(t[k])[2] > spreads)
+            rows.append(row)
+            print("narrow x%d %dx%d %-18s (%d -> %d, %dx%d): narrow == wide: %s | %s" % (n, hp, wp, name, cin, cout, ks, ks, same, " | ".join(
+                "%s %.3f (%.3f .. %.3f)%s" % (k, sorted(t[k])[2], min(t[k]), max(t[k]), "" if not k.startswith("cpw") else (" pass" if row[k.replace(" ", "_") + "_passes"] else " NO"))
+                for k in fns)), flush=True)
+            del x, res, trunk, outs
+    path = ARGS.json or os.path.join(ROOT, "profiles", "sconv_narrow_probe.json")
+    with open(path, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0),
+                       repeats="median of 5 repeats of 10 launches, each after 3 warm-up launches, all forms of a layer alternating within a repeat; ms per launch",
+                       rule="(layer, form, cpw) passes when library_ms - narrow_ms > (library_max - library_min) + (narrow_max - narrow_min)", rows=rows), f, indent=1)
+
+
+if ARGS.narrow:
+    torch.manual_seed(0)
+    narrow_probe()
+    sys.exit(0)
 
 if ARGS.s2:
     torch.manual_seed(0)

@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--stride2-precision", choices=("fp32", "bf16x1"), default="fp32", help="arithmetic of the analysis transform's fused stride-2 convolutions")
     ap.add_argument("--gdn-precision", choices=("fp32", "bf16x3"), default="fp32", help="arithmetic of the transforms' one-pass GDNs (bf16x3: the split-bf16 form)")
     ap.add_argument("--gate", choices=("library", "fused"), default="library", help="tail of the attention blocks (fused: 1x1 convolution + sigmoid + product + sum in one launch)")
+    ap.add_argument("--small", choices=("library", "narrow"), default="library", help="layers with too few workgroups for the wide kernels (narrow: on narrow workgroups, e.g. the 132 x 260 stage of one image)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     import lic360_container as box
@@ -66,8 +67,8 @@ def main():
         dec.quant.weight.data.copy_(enc.quant.weight.data)
         fc.load_layers(make_main_params(1003, 48))
         ic.load_layers(make_imp_params(1003))
-    lm.set_conv_precision(enc, args.precision, stride2=args.stride2_precision, gdn=args.gdn_precision, gate=args.gate)                             # the latent's bitstream is exact in either mode; only the pixels depend on it
-    lm.set_conv_precision(dec, args.precision, gdn=args.gdn_precision, gate=args.gate)                             # (the synthesis transform has no stride-2 layer)
+    lm.set_conv_precision(enc, args.precision, stride2=args.stride2_precision, gdn=args.gdn_precision, gate=args.gate, small=args.small)                             # the latent's bitstream is exact in either mode; only the pixels depend on it
+    lm.set_conv_precision(dec, args.precision, gdn=args.gdn_precision, gate=args.gate, small=args.small)                             # (the synthesis transform has no stride-2 layer)
     with torch.no_grad():
         torch.cuda.synchronize()
         t0 = time.time()

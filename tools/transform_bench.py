@@ -4,7 +4,9 @@ its four-kernel torch form.  Seeded random weights.  Writes one JSON document to
 --precision {fp32,bf16x3,bf16x1}: the mode of the fused convolutions (lic360_models.set_conv_precision) for every row; --ab: only the analysis and
 synthesis transforms, ms per image in all three modes, in "bf16x1" with the stride-2 layers in single-pass bf16 too (stride2="bf16x1": the row
 "bf16x1+s2"), in that mode with the GDNs in split bf16 as well (gdn="bf16x3": the row "bf16x1+s2+gdn") and in that mode with the attention blocks' gate in
-one launch (gate="fused": the row "bf16x1+s2+gdn+gate"), alternating in one run (one JSON line per repeat and a summary)."""
+one launch (gate="fused": the row "bf16x1+s2+gdn+gate"), and that mode with the small launches on narrow workgroups (small="narrow": the row
+"bf16x1+s2+gdn+gate+narrow"), alternating in one run (one JSON line per repeat and a summary); --ab --batch N: at N images per call (default 8; the narrow row
+is meant to be read at batch 1 and batch 8)."""
 import json
 import os
 import sys
@@ -203,30 +205,32 @@ def ab_transforms(batch=8, device=0, reps=3, repeats=5):
     """analysis and synthesis ms per image, the fp32, bf16x3 and bf16x1 modes, bf16x1 with stride2="bf16x1", that mode with gdn="bf16x3" and that mode with
     gate="fused" alternating on the same networks and inputs (the synthesis transform has no stride-2 layer: its fourth row is the control for drift; the fifth
     row against the fourth is the split-bf16 GDN against the fp32 one-pass GDN under the same convolutions; the sixth against the fifth is the attention blocks'
-    fused gate against their library tail)"""
+    fused gate against their library tail; the seventh against the sixth is small="narrow" -- the layers whose wide launch fails the count rule on narrow
+    workgroups -- against the library there)"""
     import lic360_models as lm
     dev = "cuda:%d" % device
     torch.manual_seed(0)
     enc, dec = lm.CMP_Encoder(gpu_id=device).to(dev).eval(), lm.CMP_Decoder(gpu_id=device).to(dev).eval()
-    modes = [(p, p, "fp32", "fp32", "library") for p in lm.CONV_PRECISIONS] + [("bf16x1+s2", "bf16x1", "bf16x1", "fp32", "library"),
-                                                                                 ("bf16x1+s2+gdn", "bf16x1", "bf16x1", "bf16x3", "library"),
-                                                                                 ("bf16x1+s2+gdn+gate", "bf16x1", "bf16x1", "bf16x3", "fused")]      # row name, precision, stride2, gdn, gate
-    t = {(m, k): [] for m, _, _, _, _ in modes for k in ("analysis", "synthesis")}
+    modes = [(p, p, "fp32", "fp32", "library", "library") for p in lm.CONV_PRECISIONS] + [
+        ("bf16x1+s2", "bf16x1", "bf16x1", "fp32", "library", "library"), ("bf16x1+s2+gdn", "bf16x1", "bf16x1", "bf16x3", "library", "library"),
+        ("bf16x1+s2+gdn+gate", "bf16x1", "bf16x1", "bf16x3", "fused", "library"),
+        ("bf16x1+s2+gdn+gate+narrow", "bf16x1", "bf16x1", "bf16x3", "fused", "narrow")]                  # row name, precision, stride2, gdn, gate, small
+    t = {(m[0], k): [] for m in modes for k in ("analysis", "synthesis")}
     with torch.no_grad():
         img = torch.rand((batch, 3, 512, 1024), device=dev)
         code, mask, _ = enc(img)
         for i in range(repeats):
-            for m, p, s2, g, gt in modes:
-                lm.set_conv_precision(enc, p, stride2=s2, gdn=g, gate=gt)
-                lm.set_conv_precision(dec, p, stride2=s2, gdn=g, gate=gt)
-                row = {"repeat": i, "precision": p, "stride2": s2, "gdn": g, "gate": gt, "batch": batch}
+            for m, p, s2, g, gt, sm in modes:
+                lm.set_conv_precision(enc, p, stride2=s2, gdn=g, gate=gt, small=sm)
+                lm.set_conv_precision(dec, p, stride2=s2, gdn=g, gate=gt, small=sm)
+                row = {"repeat": i, "precision": p, "stride2": s2, "gdn": g, "gate": gt, "small": sm, "batch": batch}
                 for k, fn in (("analysis", lambda: enc(img)), ("synthesis", lambda: dec(code, mask))):
                     row[k + "_ms_per_image"] = timed(fn, reps) / batch * 1e3
                     t[(m, k)].append(row[k + "_ms_per_image"])
                 print(json.dumps(row), flush=True)
     med = {"%s_%s_ms_per_image" % (k, p): sorted(v)[len(v) // 2] for (p, k), v in t.items()}
     spread = {"%s_%s_min_max" % (k, p): [min(v), max(v)] for (p, k), v in t.items()}
-    print(json.dumps({"summary": "median of %d alternating repeats" % repeats, **med, **spread}))
+    print(json.dumps({"summary": "median of %d alternating repeats, batch %d" % (repeats, batch), **med, **spread}))
 
 
 def ab_stride2(batch=8, device=0, reps=3, repeats=5):
@@ -261,7 +265,7 @@ if __name__ == "__main__":
         ab_stride2()
         sys.exit(0)
     if "--ab" in sys.argv:
-        ab_transforms()
+        ab_transforms(batch=int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 8)
         sys.exit(0)
     precision = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp32"
     if precision not in ("fp32", "bf16x3", "bf16x1"):
