@@ -6,6 +6,7 @@
 //   * forward = bilinear (or nearest) gather, one output element per thread, viewport-major output [14][n*c][h_out*w_out];
 //     backward = scatter-add of the gradients and of the interpolation weights (float atomics, as the reference).
 #include "common.h"
+#include "project_sample.h"
 #include <cmath>
 #include <vector>
 
@@ -26,9 +27,8 @@ Mat3 rodrigues(float x, float y, float z) {
 }
 }  // namespace
 
-LIC360_API int lic360_projects_tf(void *stream, float *tf_dev, int h_out, int w_out, const float *theta14, const float *phi14, float fov,
-                                  int height, int width) {
-    ARG_CHECK(tf_dev && theta14 && phi14 && h_out > 1 && w_out > 1 && height > 0 && width > 0);
+// the table [14][h_out * w_out][2] on the host (projects_cuda.cu:7-67,101-153 in fp32, libm where the reference runs libdevice)
+static std::vector<float> projects_tf_host(int h_out, int w_out, const float *theta14, const float *phi14, float fov, int height, int width) {
     const float pi = (float)acos(-1.0), fovr = fov * pi;
     const float hfov = fovr * h_out / w_out / 2, wfov = fovr / 2, half_pi = pi / 2;
     const float cx = (float)((w_out - 1) / 2.0), cy = (float)((h_out - 1) / 2.0);
@@ -61,10 +61,42 @@ LIC360_API int lic360_projects_tf(void *stream, float *tf_dev, int h_out, int w_
             tf[((size_t)v * inner + i) * 2 + 1] = -2 * lat / pi * hy + hy;
         }
     }
+    return tf;
+}
+
+LIC360_API int lic360_projects_tf(void *stream, float *tf_dev, int h_out, int w_out, const float *theta14, const float *phi14, float fov,
+                                  int height, int width) {
+    ARG_CHECK(tf_dev && theta14 && phi14 && h_out > 1 && w_out > 1 && height > 0 && width > 0);
+    const std::vector<float> tf = projects_tf_host(h_out, w_out, theta14, phi14, fov, height, width);
     hipError_t e = hipMemcpyAsync(tf_dev, tf.data(), tf.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     HIP_TRY(e);
     return 0;
+}
+
+// 1 when every index lic360_project_sample forms from that table lies inside one ERP plane [height][width], 0 when one does not (a viewport row
+// that looks exactly at a pole has an undefined longitude: the table leaves [0, width - 1] there), -1 on bad arguments.  Host arithmetic only.
+LIC360_API int lic360_projects_tf_inside(int h_out, int w_out, const float *theta14, const float *phi14, float fov, int height, int width, int nearest) {
+    if (!(theta14 && phi14 && h_out > 1 && w_out > 1 && height > 0 && width > 0 && (long)height * width <= 0x7fffffffL)) return -1;
+    const std::vector<float> tf = projects_tf_host(h_out, w_out, theta14, phi14, fov, height, width);
+    const long plane = (long)height * width;
+    for (size_t i = 0; i < tf.size(); i += 2) {
+        const float x = tf[i], y = tf[i + 1];
+        if (!(std::isfinite(x) && std::isfinite(y) && std::fabs(x) < 1e9f && std::fabs(y) < 1e9f)) return 0;
+        long lo, hi;                                               // the arithmetic of lic360_project_sample, in long
+        if (nearest) {
+            const long tw = (long)floor((double)x + 0.5) % width;
+            long th = (long)floor((double)y + 0.5);
+            th = th >= height ? height - 1 : th;
+            lo = hi = th * width + tw;
+        } else {
+            const long tw = (long)floorf(x), th = (long)floorf(y), pw = (tw + 1) % width, ph = th + 1 >= height ? height - 1 : th + 1;
+            lo = std::min(th, ph) * width + std::min(tw, pw);
+            hi = std::max(th, ph) * width + std::max(tw, pw);
+        }
+        if (lo < 0 || hi >= plane) return 0;
+    }
+    return 1;
 }
 
 template <bool NEAREST>
@@ -73,18 +105,7 @@ __global__ void k_projects_forward(const float *__restrict__ in, const float *__
     GRID_STRIDE(index, total) {
         const int ps = (int)(index % inner), tn = (int)((index / inner) % NC), tb = (int)(index / inner / NC);
         const float2 f = ((const float2 *)tf)[(long)tb * inner + ps];
-        const float *img = in + (long)tn * hs * ws;
-        if constexpr (NEAREST) {
-            const int tw = (int)floor((double)f.x + 0.5) % ws;
-            int th = (int)floor((double)f.y + 0.5);
-            th = th >= hs ? hs - 1 : th;
-            out[index] = img[th * ws + tw];
-        } else {
-            const int tw = (int)floorf(f.x), th = (int)floorf(f.y);
-            const int pw = (tw + 1) % ws, ph = th + 1 >= hs ? hs - 1 : th + 1;
-            const float tx = f.x - tw, ty = f.y - th, ntx = (float)(1. - tx), nty = (float)(1. - ty);
-            out[index] = img[th * ws + tw] * ntx * nty + img[th * ws + pw] * tx * nty + img[ph * ws + tw] * ntx * ty + img[ph * ws + pw] * tx * ty;
-        }
+        out[index] = lic360_project_sample<NEAREST>(in + (long)tn * hs * ws, f, hs, ws);
     }
 }
 LIC360_API int lic360_projects_forward(void *stream, const float *x, const float *tf, float *out, int nc, int h, int w, int h_out, int w_out, int nearest) {

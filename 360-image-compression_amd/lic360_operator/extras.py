@@ -9,6 +9,8 @@ metric / bookkeeping utilities, and two wrappers of out-of-scope native ops) and
   ModuleSaver    best / latest checkpoint writer (lic360_operator/ModuleSaver.py:4-35)
   Logger         screen + file log (lic360_operator/Logger.py:3-23)
   MultiProject   the 14 viewports of lic360.ProjectsOp (viewport metrics)
+  ViewportQuality  viewport MSE / SSIM per image and viewport: one fused native pass (lic360.viewport_quality), MultiProject + SSIM elsewhere;
+                 not a name of the reference
   MaskConv2      torch conv2d over a weight masked by lic360.MaskConstrainOp (the training-time form of the context conv)
 """
 import math
@@ -92,10 +94,14 @@ class DropGrad(nn.Module):
         return _GradGate.apply(x, self.drop)
 
 
-def _gauss_window(size, channel, sigma=1.5):
+def _gauss_taps(size, sigma=1.5):
     k = torch.arange(size, dtype=torch.float32) - size // 2
     g = torch.exp(-k * k / (2.0 * sigma * sigma))
-    g = g / g.sum()
+    return g / g.sum()
+
+
+def _gauss_window(size, channel, sigma=1.5):
+    g = _gauss_taps(size, sigma)
     return (g[:, None] * g[None, :]).expand(channel, 1, size, size).contiguous()
 
 
@@ -105,7 +111,8 @@ class SSIM(nn.Module):
         self.window_size, self.channel, self.size_average = int(window_size), int(channel), bool(size_average)
         self.window = _gauss_window(self.window_size, self.channel)
 
-    def forward(self, a, b):
+    def map(self, a, b):
+        """the per-cell SSIM, before any mean"""
         ch = a.shape[1]
         if ch != self.channel or self.window.device != a.device or self.window.dtype != a.dtype:
             self.window, self.channel = _gauss_window(self.window_size, ch).to(device=a.device, dtype=a.dtype), ch
@@ -114,7 +121,10 @@ class SSIM(nn.Module):
         mu_a, mu_b = blur(a), blur(b)
         var_a, var_b, cov = blur(a * a) - mu_a * mu_a, blur(b * b) - mu_b * mu_b, blur(a * b) - mu_a * mu_b
         c1, c2 = 0.01 ** 2, 0.03 ** 2
-        m = ((2 * mu_a * mu_b + c1) * (2 * cov + c2)) / ((mu_a * mu_a + mu_b * mu_b + c1) * (var_a + var_b + c2))
+        return ((2 * mu_a * mu_b + c1) * (2 * cov + c2)) / ((mu_a * mu_a + mu_b * mu_b + c1) * (var_a + var_b + c2))
+
+    def forward(self, a, b):
+        m = self.map(a, b)
         return m.mean() if self.size_average else m.mean(dim=(1, 2, 3))
 
 
@@ -192,6 +202,45 @@ class MultiProject(nn.Module):
             return self._fn.apply(x, op, False)
         with torch.no_grad():
             return op.forward(x)[0]
+
+
+class ViewportQuality(nn.Module):
+    """The viewport metrics of the evaluation mode (test/lic360_demo.py:406-449: `MultiProject(171, 256, 0.5, False, gpu)`, `SSIM(11, 3)` and
+    an MSE on the views) per image and viewport: forward(a, b) -> (mse, ssim), each [n, 14] fp32; `mse.mean()` and `ssim.mean()` are the
+    reference's two scalars (every viewport has the same number of cells).  fp32 contiguous tensors on the device, outside a recording
+    pass, take one fused native pass (lic360.viewport_quality) that writes no projected view; with return_map=True it also returns the
+    per-cell SSIM [14*n, c, h, w], viewport-major.  Anything else -- CPU tensors, other dtypes, strided tensors, a pass that records
+    gradients -- goes through MultiProject + SSIM + torch.mean and is reduced per (image, viewport) there: the module takes tensors of any
+    placement and dtype, but the projection is native in both paths, so a HIP device is needed either way (CPU tensors are projected on
+    `device_id` and the results come back to the CPU)."""
+
+    def __init__(self, h, w, fov=0.5, near=False, device_id=0, window_size=11):
+        super().__init__()
+        self.project = MultiProject(h, w, fov, near, device_id)
+        self.window_size = int(window_size)
+        self.ssim = SSIM(self.window_size, 3)
+        self.taps = _gauss_taps(self.window_size).tolist()
+        self.device_id = device_id if isinstance(device_id, int) else list(device_id)[0]
+
+    def _views(self, t, dev):
+        """the op owns its output -- the next call rewrites it (the caller clones) -- and a recorded pass leaves its graph node on that tensor"""
+        v = self.project(t.to(device=dev, dtype=torch.float32))
+        return v if self.project._recording(t) else v.detach()
+
+    def forward(self, a, b, return_map=False):
+        if a.shape != b.shape or a.dim() != 4:
+            raise ValueError("ViewportQuality takes two [n, c, h, w] tensors of one shape")
+        import lic360
+        fused = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and not self.project._recording(t) for t in (a, b))
+        if fused and a.device == b.device and a.device.index in self.project.op:
+            return lic360.viewport_quality(self.project.op[a.device.index], a, b, self.taps, return_map=return_map)
+        dev = a.device if a.is_cuda and a.device.index in self.project.op else torch.device("cuda:%d" % self.device_id)
+        n = a.shape[0]
+        va, vb = self._views(a, dev).clone(), self._views(b, dev)                               # [14 n, c, h, w], viewport-major
+        m = self.ssim.map(va, vb)
+        per_view = lambda t: t.mean(dim=(1, 2, 3)).view(14, n).t().contiguous().to(a.device)
+        mse, ssim = per_view((va - vb) ** 2), per_view(m)
+        return (mse, ssim, m.to(a.device)) if return_map else (mse, ssim)
 
 
 class _MaskConstrainFn(torch.autograd.Function):

@@ -293,6 +293,11 @@ int lic360_codec_decode_gated(void *stream, lic360_codec *codec, const uint8_t *
  *                                            extension/projects.hpp:8-20, projects_cuda.cu:7-67,101-153 */
 int lic360_projects_tf(void *stream, float *tf_dev, int h_out, int w_out, const float *theta14, const float *phi14, float fov,
                        int height, int width);
+/* 1 when every index the sampling of lic360_projects_forward / lic360_viewport_quality forms from the table of these arguments lies inside one
+ * ERP plane [height][width], 0 when one does not, -1 on bad arguments.  Host arithmetic only (no device, no stream).  A viewport with a row that
+ * looks exactly at a pole -- a square viewport of fov 0.5 in the views pitched by 45 degrees -- has an undefined longitude there: the reference's
+ * table (and this one) then leaves [0, width - 1], and the sampling kernels, which trust the table as the reference's do, read outside x. */
+int lic360_projects_tf_inside(int h_out, int w_out, const float *theta14, const float *phi14, float fov, int height, int width, int nearest);
 /* ProjectsOp.forward: x [nc][h][w] -> out [14][nc][h_out][w_out] (viewport-major), bilinear or nearest
  *                                            extension/projects_cuda.cu:181-232 */
 int lic360_projects_forward(void *stream, const float *x, const float *tf, float *out, int nc, int h, int w, int h_out, int w_out, int nearest);
@@ -300,6 +305,20 @@ int lic360_projects_forward(void *stream, const float *x, const float *tf, float
  *                                            extension/projects_cuda.cu:234-329 */
 int lic360_projects_backward(void *stream, const float *top_diff, const float *tf, float *in_diff, float *count, int nc, int h, int w,
                              int h_out, int w_out, int nearest);
+
+/* Fused viewport metrics (no reference kernel: the evaluation mode of test/lic360_demo.py:406-449 projects both images with ProjectsOp and
+ * runs lic360_operator/pytorch_ssim.py and an MSE on the views).  a, b [n][c][h][w] fp32 ERP batches; tf the table of lic360_projects_tf for
+ * (h_out, w_out) on an h x w ERP; taps: `window` floats in HOST memory, the normalised 1-D window (window odd, at most 11; the 2-D window is
+ * their outer product, applied as a row pass and a column pass with zero padding).  mse, ssim [n][14] fp32 (device): per image and viewport,
+ * the mean over c*h_out*w_out cells of (a - b)^2 and of the SSIM map, summed in double in a fixed order (no atomics: bit-reproducible).
+ * ssim_map: NULL, or [14][n][c][h_out][w_out] fp32 (the layout of lic360_projects_forward's output) for the per-cell SSIM.  scratch:
+ * lic360_viewport_quality_scratch_bytes(n, h_out, w_out) bytes of device memory, 16-byte aligned, fully written before it is read (the
+ * query returns 0 for arguments the launch refuses).  The outputs, the map and the scratch must not overlap.  The samples are bit for
+ * bit those of lic360_projects_forward, and like it this entry trusts tf: a table for which lic360_projects_tf_inside returns 0 makes it
+ * read outside a and b (the Python shim asks and refuses). */
+long lic360_viewport_quality_scratch_bytes(int n, int h_out, int w_out);
+int lic360_viewport_quality(void *stream, const float *a, const float *b, const float *tf, int n, int c, int h, int w, int h_out, int w_out,
+                            int nearest, const float *taps, int window, void *scratch, float *mse, float *ssim, float *ssim_map);
 
 /* CppOp: ERP -> Craster parabolic projection.  lic360_cpp_rows fills the per-row column window ws [h][2] = (first column, count) and the
  * row angle theta [h] (host computes, device write); lic360_cpp_forward resamples x [nc][h][w] row by row, zero outside the window; mask

@@ -88,15 +88,13 @@ def main():
         rec = dec(fc.decode([b["latent"] for b in blobs], m2), m2).clamp(0, 1)
         torch.cuda.synchronize()
         t3 = time.time()
-        pr = lo.MultiProject(171, 256, 0.5, False, 0)
-        va, vb = pr(x).clone(), pr(rec.contiguous())
-        ssim = lo.SSIM(11, 3)
+        vmse, vssim = lo.ViewportQuality(171, 256, 0.5, False, 0)(x, rec.contiguous())          # each [n, 14]: per image and viewport, one fused pass
+        vmse, vssim = vmse.mean(dim=1).tolist(), vssim.mean(dim=1).tolist()
     for i in range(n):
         mse = float(torch.mean((x[i] - rec[i]) ** 2))
-        vm = float(torch.mean((va[i * 14:(i + 1) * 14] - vb[i * 14:(i + 1) * 14]) ** 2))
         print("%s  %.3f bpp  PSNR %.2f dB  viewport PSNR %.2f dB  viewport SSIM %.4f" % (
-            files[i], os.path.getsize(files[i]) * 8 / (512.0 * 1024.0), 10 * math.log10(1.0 / max(mse, 1e-12)), 10 * math.log10(1.0 / max(vm, 1e-12)),
-            float(ssim(va[i * 14:(i + 1) * 14], vb[i * 14:(i + 1) * 14]))))
+            files[i], os.path.getsize(files[i]) * 8 / (512.0 * 1024.0), 10 * math.log10(1.0 / max(mse, 1e-12)), 10 * math.log10(1.0 / max(vmse[i], 1e-12)),
+            vssim[i]))
         np.save(os.path.join(args.out, "img%03d_decoded.npy" % i), (rec[i].permute(1, 2, 0).cpu().numpy() * 255).astype(np.uint8))
     print("encode %.1f ms, decode %.1f ms for %d image(s) (first call: includes library autotuning)" % ((t1 - t0) * 1e3, (t3 - t2) * 1e3, n))
 
