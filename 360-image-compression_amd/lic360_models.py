@@ -14,9 +14,19 @@ setter's keyword asks otherwise: set_conv_precision(model, precision, stride2="b
 (`lic360.sconv3x3s2_bf16x1` / `sconv1x1s2_bf16x1`, csrc/sconv_b1s2.inc), independently of `precision`.
 set_conv_precision(model, precision, gate="fused") runs the tail of the attention blocks -- the gate's 1x1 convolution, sigmoid, product and sum -- as one launch
 of `lic360.sconv1x1_gate` in the block's precision (csrc/conv3x3_kernels.hip, the gate epilogue); the default, "library", leaves it to torch.
+set_conv_precision(model, precision, small="narrow") retries layers whose wide launch would have too few workgroups on narrow ones (`lic360.sconv3x3_narrow` /
+`sconv1x1_narrow` / `sconv1x1_gate_narrow`: 96 or 48 output channels per workgroup, the wide kernel's bits).
+Routing: which of these forms a layer runs on, or the library, is decided in one function, `_route` -- admission (no recording, GPU fp32, bias, shape), the
+precision after the predicates' fallback, the wide launch's count and fill rule, then the narrow retry -- on one statement of the launch geometry (`_workgroups`,
+`_fills`).  A block puts its question through `_fusable` / `_fusable_s2`, each layer its own through `_sconv` / `_sconv_gate` / `_sconv_s2`, and `_launch` turns
+the answer into the `lic360` call (`_names`: the one place where a function's name is put together).
 The first stage's stride-2 layers (3 input channels: no 16-channel chunk, and bound by their output, not by MFMAs), convolutions off the fused
 shapes, small maps and every recording (training) pass are library work (torch -> MIOpen); native around them:
 sphere pad / trim / cut-edge / pixel-shuffle / importance map / quantiser kernels and the one-pass GDN (csrc/gdn_kernels.hip)."""
+import collections
+import functools
+import types
+
 import torch
 from torch import nn
 import lic360
@@ -29,36 +39,11 @@ def _conv(cin, cout, k, stride=1, pad=0):
 
 FUSED_MIN_WORKGROUPS = 256          # lic360.sconv3x3 is used when its workgroups (330 us each) fill whole rounds of the 256 CUs to 80 % or more: 512 per
                                     # 260x516 map -- one image is two exact rounds -- but not 128 (measured against MIOpen, batches 1..8: tools/conv3x3_probe.py)
-
-
 FUSED_MIN_FILL = 0.8
 FUSED_S2_MIN_WORKGROUPS = 128       # lic360.sconv3x3s2 / sconv1x1s2 (one workgroup per 16x16 tile of the OUTPUT window and 192 channels, one workgroup per CU: a round of
                                     # up to 256 takes 0.334 ms at 192 -> 192) are used from this many workgroups on: the smallest count from which they are not slower than
                                     # SpherePad + MIOpen on any measured shape (batches 1..32: tools/conv3x3_probe.py --s2, profiles/sconv_s2_probe.json; at 64 the
                                     # 3x3 loses 1.8x, so SphereConv2 -- 8 tiles per image -- stays on the library below batch 16); past one round the FUSED_MIN_FILL rule holds
-
-
-def _fusable(conv, x, ring, ring_w=None, mod=None):
-    """does this 3x3 stride-1 convolution of a map with x's batch, height and width run on lic360.sconv3x3?  (inference only: the kernels have
-    no backward -- with gradients enabled the fused path is taken only if neither x nor ANY parameter of the block `mod` that the path pushes
-    through them (the 1x1 layers, shortcuts, PReLU slopes, biases: all of the block) requires one)"""
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (mod is not None and any(p.requires_grad for p in mod.parameters()))):
-        return False
-    if not (x.is_cuda and x.dtype == torch.float32 and conv.bias is not None):
-        return False
-    cout, cin = conv.weight.shape[:2]
-    if not lic360.sconv3x3_supported(cin, cout):
-        return False
-    n, _, hp, wp = x.shape
-    nr, nc = hp - 2 * ring, wp - 2 * (ring if ring_w is None else ring_w)
-    rows = nr // 16 if 0 < nr % 16 <= (2 if cout % 192 == 0 else 4) and nr >= 16 else (nr + 15) // 16      # (a short remainder rides on the last tile row)
-    tiles = n * rows * ((nc + 15) // 16) * (cout // 192 if cout % 192 == 0 else 1)
-    if tiles >= FUSED_MIN_WORKGROUPS and tiles >= FUSED_MIN_FILL * 256 * ((tiles + 255) // 256):
-        return True
-    # refused for its workgroup count alone: with small="narrow" the layer is retried on narrow workgroups (_narrow_cpw)
-    return getattr(mod, "_small_mode", "library") == "narrow" and _narrow_cpw(mod, 3, cin, cout, n, nr, nc) is not None
-
-
 SMALL_MODES = ("library", "narrow")
 NARROW_CPWS = (96, 48)              # output channels per workgroup of lic360.sconv3x3_narrow / sconv1x1_narrow / sconv1x1_gate_narrow, widest first
 NARROW_MIN_WORKGROUPS = 256         # the count rule of the narrow launches is _fusable's (FUSED_MIN_WORKGROUPS, FUSED_MIN_FILL).  A floor of 128 was measured and not taken
@@ -71,53 +56,6 @@ NARROW_ROUTED_BACK = {("fp32", 3, 96, True)}    # (precision, kernel size, cpw, 
                                     # against the library's 0.254 (0.252 - 0.290): 0.036 apart, inside the spreads added (0.048).  Without the tall row (conv2, GDN conv2: 0.194 /
                                     # 0.181 against 0.264 / 0.242) and in bf16x3 / bf16x1 (0.072 / 0.045) the same layer passes.  A routed-back layer is not retried narrower
                                     # (cpw 48 there: 0.268); ResidualBlockV2 asks _fusable for its conv1, so in fp32 that block stays on the library at that shape.
-
-
-def _narrow_cpw(mod, ks, cin, cout, n, nr, nc):
-    """the channels per workgroup at which a stride-1 layer (ks x ks, cin -> cout, a window of nr x nc cells on n images) of block `mod` runs on narrow workgroups, or
-    None: the block asks for them (set_conv_precision(.., small="narrow")), the wide launch fails the count rule of _fusable (a map the wide kernel takes makes no
-    narrow call), and `cpw` is the widest of NARROW_CPWS that the narrow form of the block's precision (else fp32: _sconv's rule) takes and whose workgroup count --
-    tiles x cout / cpw, the tall last tile row by the narrow form's own rule -- passes the same count rule (NARROW_MIN_WORKGROUPS), unless the measurement routed that
-    (precision, ks, cpw, tall) back (NARROW_ROUTED_BACK).  A block goes one way on _fusable's question about ONE of its 3x3 layers; each of its layers then asks for
-    itself, with its own kernel size and window.  A sibling whose own narrow count fails where the asked layer's passed would run the wide kernel below the count
-    rule; no production block has such a sibling (their layers share one window up to the 1-ring, and the counts above are taken per 16-row tile)."""
-    if getattr(mod, "_small_mode", "library") != "narrow" or nr <= 0 or nc <= 0:
-        return None
-    wide_ok = lambda wg: wg >= FUSED_MIN_WORKGROUPS and wg >= FUSED_MIN_FILL * 256 * ((wg + 255) // 256)
-    count_ok = lambda wg: wg >= NARROW_MIN_WORKGROUPS and wg >= FUSED_MIN_FILL * 256 * ((wg + 255) // 256)
-    is_tall = lambda nrg, tall: bool(tall and 0 < nr % 16 <= nrg and nr >= 16)
-    tiles = lambda nrg, tall: n * (nr // 16 if is_tall(nrg, tall) else (nr + 15) // 16) * ((nc + 15) // 16)
-    if wide_ok(tiles(2 if cout % 192 == 0 else 4, ks == 3) * (cout // 192 if cout % 192 == 0 else 1)):
-        return None
-    precision = getattr(mod, "_conv_precision", "fp32")
-    if precision != "fp32" and not getattr(lic360, _SCONV[ks, precision][2])(cin, cout):
-        precision = "fp32"
-    for cpw in NARROW_CPWS:
-        nrg, tall = 8 // (cpw // 48), ks == 3 and not (precision == "bf16x3" and cpw == 48)
-        if lic360.sconv_narrow_supported(precision, ks, cin, cout, cpw) and count_ok(tiles(nrg, tall) * (cout // cpw)):
-            return None if (precision, ks, cpw, is_tall(nrg, tall)) in NARROW_ROUTED_BACK else cpw
-    return None
-
-
-def _fusable_s2(conv, x, mod=None):
-    """does this stride-2 convolution (3x3 or the 1x1 shortcut) of the 2-cell-apron map x run on lic360.sconv3x3s2 / sconv1x1s2?  The rules of
-    _fusable (inference only, fp32, contiguous, a bias, a supported shape), an even interior, and enough tiles of the OUTPUT window: at least FUSED_S2_MIN_WORKGROUPS,
-    and past one round of the 256 CUs whole rounds filled to FUSED_MIN_FILL as in _fusable (one round of 128 or more already wins as measured)."""
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (mod is not None and any(p.requires_grad for p in mod.parameters()))):
-        return False
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and conv.bias is not None):
-        return False
-    cout, cin = conv.weight.shape[:2]
-    if not (lic360.sconv3x3s2_supported if conv.kernel_size[0] == 3 else lic360.sconv1x1s2_supported)(cin, cout):
-        return False
-    n, _, hp, wp = x.shape
-    h, w = hp - 4, wp - 4
-    if h <= 0 or w <= 0 or h % 2 or w % 2:
-        return False
-    tiles = n * ((h // 2 + 15) // 16) * ((w // 2 + 15) // 16) * (cout // 192 if cout % 192 == 0 else 1)
-    return tiles >= FUSED_S2_MIN_WORKGROUPS and (tiles <= 256 or tiles >= FUSED_MIN_FILL * 256 * ((tiles + 255) // 256))
-
-
 CONV_PRECISIONS = ("fp32", "bf16x3", "bf16x1")
 STRIDE2_PRECISIONS = ("fp32", "bf16x1")
 S2_BF16X1_1X1_MAX_CELLS = 132 * 260  # lic360.sconv1x1s2_bf16x1 is taken on input maps of up to this many cells: the largest on which it beat the fp32 stride-2 kernel by more
@@ -125,11 +63,7 @@ S2_BF16X1_1X1_MAX_CELLS = 132 * 260  # lic360.sconv1x1s2_bf16x1 is taken on inpu
                                      # what the memory takes (0.348 against 0.359 ms, inside the spreads): that shape, and any unmeasured one above the bound, stays on fp32.
                                      # The 3x3 form passed on every production shape (3.7 - 6.4 x) and has no such bound.  tools/conv3x3_probe.py --s2 --precision bf16x1,
                                      # profiles/sconv_s2_bf16x1_probe.json, DESIGN §7c‴.
-
-
 GDN_PRECISIONS = ("fp32", "bf16x3")
-
-
 GATE_MODES = ("library", "fused")
 
 
@@ -173,47 +107,112 @@ def set_conv_precision(module, precision, stride2="fp32", gdn="fp32", gate="libr
     return module
 
 
+def _records_grad(x, conv, mod=None):
+    """is a gradient recorded here?  (The kernels have no backward: with gradients enabled a fused path is taken only if neither x, the layer's weight nor ANY parameter
+    of the block `mod` that the path pushes through them -- the 1x1 layers, shortcuts, PReLU slopes, biases: all of the block -- requires one)"""
+    return torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (mod is not None and any(p.requires_grad for p in mod.parameters())))
+
+
+# The launch geometry, restated from sconv_plan, sconv_tall and sconv_s2_launch of csrc/conv3x3_kernels.hip (tests/test_sconv_routes_cpu.py holds it against the
+# restatements of the exact tests' case files)
+def _workgroups(n, nr, nc, cout, ks, stride=1, cpw=None, precision="fp32"):
+    """(workgroups, tall last tile row?) of one launch on a window of nr x nc cells -- at stride 2 the OUTPUT's -- of n images: one per 16 x 16 tile and `cpw` output channels,
+    on a wide launch the pack's block (192, or all 96); its 8 waves stand NQ = channels / 48 wide, in 8 / NQ row groups.  At stride 1 a 3x3 window's remainder of 1 .. 8 / NQ
+    rows rides on the last tile row -- except in bf16x3 at 48 channels per workgroup, whose tall tile does not fit the LDS; any other remainder takes a tile row of its own"""
+    nq = cpw // 48 if cpw else 4 if cout % 192 == 0 else 2
+    tall = stride == 1 and ks == 3 and not (precision == "bf16x3" and nq == 1) and 0 < nr % 16 <= 8 // nq and nr >= 16
+    return n * (nr // 16 if tall else (nr + 15) // 16) * ((nc + 15) // 16) * (cout // cpw if cpw else cout // 192 if nq == 4 else 1), tall
+
+
+def _fills(workgroups, floor, one_round=False):
+    """the count and fill rule: `floor` workgroups or more, in whole rounds of the 256 CUs filled to FUSED_MIN_FILL (300 workgroups would run two rounds for the work of
+    1.2) -- with `one_round`, a single round as it is (stride 2: one round of FUSED_S2_MIN_WORKGROUPS or more already wins as measured)"""
+    return workgroups >= floor and ((one_round and workgroups <= 256) or workgroups >= FUSED_MIN_FILL * 256 * ((workgroups + 255) // 256))
+
+
+Route = collections.namedtuple("Route", "ks stride precision cpw gate")      # cpw: output channels per workgroup of a narrow launch, None: the wide kernel
+
+
+def _route(mod, conv, x, ring=None, ring_w=None, stride=1, ks=None, gate=False, decided=False):
+    """THE routing decision of the fused convolutions: the Route on which the layer `conv` (3x3 or 1x1; `gate`: as the attention blocks' gate launch) of block `mod` runs
+    on the map x -- at stride 1 on the window inside `ring` rows and `ring_w` columns, at stride 2 (the 3x3 or the 1x1 shortcut of a 2-cell-apron map) on the OUTPUT
+    window -- or None: the library.  In this order:
+    1. admission: no gradient recorded (_records_grad); a GPU fp32 map, a bias and, at stride 2, a contiguous map; a shape the fp32 form's predicate takes; at stride 2
+       an even interior.
+    2. precision: the block's (_conv_precision; at stride 2 _stride2_precision, whatever _conv_precision says), unless that form's predicate refuses the shape or the
+       measurement sends it back (S2_BF16X1_1X1_MAX_CELLS: the 1x1 stride-2 shortcut on maps above 132 x 260), then fp32.
+    3. the wide launch, if its workgroups pass the count and fill rule (_fills: FUSED_MIN_WORKGROUPS, at stride 2 FUSED_S2_MIN_WORKGROUPS with the one-round rule).
+    4. only after the wide count has failed, where the block asks for it (set_conv_precision(.., small="narrow"); stride 1; a gate only at cout % 192 == 0): the widest
+       cpw of NARROW_CPWS that the narrow form of that precision takes and whose workgroup count -- tiles x cout / cpw, the tall last tile row by the narrow form's own
+       rule -- passes the same rule (NARROW_MIN_WORKGROUPS), unless the measurement routed that (precision, ks, cpw, tall) back (NARROW_ROUTED_BACK): a routed-back
+       layer is not retried narrower.  A map the wide kernel takes makes no narrow call.
+    A block goes one way on this question about ONE of its 3x3 layers (_fusable, _fusable_s2); each of its layers then asks for itself with `decided`, its own kernel
+    size and window: admission is behind it and the answer is never None -- a layer no narrow width takes runs wide.  So a sibling whose own narrow count fails where
+    the asked layer's passed would run the wide kernel below the count rule; no production block has such a sibling (their layers share one window up to the 1-ring,
+    and the counts above are taken per 16-row tile)."""
+    ks = conv.kernel_size[0] if ks is None else ks
+    cout, cin = conv.weight.shape[:2]
+    n, _, hp, wp = x.shape
+    if stride == 2:
+        nr, nc = (hp - 4) // 2, (wp - 4) // 2
+    else:
+        ring = (1 if ks == 3 else 2) if ring is None else ring               # (lic360.sconv3x3's / sconv1x1's own default)
+        nr, nc = hp - 2 * ring, wp - 2 * (ring if ring_w is None else ring_w)
+    if not decided:
+        if _records_grad(x, conv, mod):
+            return None
+        if not (x.is_cuda and x.dtype == torch.float32 and conv.bias is not None and (stride == 1 or x.is_contiguous())):
+            return None
+        if not _takes(getattr(lic360, _names(ks, "fp32", stride)[2]), cin, cout):
+            return None
+        if stride == 2 and (hp <= 4 or wp <= 4 or hp % 2 or wp % 2):
+            return None
+    precision = getattr(mod, "_conv_precision" if stride == 1 else "_stride2_precision", "fp32")
+    if precision != "fp32" and not (_takes(getattr(lic360, _names(ks, precision, stride)[2]), cin, cout) and (stride == 1 or ks == 3 or hp * wp <= S2_BF16X1_1X1_MAX_CELLS)):
+        precision = "fp32"
+    wide = Route(ks, stride, precision, None, gate)
+    retry = stride == 1 and getattr(mod, "_small_mode", "library") == "narrow" and nr > 0 and nc > 0 and (not gate or cout % 192 == 0)
+    if decided and not retry:
+        return wide                                                         # (nothing left to decide: no count is taken)
+    if _fills(_workgroups(n, nr, nc, cout, ks, stride)[0], FUSED_MIN_WORKGROUPS if stride == 1 else FUSED_S2_MIN_WORKGROUPS, stride == 2):
+        return wide
+    if retry:
+        for cpw in NARROW_CPWS:
+            workgroups, tall = _workgroups(n, nr, nc, cout, ks, 1, cpw, precision)
+            if _takes(lic360.sconv_narrow_supported, precision, ks, cin, cout, cpw) and _fills(workgroups, NARROW_MIN_WORKGROUPS):
+                if (precision, ks, cpw, tall) in NARROW_ROUTED_BACK:
+                    break
+                return wide._replace(cpw=cpw)
+    return wide if decided else None
+
+
+@functools.lru_cache(maxsize=1024)
+def _takes(predicate, *shape):
+    """a shape predicate of lic360 (the attribute as it is at call time), remembered per function and shape: pure, and asked the same few questions on every forward"""
+    return bool(predicate(*shape))
+
+
+@functools.lru_cache(maxsize=None)
+def _names(ks, precision, stride=1, narrow=False, gate=False):
+    """the names in lic360 of a route's function, of the pack it reads and of its form's shape predicate: the one place where they are put together.  The stride-2 and gate
+    forms read the stride-1 pack of their precision (the one the stride-1 form caches); a narrow launch is one function per kernel size, told its form by keyword"""
+    size, form = "sconv%dx%d" % (ks, ks), "" if precision == "fp32" else "_" + precision
+    kind = size + ("s2" if stride == 2 else "_gate" if gate else "")
+    return kind + ("_narrow" if narrow else form), size + form + "_pack", (kind if stride == 2 else size) + form + "_supported"
+
+
 # (kernel size, precision) -> the names of the convolution, its pack and its shape predicate in lic360.  A bf16x1 row serves every shape its predicate takes:
 # each 3x3 and 1x1 shape of the transforms ran faster on it than on bf16x3 by more than the spread of the repeats (DESIGN §7c″, profiles/sconv_bf16x1_probe.json)
-_SCONV = {(3, "fp32"): ("sconv3x3", "sconv3x3_pack", "sconv3x3_supported"),
-          (1, "fp32"): ("sconv1x1", "sconv1x1_pack", "sconv1x1_supported"),
-          (3, "bf16x3"): ("sconv3x3_bf16x3", "sconv3x3_bf16x3_pack", "sconv3x3_bf16x3_supported"),
-          (1, "bf16x3"): ("sconv1x1_bf16x3", "sconv1x1_bf16x3_pack", "sconv1x1_bf16x3_supported"),
-          (3, "bf16x1"): ("sconv3x3_bf16x1", "sconv3x3_bf16x1_pack", "sconv3x3_bf16x1_supported"),
-          (1, "bf16x1"): ("sconv1x1_bf16x1", "sconv1x1_bf16x1_pack", "sconv1x1_bf16x1_supported")}
+_SCONV = {(ks, precision): _names(ks, precision) for ks in (3, 1) for precision in CONV_PRECISIONS}
 
 
-def _sconv(mod, conv, x, slope, residual, out, **kw):
-    """the fused convolution `conv` (3x3 or 1x1) of block `mod` in the block's precision: lic360.sconv3x3 / sconv1x1 (the fp32 call is exactly
-    theirs), or their bf16x3 / bf16x1 forms when the block asks for them and they take the layer's shape.  The functions are lic360's attributes at
-    call time.  The weight travels in the chosen form's operand order, repacked when the parameter was written (its version counter) or moved;
-    each precision keeps its own pack, so switching modes never reuses the other's."""
-    ks, precision = conv.kernel_size[0], getattr(mod, "_conv_precision", "fp32")
-    cout, cin = conv.weight.shape[:2]
-    if precision != "fp32" and not getattr(lic360, _SCONV[ks, precision][2])(cin, cout):
-        precision = "fp32"
-    fn, pack, _ = _SCONV[ks, precision]
-    ring = kw.get("ring", 1 if ks == 3 else 2)
-    ring_w = kw.get("ring_w") or ring
-    cpw = _narrow_cpw(mod, ks, cin, cout, x.shape[0], x.shape[2] - 2 * ring, x.shape[3] - 2 * ring_w)
-    if cpw is not None:                                                     # the same pack on narrow workgroups
-        return getattr(lic360, "sconv%dx%d_narrow" % (ks, ks))(x, _packed(conv, precision, pack), conv.bias, slope, residual, out, form=precision, cpw=cpw, **kw)
-    return getattr(lic360, fn)(x, _packed(conv, precision, pack), conv.bias, slope, residual, out, **kw)
-
-
-def _sconv_gate(mod, conv, x, trunk, residual, out, **kw):
-    """the gate launch of block `mod` on its 1x1 convolution `conv`, in the block's precision under _sconv's rule (the form's predicate, else fp32): the 1x1
-    names of _SCONV with `_gate` behind `sconv1x1`, on the pack the 1x1 form of that precision caches"""
-    precision = getattr(mod, "_conv_precision", "fp32")
-    cout, cin = conv.weight.shape[:2]
-    if precision != "fp32" and not getattr(lic360, _SCONV[1, precision][2])(cin, cout):
-        precision = "fp32"
-    fn, pack, _ = _SCONV[1, precision]
-    ring = kw.get("ring", 2)
-    cpw = _narrow_cpw(mod, 1, cin, cout, x.shape[0], x.shape[2] - 2 * ring, x.shape[3] - 2 * (kw.get("ring_w") or ring)) if cout % 192 == 0 else None
-    if cpw is not None:
-        return lic360.sconv1x1_gate_narrow(x, _packed(conv, precision, pack), conv.bias, trunk, residual, out, form=precision, cpw=cpw, **kw)
-    return getattr(lic360, fn.replace("sconv1x1", "sconv1x1_gate"))(x, _packed(conv, precision, pack), conv.bias, trunk, residual, out, **kw)
+def _launch(route, conv, x, a, residual, out, **kw):
+    """the call a Route stands for (`a`: the PReLU slopes, or the gate's trunk).  The function is lic360's attribute at call time.  The weight travels in the chosen form's
+    operand order, repacked when the parameter was written (its version counter) or moved; each precision keeps its own pack, so switching modes never reuses the other's."""
+    fn, pack, _ = _names(route.ks, route.precision, route.stride, route.cpw is not None, route.gate)
+    if route.cpw is not None:                                               # the same pack on narrow workgroups
+        kw.update(form=route.precision, cpw=route.cpw)
+    return getattr(lic360, fn)(x, _packed(conv, route.precision, pack), conv.bias, a, residual, out, **kw)
 
 
 def _packed(conv, precision, pack):
@@ -226,18 +225,35 @@ def _packed(conv, precision, pack):
     return packs[precision][1]
 
 
+def _fusable(conv, x, ring, ring_w=None, mod=None):
+    """does a block `mod` whose 3x3 stride-1 convolution `conv` meets a map with x's batch, height and width go fused (lic360.sconv3x3, or its narrow form)?"""
+    return _route(mod, conv, x, ring, ring_w, ks=3) is not None
+
+
+def _fusable_s2(conv, x, mod=None):
+    """does this stride-2 convolution (3x3 or the 1x1 shortcut) of the 2-cell-apron map x run on lic360.sconv3x3s2 / sconv1x1s2?"""
+    return _route(mod, conv, x, stride=2) is not None
+
+
+def _narrow_cpw(mod, ks, cin, cout, n, nr, nc):
+    """the channels per workgroup at which a stride-1 layer (ks x ks, cin -> cout, a window of nr x nc cells on n images) of block `mod` runs on narrow workgroups, or None"""
+    layer, window = types.SimpleNamespace(weight=types.SimpleNamespace(shape=(cout, cin, ks, ks))), types.SimpleNamespace(shape=(n, cin, nr, nc))
+    return _route(mod, layer, window, 0, ks=ks, decided=True).cpw
+
+
+def _sconv(mod, conv, x, slope, residual, out, **kw):
+    """the fused convolution `conv` (3x3 or 1x1) of block `mod`, in the block's precision and on the workgroups its own window asks for"""
+    return _launch(_route(mod, conv, x, kw.get("ring"), kw.get("ring_w"), decided=True), conv, x, slope, residual, out, **kw)
+
+
+def _sconv_gate(mod, conv, x, trunk, residual, out, **kw):
+    """the gate launch of block `mod` on its 1x1 convolution `conv`: lic360.sconv1x1_gate, its bf16x3 / bf16x1 form or the narrow one, under _sconv's rules"""
+    return _launch(_route(mod, conv, x, kw.get("ring"), kw.get("ring_w"), ks=1, gate=True, decided=True), conv, x, trunk, residual, out, **kw)
+
+
 def _sconv_s2(mod, conv, x, slope, residual, out):
-    """the stride-2 convolution `conv` (3x3 or the 1x1 shortcut) of block `mod` on a 2-cell-apron map: lic360.sconv3x3s2 / sconv1x1s2 (fp32, on the stride-1
-    fp32 pack of the weight) whatever the block's _conv_precision, or -- when the block's _stride2_precision is "bf16x1", their shape predicate takes
-    the layer and the layer is not one the measurement routes to fp32 (S2_BF16X1_1X1_MAX_CELLS: the 1x1 shortcut on maps above 132 x 260) --
-    lic360.sconv3x3s2_bf16x1 / sconv1x1s2_bf16x1 on the stride-1 bf16x1 pack (the one the stride-1 form caches)"""
-    ks = conv.kernel_size[0]
-    cout, cin = conv.weight.shape[:2]
-    fn, pack, _ = _SCONV[ks, "fp32"]
-    if (getattr(mod, "_stride2_precision", "fp32") == "bf16x1" and getattr(lic360, fn + "s2_bf16x1_supported")(cin, cout)
-            and (ks == 3 or x.shape[2] * x.shape[3] <= S2_BF16X1_1X1_MAX_CELLS)):
-        return getattr(lic360, fn + "s2_bf16x1")(x, _packed(conv, "bf16x1", _SCONV[ks, "bf16x1"][1]), conv.bias, slope, residual, out, pad=2, oring=2)
-    return getattr(lic360, fn + "s2")(x, _packed(conv, "fp32", pack), conv.bias, slope, residual, out, pad=2, oring=2)
+    """the stride-2 convolution `conv` (3x3 or the 1x1 shortcut) of block `mod` on a 2-cell-apron map"""
+    return _launch(_route(mod, conv, x, stride=2, decided=True), conv, x, slope, residual, out, pad=2, oring=2)
 
 
 def _scratch(shape, like):
@@ -309,7 +325,7 @@ class AttentionBlock(nn.Module):
         x contiguous as it arrives (its bottlenecks are then on their fused paths too), no gradient recorded for any parameter of the whole block, a gate
         convolution with a bias and a shape the 1x1 kernel takes"""
         conv = self.attention[3]
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if _records_grad(x, conv, self):
             return False
         cout, cin = conv.weight.shape[:2]
         return x.is_contiguous() and conv.bias is not None and lic360.sconv1x1_supported(cin, cout)
@@ -449,13 +465,14 @@ class ResidualBlockUp(nn.Module):
             b = self.dtow1(self.relu1(self.conv1(self.pad1(x))))           # (trim1 -> pad2 in place, model_zoo.py:160-161: the refresh overwrites what the trim zeroed)
             if torch.is_grad_enabled() and b.requires_grad:
                 b = self.trim1(b)                                           # (recording pass: the reference's sequence, see ResidualBlockDown)
-        if _fusable(self.conv2, b, 2, mod=self) and b.is_contiguous():
+        fused2 = _fusable(self.conv2, b, 2, mod=self)                       # (asked once: relu2 keeps the map's shape, and only parameters of this block, which the question covers, could make its output record)
+        if fused2 and b.is_contiguous():
             b2 = _scratch(b.shape, b)
             b = self.relu2(_sconv(self, self.conv2, b, None, None, b2, pad=2, sphere=True, ring=2))
         else:
             b = self.relu2(self.conv2(self.pad2(b)))
         c_in, c_out = self.short_cut.in_channels, self.short_cut.out_channels
-        if (_fusable(self.conv2, b, 2, mod=self) and x.is_contiguous() and b.is_contiguous() and lic360.sconv1x1_supported(c_in, c_out) and self.short_cut.bias is not None
+        if (fused2 and x.is_contiguous() and b.is_contiguous() and lic360.sconv1x1_supported(c_in, c_out) and self.short_cut.bias is not None
                 and tuple(b.shape) == (x.shape[0], c_out // 4, 2 * (x.shape[2] - 2), 2 * (x.shape[3] - 2))):
             # the shortcut -- cut_edge(1) -> 1x1 conv to 4c -> Dtow(2) -- and the `b +` in one launch: the 1x1 instantiation with the shuffled store,
             # b as its (shuffled) residual, on the interior window (trim2 zeroes the rest)
