@@ -36,8 +36,10 @@
 //
 // Three arithmetic forms, one of everything else.  s3_body (here) is the fp32 form, b3_body (sconv_bf16x3.inc, opt-in) the split-bf16 form ("bf16x3") and,
 // with its lo parts left out, the single-pass bf16 form ("bf16x1"); they differ in their chunk loop, LDS layout and weight pack.  What decides which cells a convolution reads and writes exists once and serves both:
-// s3_cell_offset (the source cell of a loader's LDS cell), s3_epilogue (bias, PReLU, residual, window test, store), the kernel wrapper sconv_workgroup<NT, ..>
-// (tile decode, tall last tile row) and the host's sconv_launch<NT> (shape predicate, argument contract, tile geometry, grid).
+// s3_cell_offset (the source cell of a loader's LDS cell), s3_epilogue (bias, PReLU, residual, window test, store), sconv_tile (a workgroup's LDS and tile decode,
+// under the kernel wrappers sconv_workgroup<NT, ..> -- tall last tile row --, sconv_s2_workgroup and sconv_gate_workgroup) and, on the host, one path for every
+// entry point: a SconvCall (form, kernel size, stride, gate, channels per workgroup; the operands) through sconv_plan (shape predicate, argument contract, tile
+// geometry, grid: the shared checks once, the stride's own beside them) and sconv_launch (the one pick of the kernel instantiation).
 //
 // The gate of the attention blocks (k_gate_sconv / k_gate_sconv_b3 / k_gate_sconv_b1; lic360_sconv1x1_gate / _bf16x3 / _bf16x1, opt-in:
 // lic360_models.set_conv_precision(.., gate="fused")).  Replaces the tail of AttentionBlock, test/model_zoo.py:25-46: nn.Conv2d(c, c, 1) + nn.Sigmoid + the `*` with
@@ -47,6 +49,7 @@
 #include "common.h"
 #include "lic360_exact_math.h"
 #include <cstdint>
+#include <type_traits>
 
 typedef float s3_f4 __attribute__((ext_vector_type(4)));
 
@@ -364,6 +367,15 @@ __device__ __forceinline__ void s3_body(const S3Args &a, float *lds, int ty, int
 #include "sconv_bf16x3.inc"          // b3_body: the split-bf16 and single-pass bf16 forms of s3_body (arithmetic, pack kernel); everything around the bodies is below
 #include "sconv_b1s2.inc"            // b1s2_body: the single-pass bf16 form of the 3x3 at stride 2 (a register-path loader into a double-buffered bf16 image)
 
+// ---- what every workgroup starts with: its LDS (LDS_FLOATS: the body's, of its tallest tile) and its tile, blockIdx.x = (image, tile row, tile column);
+// `body(lds, ty, tx, img)` is the rest of the kernel
+template <int LDS_FLOATS, class Body>
+__device__ __forceinline__ void sconv_tile(const S3Args &a, Body body) {
+    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
+    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
+    const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
+    body(lds, ty, tx, img);
+}
 // ---- one workgroup wrapper, one launch for all forms.  NT = bf16 MFMAs per product: 0 the fp32 body, 3 the split-bf16 body, 1 its single-pass form.
 template <int NT, int NQ, int RW, int KS, int PQ = NQ>
 __device__ __forceinline__ void sconv_body(const S3Args &a, float *lds, int ty, int tx, int img) {
@@ -378,24 +390,22 @@ constexpr bool sconv_tall(int nt, int nq, int ks) { return ks == 3 && !(nt == 3 
 template <int NT, int NQ, int RW, int KS, int PQ = NQ>
 __device__ __forceinline__ void sconv_workgroup(const S3Args &a) {
     constexpr int TR = 8 / NQ * (RW + (sconv_tall(NT, NQ, KS) ? 1 : 0));    // rows of the tallest tile
-    __shared__ __attribute__((aligned(16))) float lds[NT ? b3_lds(TR, KS, NT) : s3_lds(TR, KS)];
-    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
-    const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
-    if constexpr (sconv_tall(NT, NQ, KS)) {
-        if (a.tall_last && ty == a.tiles_y - 1) { sconv_body<NT, NQ, RW + 1, 3, PQ>(a, lds, ty, tx, img); return; }
-    }
-    sconv_body<NT, NQ, RW, KS, PQ>(a, lds, ty, tx, img);
+    sconv_tile<NT ? b3_lds(TR, KS, NT) : s3_lds(TR, KS)>(a, [&](float *lds, int ty, int tx, int img) {
+        if constexpr (sconv_tall(NT, NQ, KS)) {
+            if (a.tall_last && ty == a.tiles_y - 1) { sconv_body<NT, NQ, RW + 1, 3, PQ>(a, lds, ty, tx, img); return; }
+        }
+        sconv_body<NT, NQ, RW, KS, PQ>(a, lds, ty, tx, img);
+    });
 }
 // the stride-2 workgroup (NT = 0: the fp32 form, 1: the single-pass bf16 form): no tall last tile row -- (2 (TR + NR) + 1) x 33 halos do not fit LDS twice -- a
 // remainder takes an ordinary tile row
 template <int NQ, int RW, int KS, int NT = 0>
 __device__ __forceinline__ void sconv_s2_workgroup(const S3Args &a) {
-    __shared__ __attribute__((aligned(16))) float lds[NT == 0 ? s3_lds_st(8 / NQ * RW, KS, 2) : KS == 3 ? b1s2_lds() : b3_lds(8 / NQ * RW, 1, 1)];
-    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
-    const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
-    if constexpr (NT == 0) s3_body<NQ, RW, KS, 2>(a, lds, ty, tx, img);
-    else if constexpr (KS == 3) b1s2_body<NQ, RW>(a, lds, ty, tx, img);
-    else b3_body<NQ, RW, 1, 1, 2>(a, lds, ty, tx, img);
+    sconv_tile<NT == 0 ? s3_lds_st(8 / NQ * RW, KS, 2) : KS == 3 ? b1s2_lds() : b3_lds(8 / NQ * RW, 1, 1)>(a, [&](float *lds, int ty, int tx, int img) {
+        if constexpr (NT == 0) s3_body<NQ, RW, KS, 2>(a, lds, ty, tx, img);
+        else if constexpr (KS == 3) b1s2_body<NQ, RW>(a, lds, ty, tx, img);
+        else b3_body<NQ, RW, 1, 1, 2>(a, lds, ty, tx, img);
+    });
 }
 template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv3x3s2(S3Args a) { sconv_s2_workgroup<NQ, RW, KS>(a); }
 template <int NQ, int RW, int KS> __global__ __launch_bounds__(S3_THREADS) void k_sconv_b1s2(S3Args a) { sconv_s2_workgroup<NQ, RW, KS, 1>(a); }
@@ -422,12 +432,10 @@ struct S3GateArgs {
 };
 template <int NT, int NQ, int RW, int PQ = NQ>
 __device__ __forceinline__ void sconv_gate_workgroup(const S3GateArgs &g) {
-    const S3Args &a = g.a;
-    __shared__ __attribute__((aligned(16))) float lds[NT ? b3_lds(8 / NQ * RW, 1, NT) : s3_lds(8 / NQ * RW, 1)];
-    static_assert(sizeof(lds) <= 160 * 1024, "LDS of a gfx950 CU");
-    const int tpi = a.tiles_x * a.tiles_y, img = blockIdx.x / tpi, trem = blockIdx.x - img * tpi, ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
-    if constexpr (NT == 0) s3_body<NQ, RW, 1, 1, 1, PQ>(a, lds, ty, tx, img, g.trunk);
-    else b3_body<NQ, RW, 1, NT, 1, 1, PQ>(a, lds, ty, tx, img, g.trunk);
+    sconv_tile<NT ? b3_lds(8 / NQ * RW, 1, NT) : s3_lds(8 / NQ * RW, 1)>(g.a, [&](float *lds, int ty, int tx, int img) {
+        if constexpr (NT == 0) s3_body<NQ, RW, 1, 1, 1, PQ>(g.a, lds, ty, tx, img, g.trunk);
+        else b3_body<NQ, RW, 1, NT, 1, 1, PQ>(g.a, lds, ty, tx, img, g.trunk);
+    });
 }
 template <int NQ, int RW> __global__ __launch_bounds__(S3_THREADS) void k_gate_sconv(S3GateArgs g) { sconv_gate_workgroup<0, NQ, RW>(g); }
 template <int NQ, int RW> __global__ __launch_bounds__(S3_THREADS) void k_gate_sconv_b3(S3GateArgs g) { sconv_gate_workgroup<3, NQ, RW>(g); }
@@ -456,12 +464,13 @@ static inline int sconv_ck(int nt, int ks) { return nt ? B3_CK : s3_ck(ks); }
 static inline bool sconv_ok(int nt, int cin, int cout, int ks) {
     return (ks == 3 || ks == 1) && cin >= sconv_ck(nt, ks) && cin % sconv_ck(nt, ks) == 0 && cout >= 96 && (cout % 192 == 0 || cout == 96);
 }
+static inline int sconv_nq(int cout) { return cout % 192 == 0 ? 4 : 2; }    // the pack's channel blocks: NQ * 48 = 192 output channels, or the 96 of cout = 96
 static inline long s3_packed(int cin, int cout, int ks) { return sconv_ok(0, cin, cout, ks) ? (long)cout / 48 * (cin / 4) * ks * s3_na4(ks) * 256 : 0; }
 static inline long b3_packed_bytes(int nt, int cin, int cout, int ks) { return sconv_ok(nt, cin, cout, ks) ? (long)cout * cin * ks * ks * (nt == 3 ? 4 : 2) : 0; }   // hi + lo bf16 per weight, or hi
 static int s3_pack(void *stream, const float *weight, float *packed, int cin, int cout, int ks) {
     ARG_CHECK(weight && packed && sconv_ok(0, cin, cout, ks));
     const long total = s3_packed(cin, cout, ks);
-    hipLaunchKernelGGL(k_sconv3x3_pack, dim3(lic360_blocks(total, 4)), dim3(256), 0, (hipStream_t)stream, weight, packed, cin, cout, cout % 192 == 0 ? 4 : 2, ks, total);
+    hipLaunchKernelGGL(k_sconv3x3_pack, dim3(lic360_blocks(total, 4)), dim3(256), 0, (hipStream_t)stream, weight, packed, cin, cout, sconv_nq(cout), ks, total);
     LAUNCH_CHECK();
     return 0;
 }
@@ -469,121 +478,97 @@ static int b3_pack(int nt, void *stream, const float *weight, void *packed, int 
     ARG_CHECK(weight && packed && sconv_ok(nt, cin, cout, ks) && ((uintptr_t)packed & 15) == 0);
     const long total = b3_packed_bytes(nt, cin, cout, ks) / 16;
     hipLaunchKernelGGL(k_sconv_b3_pack, dim3(lic360_blocks(total)), dim3(256), 0, (hipStream_t)stream, weight, (b3_u4 *)packed, cin, cout,
-                       cout % 192 == 0 ? 4 : 2, ks, nt == 3 ? 2 : 1, total);
-    LAUNCH_CHECK();
-    return 0;
-}
-// the argument contract, tile geometry and grid of a stride-1 launch (sconv_launch, and sconv_gate_launch with ks = 1, crop = 0, shuffle = 0)
-template <int NT>
-static int sconv_plan(const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                      int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle, S3Args &a, dim3 &grid,
-                      int cpw = 0) {                                        // != 0: a narrow launch, `cpw` channels per workgroup (sconv_narrow_ok holds)
-    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(NT, cin, cout, ks) && pad >= 0 && ring >= ks / 2 && ring_w >= ring && hp > 2 * ring && wp > 2 * ring_w &&
-              out_crop >= 0 && out_crop <= ring && sphere >= 0 && sphere <= 2);
-    ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
-    ARG_CHECK((double)sconv_ck(NT, ks) * hp * wp * 4.0 < 4294967296.0 && (!NT || ((uintptr_t)packed & 15) == 0) && ((uintptr_t)bias & 15) == 0 &&
-              (!slope || ((uintptr_t)slope & 15) == 0));                    // a chunk's cells at 32-bit byte offsets; 16-byte operand loads
-    ARG_CHECK(!residual || out_crop == 0 || shuffle);                       // the residual has the input's geometry -- or, shuffled, the output's
-    ARG_CHECK(!shuffle || (((uintptr_t)out & 7) == 0 && ((uintptr_t)residual & 7) == 0));   // the shuffled store / residual load move aligned pairs
-    a.x = x; a.w = (const float *)packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
-    a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = ring; a.ringw = ring_w;
-    a.ooff = out_crop; a.ohp = hp - 2 * out_crop; a.owp = wp - 2 * out_crop; a.shuffle = shuffle;
-    a.tiles_x = (wp - 2 * ring_w + S3_T - 1) / S3_T;
-    const int nq = cpw ? cpw / 48 : cout % 192 == 0 ? 4 : 2, nrg = 8 / nq, nr = hp - 2 * ring, full = nr / S3_T, rem = nr - full * S3_T;
-    a.rw = S3_T / nrg;
-    a.tall_last = sconv_tall(NT, nq, ks) && rem > 0 && rem <= nrg && full > 0;   // the remainder fits one more row per wave of the last tile row
-    a.tiles_y = a.tall_last ? full : (nr + S3_T - 1) / S3_T;
-    const long tiles = (long)n * a.tiles_x * a.tiles_y;
-    ARG_CHECK(tiles < (1L << 31) && (!cpw || cout / cpw < 65536));
-    grid = dim3((unsigned)tiles, cpw ? cout / cpw : nq == 4 ? cout / 192 : 1);
-    return 0;
-}
-template <int NT>
-static int sconv_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                        int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int ks, int shuffle) {
-    S3Args a;
-    dim3 grid;
-    if (const int rc = sconv_plan<NT>(x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, ks, shuffle, a, grid)) return rc;
-    const int nq = cout % 192 == 0 ? 4 : 2;
-    if (ks == 3 && nq == 4) hipLaunchKernelGGL((sconv_kernel<NT, 4, 8, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (ks == 3) hipLaunchKernelGGL((sconv_kernel<NT, 2, 4, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (nq == 4) hipLaunchKernelGGL((sconv_kernel<NT, 4, 8, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((sconv_kernel<NT, 2, 4, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    LAUNCH_CHECK();
-    return 0;
-}
-// the gate: the shapes and refusals of the 1x1 launch; trunk and residual are required
-template <int NT>
-static int sconv_gate_launch(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
-                             int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
-    ARG_CHECK(trunk && residual);
-    S3GateArgs g;
-    dim3 grid;
-    if (const int rc = sconv_plan<NT>(x, packed, bias, nullptr, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, 0, 1, 0, g.a, grid)) return rc;
-    g.trunk = trunk;
-    if (cout % 192 == 0) hipLaunchKernelGGL((sconv_gate_kernel<NT, 4, 8>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL((sconv_gate_kernel<NT, 2, 4>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
+                       sconv_nq(cout), ks, nt == 3 ? 2 : 1, total);
     LAUNCH_CHECK();
     return 0;
 }
 // the narrow launches: a form the three bodies have, 48 or 96 channels per workgroup and fewer than the pack's block (192 where cout is a multiple of 192, else 96)
 static inline bool sconv_narrow_ok(int form, int ks, int cin, int cout, int cpw) {
-    return (form == 0 || form == 3 || form == 1) && (cpw == 48 || cpw == 96) && sconv_ok(form, cin, cout, ks) && cpw < (cout % 192 == 0 ? 192 : 96);
-}
-template <int NT, int KS>
-static int sconv_narrow_launch(void *stream, int cpw, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                               int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    S3NarrowArgs g;
-    dim3 grid;
-    if (const int rc = sconv_plan<NT>(x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, KS, shuffle, g.a, grid, cpw)) return rc;
-    if (cpw == 96) hipLaunchKernelGGL((k_narrow_conv<NT, 2, 4, KS, 4>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
-    else if (cout % 192 == 0) hipLaunchKernelGGL((k_narrow_conv<NT, 1, 2, KS, 4>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL((k_narrow_conv<NT, 1, 2, KS, 2>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
-    LAUNCH_CHECK();
-    return 0;
-}
-template <int NT>
-static int sconv_gate_narrow_launch(void *stream, int cpw, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
-                                    int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
-    ARG_CHECK(trunk && residual);
-    S3GateArgs g;
-    dim3 grid;
-    if (const int rc = sconv_plan<NT>(x, packed, bias, nullptr, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, 0, 1, 0, g.a, grid, cpw)) return rc;
-    g.trunk = trunk;
-    if (cpw == 96) hipLaunchKernelGGL((k_narrow_gate<NT, 2, 4, 4>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL((k_narrow_gate<NT, 1, 2, 4>), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, g);
-    LAUNCH_CHECK();
-    return 0;
+    return (form == 0 || form == 3 || form == 1) && (cpw == 48 || cpw == 96) && sconv_ok(form, cin, cout, ks) && cpw < sconv_nq(cout) * 48;
 }
 
-// the stride-2 forms: x [n][cin][hp][wp] with a `pad` apron and an even interior H x W; out / residual [n][cout][H / 2 + 2 oring][W / 2 + 2 oring], whose
-// interior window is written.  S3Args: hp / wp / pad / sphere are the input's, ohp / owp / ring / ringw the output's grid and window.
-// NT = 0: the fp32 form on the stride-1 fp32 pack; NT = 1: the single-pass bf16 form on the stride-1 single-pass pack (32-channel chunks, a 16-byte aligned pack).
-template <int NT>
-static int sconv_s2_launch(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
-                           int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring, int ks) {
-    ARG_CHECK(x && packed && bias && out && n > 0 && sconv_ok(NT, cin, cout, ks) && pad >= 0 && oring >= 0 && hp > 2 * pad && wp > 2 * pad && sphere >= 0 && sphere <= 1);
-    ARG_CHECK((hp - 2 * pad) % 2 == 0 && (wp - 2 * pad) % 2 == 0);           // even interiors: the last tap row / column is the interior's last
-    ARG_CHECK(ks == 1 || pad >= 1);                                         // the 3x3 taps reach one apron row above / column left of the interior
-    ARG_CHECK(!sphere || (pad >= 1 && hp >= 4 * pad && wp >= 4 * pad));     // the wrapped / reflected source of an apron cell is an interior cell
-    ARG_CHECK((double)sconv_ck(NT, ks) * hp * wp * 4.0 < 4294967296.0 && (!NT || ((uintptr_t)packed & 15) == 0) && ((uintptr_t)bias & 15) == 0 &&
-              (!slope || ((uintptr_t)slope & 15) == 0));
-    S3Args a;
-    a.x = x; a.w = (const float *)packed; a.bias = bias; a.slope = slope; a.res = residual; a.out = out;
-    a.n = n; a.cin = cin; a.cout = cout; a.hp = hp; a.wp = wp; a.pad = pad; a.sphere = sphere; a.ring = oring; a.ringw = oring;
-    const int oh = (hp - 2 * pad) / 2, ow = (wp - 2 * pad) / 2;
-    ARG_CHECK((long)oh + 2L * oring < (1L << 30) && (long)ow + 2L * oring < (1L << 30));
-    a.ooff = 0; a.ohp = oh + 2 * oring; a.owp = ow + 2 * oring; a.shuffle = 0; a.tall_last = 0;
-    const int nq = cout % 192 == 0 ? 4 : 2;
-    a.rw = S3_T / (8 / nq);
-    a.tiles_x = (ow + S3_T - 1) / S3_T; a.tiles_y = (oh + S3_T - 1) / S3_T;
-    const long tiles = (long)n * a.tiles_x * a.tiles_y;
-    ARG_CHECK(tiles < (1L << 31));
-    const dim3 grid((unsigned)tiles, nq == 4 ? cout / 192 : 1);
-    if (ks == 3 && nq == 4) hipLaunchKernelGGL((sconv_s2_kernel<NT, 4, 8, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (ks == 3) hipLaunchKernelGGL((sconv_s2_kernel<NT, 2, 4, 3>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else if (nq == 4) hipLaunchKernelGGL((sconv_s2_kernel<NT, 4, 8, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((sconv_s2_kernel<NT, 2, 4, 1>()), grid, dim3(S3_THREADS), 0, (hipStream_t)stream, a);
+// ---- one call, one contract, one kernel pick.  Every entry point below fills a SconvCall; sconv_launch is the only way from there to a kernel.
+struct SconvCall {
+    int nt, ks, stride, gate, cpw;                   // what is asked: the form (0 fp32, 3 split-bf16, 1 single-pass bf16), 3 or 1, 1 or 2, the gate epilogue,
+                                                     // channels per workgroup (0: wide, the pack's block)
+    const float *x;                                  // the operands: [n][cin][hp][wp]
+    const void *packed;                              // the form's stride-1 pack of that kernel size
+    const float *bias, *slope, *residual, *trunk;
+    float *out;
+    int n, cin, cout, hp, wp, pad, sphere;
+    int ring, ring_w;                                // stride 1: the window in the input's grid; stride 2: the ring of the OUTPUT's grid around its interior, the window
+    int out_crop, shuffle;                           // stride 1 only
+};
+// the argument contract, tile geometry and grid of a launch.  Stride 2: x has a `pad` apron and an even interior H x W; out / residual are
+// [n][cout][H / 2 + 2 ring][W / 2 + 2 ring], whose interior is written; in S3Args hp / wp / pad / sphere are the input's, ohp / owp / ring / ringw the output's grid and window.
+static int sconv_plan(const SconvCall &c, S3Args &a, dim3 &grid, int &nq) {
+    // what the forms ask of a call of their own
+    ARG_CHECK(!c.cpw || (c.stride == 1 && sconv_narrow_ok(c.nt, c.ks, c.cin, c.cout, c.cpw) && (c.ks == 3 || (c.pad == 0 && c.sphere == 0)) && (!c.gate || c.cout % 192 == 0)));
+    ARG_CHECK(!c.gate || (c.trunk && c.residual && c.stride == 1 && c.ks == 1));
+    // what every call owes
+    ARG_CHECK(c.x && c.packed && c.bias && c.out && c.n > 0 && sconv_ok(c.nt, c.cin, c.cout, c.ks) && c.pad >= 0 && c.sphere >= 0);
+    ARG_CHECK(!c.sphere || (c.pad >= 1 && c.hp >= 4 * c.pad && c.wp >= 4 * c.pad));   // the wrapped / reflected source of an apron cell is an interior cell
+    ARG_CHECK((double)sconv_ck(c.nt, c.ks) * c.hp * c.wp * 4.0 < 4294967296.0 && (!c.nt || ((uintptr_t)c.packed & 15) == 0) && ((uintptr_t)c.bias & 15) == 0 &&
+              (!c.slope || ((uintptr_t)c.slope & 15) == 0));                // a chunk's cells at 32-bit byte offsets; 16-byte operand loads
+    int rows, cols;                                                         // the window, in cells of the output
+    if (c.stride == 1) {
+        ARG_CHECK(c.ring >= c.ks / 2 && c.ring_w >= c.ring && c.hp > 2 * c.ring && c.wp > 2 * c.ring_w && c.out_crop >= 0 && c.out_crop <= c.ring && c.sphere <= 2);
+        ARG_CHECK(!c.residual || c.out_crop == 0 || c.shuffle);             // the residual has the input's geometry -- or, shuffled, the output's
+        ARG_CHECK(!c.shuffle || (((uintptr_t)c.out & 7) == 0 && ((uintptr_t)c.residual & 7) == 0));   // the shuffled store / residual load move aligned pairs
+        rows = c.hp - 2 * c.ring; cols = c.wp - 2 * c.ring_w;
+        a.ooff = c.out_crop; a.ohp = c.hp - 2 * c.out_crop; a.owp = c.wp - 2 * c.out_crop; a.shuffle = c.shuffle;
+    } else {
+        ARG_CHECK(c.stride == 2 && c.nt != 3 && c.ring >= 0 && c.ring_w == c.ring && c.hp > 2 * c.pad && c.wp > 2 * c.pad && c.sphere <= 1);
+        ARG_CHECK((c.hp - 2 * c.pad) % 2 == 0 && (c.wp - 2 * c.pad) % 2 == 0);   // even interiors: the last tap row / column is the interior's last
+        ARG_CHECK(c.ks == 1 || c.pad >= 1);                                 // the 3x3 taps reach one apron row above / column left of the interior
+        rows = (c.hp - 2 * c.pad) / 2; cols = (c.wp - 2 * c.pad) / 2;
+        ARG_CHECK((long)rows + 2L * c.ring < (1L << 30) && (long)cols + 2L * c.ring < (1L << 30));
+        a.ooff = 0; a.ohp = rows + 2 * c.ring; a.owp = cols + 2 * c.ring; a.shuffle = 0;
+    }
+    a.x = c.x; a.w = (const float *)c.packed; a.bias = c.bias; a.slope = c.slope; a.res = c.residual; a.out = c.out;
+    a.n = c.n; a.cin = c.cin; a.cout = c.cout; a.hp = c.hp; a.wp = c.wp; a.pad = c.pad; a.sphere = c.sphere; a.ring = c.ring; a.ringw = c.ring_w;
+    nq = c.cpw ? c.cpw / 48 : sconv_nq(c.cout);                             // a workgroup's NQ * 48 channels
+    const int nrg = 8 / nq, full = rows / S3_T, rem = rows - full * S3_T;
+    a.rw = S3_T / nrg;
+    // the remainder fits one more row per wave of the last tile row; not at stride 2 (no tall tile there: a remainder takes an ordinary tile row)
+    a.tall_last = c.stride == 1 && sconv_tall(c.nt, nq, c.ks) && rem > 0 && rem <= nrg && full > 0;
+    a.tiles_x = (cols + S3_T - 1) / S3_T;
+    a.tiles_y = a.tall_last ? full : (rows + S3_T - 1) / S3_T;
+    const long tiles = (long)c.n * a.tiles_x * a.tiles_y;
+    ARG_CHECK(tiles < (1L << 31) && (!c.cpw || c.cout / c.cpw < 65536));
+    grid = dim3((unsigned)tiles, c.cout / (nq * 48));
+    return 0;
+}
+// A run-time value as a template argument, through a generic lambda (codec_fused.hip: imp_tables_launch).  The workgroup shapes are (NQ, PQ) with RW = 2 NQ:
+// the wide (4, 4) and (2, 2), the narrow (2, 4), (1, 4) and (1, 2).  Each branch below is closed where no kernel of it exists, and the contract above refuses
+// the same calls: no split-bf16 form at stride 2, no narrow gate on a pack of 96-channel blocks.
+template <int V> using sconv_int = std::integral_constant<int, V>;
+static int sconv_launch(void *stream, const SconvCall &c) {
+    S3GateArgs g;
+    dim3 grid;
+    int nq;
+    if (const int rc = sconv_plan(c, g.a, grid, nq)) return rc;
+    g.trunk = c.trunk;
+    const int pq = sconv_nq(c.cout);
+    auto launch = [&](auto kernel, const auto &args) { hipLaunchKernelGGL(kernel, grid, dim3(S3_THREADS), 0, (hipStream_t)stream, args); };
+    auto pick = [&](auto nt_, auto ks_, auto nq_, auto pq_) {
+        constexpr int NT = decltype(nt_)::value, KS = decltype(ks_)::value, NQ = decltype(nq_)::value, PQ = decltype(pq_)::value, RW = 2 * NQ;
+        if constexpr (NQ != PQ) {
+            if (!c.gate) launch(&k_narrow_conv<NT, NQ, RW, KS, PQ>, S3NarrowArgs{g.a});
+            else if constexpr (PQ == 4) launch(&k_narrow_gate<NT, NQ, RW, PQ>, g);
+        } else if (c.gate) launch(sconv_gate_kernel<NT, NQ, RW>(), g);
+        else if (c.stride == 1) launch(sconv_kernel<NT, NQ, RW, KS>(), g.a);
+        else if constexpr (NT != 3) launch(sconv_s2_kernel<NT, NQ, RW, KS>(), g.a);
+    };
+    auto by_shape = [&](auto nt_, auto ks_) {
+        if (nq == 4) pick(nt_, ks_, sconv_int<4>(), sconv_int<4>());
+        else if (nq == pq) pick(nt_, ks_, sconv_int<2>(), sconv_int<2>());
+        else if (nq == 2) pick(nt_, ks_, sconv_int<2>(), sconv_int<4>());
+        else if (pq == 4) pick(nt_, ks_, sconv_int<1>(), sconv_int<4>());
+        else pick(nt_, ks_, sconv_int<1>(), sconv_int<2>());
+    };
+    auto by_ks = [&](auto nt_) { if (c.ks == 3) by_shape(nt_, sconv_int<3>()); else by_shape(nt_, sconv_int<1>()); };
+    if (c.nt == 3) by_ks(sconv_int<3>()); else if (c.nt == 1) by_ks(sconv_int<1>()); else by_ks(sconv_int<0>());
     LAUNCH_CHECK();
     return 0;
 }
@@ -593,7 +578,7 @@ LIC360_API long lic360_sconv3x3_packed_floats(int cin, int cout) { return s3_pac
 LIC360_API int lic360_sconv3x3_pack(void *stream, const float *weight, float *packed, int cin, int cout) { return s3_pack(stream, weight, packed, cin, cout, 3); }
 LIC360_API int lic360_sconv3x3(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    return sconv_launch<0>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+    return sconv_launch(stream, {0, 3, 1, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, shuffle});
 }
 // the transforms' 1x1 layers on the same body (K = input channels only, no halo): bias + PReLU + residual in the epilogue, the window as above
 LIC360_API int lic360_sconv1x1_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 1) ? 1 : 0; }
@@ -601,7 +586,7 @@ LIC360_API long lic360_sconv1x1_packed_floats(int cin, int cout) { return s3_pac
 LIC360_API int lic360_sconv1x1_pack(void *stream, const float *weight, float *packed, int cin, int cout) { return s3_pack(stream, weight, packed, cin, cout, 1); }
 LIC360_API int lic360_sconv1x1(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
-    return sconv_launch<0>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+    return sconv_launch(stream, {0, 1, 1, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, shuffle});
 }
 // the split-bf16 forms of the four
 LIC360_API int lic360_sconv3x3_bf16x3_supported(int cin, int cout) { return sconv_ok(3, cin, cout, 3) ? 1 : 0; }
@@ -609,14 +594,14 @@ LIC360_API long lic360_sconv3x3_bf16x3_packed_bytes(int cin, int cout) { return 
 LIC360_API int lic360_sconv3x3_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(3, stream, weight, packed, cin, cout, 3); }
 LIC360_API int lic360_sconv3x3_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                       int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    return sconv_launch<3>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+    return sconv_launch(stream, {3, 3, 1, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, shuffle});
 }
 LIC360_API int lic360_sconv1x1_bf16x3_supported(int cin, int cout) { return sconv_ok(3, cin, cout, 1) ? 1 : 0; }
 LIC360_API long lic360_sconv1x1_bf16x3_packed_bytes(int cin, int cout) { return b3_packed_bytes(3, cin, cout, 1); }
 LIC360_API int lic360_sconv1x1_bf16x3_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(3, stream, weight, packed, cin, cout, 1); }
 LIC360_API int lic360_sconv1x1_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                       int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
-    return sconv_launch<3>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+    return sconv_launch(stream, {3, 1, 1, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, shuffle});
 }
 // the single-pass bf16 forms of the four: the argument lists of the split-bf16 ones, a pack of their own (hi planes only, 2 bytes per weight)
 LIC360_API int lic360_sconv3x3_bf16x1_supported(int cin, int cout) { return sconv_ok(1, cin, cout, 3) ? 1 : 0; }
@@ -624,66 +609,60 @@ LIC360_API long lic360_sconv3x3_bf16x1_packed_bytes(int cin, int cout) { return 
 LIC360_API int lic360_sconv3x3_bf16x1_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(1, stream, weight, packed, cin, cout, 3); }
 LIC360_API int lic360_sconv3x3_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                       int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    return sconv_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, 3, shuffle);
+    return sconv_launch(stream, {1, 3, 1, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, shuffle});
 }
 LIC360_API int lic360_sconv1x1_bf16x1_supported(int cin, int cout) { return sconv_ok(1, cin, cout, 1) ? 1 : 0; }
 LIC360_API long lic360_sconv1x1_bf16x1_packed_bytes(int cin, int cout) { return b3_packed_bytes(1, cin, cout, 1); }
 LIC360_API int lic360_sconv1x1_bf16x1_pack(void *stream, const float *weight, void *packed, int cin, int cout) { return b3_pack(1, stream, weight, packed, cin, cout, 1); }
 LIC360_API int lic360_sconv1x1_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                       int n, int cin, int cout, int hp, int wp, int ring, int ring_w, int crop, int shuffle) {
-    return sconv_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, 1, shuffle);
+    return sconv_launch(stream, {1, 1, 1, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, crop, shuffle});
 }
 // the attention blocks' gate in the three forms: out = residual + trunk * sigmoid(conv1x1(x) + bias) on the window, one launch; they read the stride-1 1x1 packs
 LIC360_API int lic360_sconv1x1_gate(void *stream, const float *x, const float *packed, const float *bias, const float *trunk, const float *residual, float *out,
                                     int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
-    return sconv_gate_launch<0>(stream, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
+    return sconv_launch(stream, {0, 1, 1, 1, 0, x, packed, bias, nullptr, residual, trunk, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, 0, 0});
 }
 LIC360_API int lic360_sconv1x1_gate_bf16x3(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
                                            int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
-    return sconv_gate_launch<3>(stream, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
+    return sconv_launch(stream, {3, 1, 1, 1, 0, x, packed, bias, nullptr, residual, trunk, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, 0, 0});
 }
 LIC360_API int lic360_sconv1x1_gate_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual, float *out,
                                            int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
-    return sconv_gate_launch<1>(stream, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
+    return sconv_launch(stream, {1, 1, 1, 1, 0, x, packed, bias, nullptr, residual, trunk, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, 0, 0});
 }
 // the stride-2 forms of the fp32 pair (the analysis transform's down-sampling layers); they read the stride-1 packs
 LIC360_API int lic360_sconv3x3s2_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 3) ? 1 : 0; }
 LIC360_API int lic360_sconv3x3s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                  int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring) {
-    return sconv_s2_launch<0>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, oring, 3);
+    return sconv_launch(stream, {0, 3, 2, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, pad, sphere, oring, oring, 0, 0});
 }
 LIC360_API int lic360_sconv1x1s2_supported(int cin, int cout) { return sconv_ok(0, cin, cout, 1) ? 1 : 0; }
 LIC360_API int lic360_sconv1x1s2(void *stream, const float *x, const float *packed, const float *bias, const float *slope, const float *residual, float *out,
                                  int n, int cin, int cout, int hp, int wp, int pad, int oring) {
-    return sconv_s2_launch<0>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, 0, oring, 1);
+    return sconv_launch(stream, {0, 1, 2, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, pad, 0, oring, oring, 0, 0});
 }
 // the single-pass bf16 forms of the stride-2 pair (opt-in: lic360_models.set_conv_precision(.., stride2="bf16x1")); they read the stride-1 single-pass packs
 LIC360_API int lic360_sconv3x3s2_bf16x1_supported(int cin, int cout) { return sconv_ok(1, cin, cout, 3) ? 1 : 0; }
 LIC360_API int lic360_sconv3x3s2_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                         int n, int cin, int cout, int hp, int wp, int pad, int sphere, int oring) {
-    return sconv_s2_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, oring, 3);
+    return sconv_launch(stream, {1, 3, 2, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, pad, sphere, oring, oring, 0, 0});
 }
 LIC360_API int lic360_sconv1x1s2_bf16x1_supported(int cin, int cout) { return sconv_ok(1, cin, cout, 1) ? 1 : 0; }
 LIC360_API int lic360_sconv1x1s2_bf16x1(void *stream, const float *x, const void *packed, const float *bias, const float *slope, const float *residual, float *out,
                                         int n, int cin, int cout, int hp, int wp, int pad, int oring) {
-    return sconv_s2_launch<1>(stream, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, 0, oring, 1);
+    return sconv_launch(stream, {1, 1, 2, 0, 0, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, pad, 0, oring, oring, 0, 0});
 }
 // the narrow workgroups (above: "the narrow workgroups"): one entry point for the stride-1 convolutions of every form and kernel size, one for the gate.  form: 0 fp32,
 // 3 split-bf16, 1 single-pass bf16; `packed` is the form's ordinary pack of that kernel size; ks = 1 takes pad = 0, sphere = 0.  Refusals precede any launch.
 LIC360_API int lic360_sconv_narrow_supported(int form, int ks, int cin, int cout, int cpw) { return sconv_narrow_ok(form, ks, cin, cout, cpw) ? 1 : 0; }
 LIC360_API int lic360_sconv_narrow(void *stream, int form, int ks, int cpw, const float *x, const void *packed, const float *bias, const float *slope, const float *residual,
                                    float *out, int n, int cin, int cout, int hp, int wp, int pad, int sphere, int ring, int ring_w, int out_crop, int shuffle) {
-    ARG_CHECK(sconv_narrow_ok(form, ks, cin, cout, cpw) && (ks == 3 || (pad == 0 && sphere == 0)));
-#define NARROW_CASE(NT, KS) \
-    if (form == NT && ks == KS) return sconv_narrow_launch<NT, KS>(stream, cpw, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, shuffle)
-    NARROW_CASE(0, 3); NARROW_CASE(0, 1); NARROW_CASE(3, 3); NARROW_CASE(3, 1); NARROW_CASE(1, 3);
-#undef NARROW_CASE
-    return sconv_narrow_launch<1, 1>(stream, cpw, x, packed, bias, slope, residual, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, shuffle);
+    ARG_CHECK(cpw != 0);                                                    // (0 is the descriptor's "wide")
+    return sconv_launch(stream, {form, ks, 1, 0, cpw, x, packed, bias, slope, residual, nullptr, out, n, cin, cout, hp, wp, pad, sphere, ring, ring_w, out_crop, shuffle});
 }
 LIC360_API int lic360_sconv1x1_gate_narrow(void *stream, int form, int cpw, const float *x, const void *packed, const float *bias, const float *trunk, const float *residual,
                                            float *out, int n, int cin, int cout, int hp, int wp, int ring, int ring_w) {
-    ARG_CHECK(sconv_narrow_ok(form, 1, cin, cout, cpw) && cout % 192 == 0);
-    if (form == 0) return sconv_gate_narrow_launch<0>(stream, cpw, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
-    if (form == 3) return sconv_gate_narrow_launch<3>(stream, cpw, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
-    return sconv_gate_narrow_launch<1>(stream, cpw, x, packed, bias, trunk, residual, out, n, cin, cout, hp, wp, ring, ring_w);
+    ARG_CHECK(cpw != 0);
+    return sconv_launch(stream, {form, 1, 1, 1, cpw, x, packed, bias, nullptr, residual, trunk, out, n, cin, cout, hp, wp, 0, 0, ring, ring_w, 0, 0});
 }

@@ -113,7 +113,7 @@ def _records_grad(x, conv, mod=None):
     return torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (mod is not None and any(p.requires_grad for p in mod.parameters())))
 
 
-# The launch geometry, restated from sconv_plan, sconv_tall and sconv_s2_launch of csrc/conv3x3_kernels.hip (tests/test_sconv_routes_cpu.py holds it against the
+# The launch geometry, restated from sconv_plan (both strides) and sconv_tall of csrc/conv3x3_kernels.hip (tests/test_sconv_routes_cpu.py holds it against the
 # restatements of the exact tests' case files)
 def _workgroups(n, nr, nc, cout, ks, stride=1, cpw=None, precision="fp32"):
     """(workgroups, tall last tile row?) of one launch on a window of nr x nc cells -- at stride 2 the OUTPUT's -- of n images: one per 16 x 16 tile and `cpw` output channels,

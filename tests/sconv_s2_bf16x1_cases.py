@@ -31,7 +31,7 @@ PRODUCTION = [c for c in CASES if c.prod]
 BODIES = {(4, 8, 3), (2, 4, 3), (4, 8, 1), (2, 4, 1)}                      # (NQ, RW, KS) of every k_sconv_b1s2 instantiation
 
 
-# ---- the launch geometry, restated from sconv_ok(1, ..) / sconv_s2_launch<1> (csrc/conv3x3_kernels.hip)
+# ---- the launch geometry, restated from sconv_ok(1, ..) / sconv_plan's stride-2 branch (csrc/conv3x3_kernels.hip)
 def supported(cin, cout, ks):
     return ks in (1, 3) and cin >= CHUNK and cin % CHUNK == 0 and cout >= 96 and (cout % 192 == 0 or cout == 96)
 

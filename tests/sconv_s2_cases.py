@@ -64,7 +64,7 @@ PRODUCTION = [
 CASES = SMALL + PRODUCTION
 
 
-# ---- the launch geometry, restated from sconv_ok / sconv_s2_launch (csrc/conv3x3_kernels.hip)
+# ---- the launch geometry, restated from sconv_ok / sconv_plan's stride-2 branch (csrc/conv3x3_kernels.hip)
 def chunk_of(ks):
     return 32 if ks == 1 else 16
 

@@ -22,7 +22,7 @@ MUTATED = [c for c in s2.CASES if _macs(c) <= MUTATION_MACS]
 
 
 def test_every_case_is_a_legal_call():
-    """sconv_s2_launch's argument contract, restated: a case the native check would refuse tests nothing"""
+    """sconv_plan's stride-2 argument contract, restated: a case the native check would refuse tests nothing"""
     names = [c.name for c in s2.CASES]
     assert len(set(names)) == len(names)
     for c in s2.CASES:
@@ -73,7 +73,7 @@ def test_the_case_list_covers_the_branch_matrix():
             need(f + "pad 3 under the sphere rule", mine(lambda c, b: c.sphere == 1 and c.pad == 3))
         need(f + "a production shape", mine(lambda c, b: c.prod))
     assert not missing, "the case list lost: " + "; ".join(missing)
-    # every kernel instantiation sconv_s2_launch can pick: k_sconv3x3s2<NQ, RW, KS>
+    # every kernel instantiation sconv_launch can pick at stride 2: k_sconv3x3s2<NQ, RW, KS>
     assert {(b.nq, b.rw, b.ks) for c, b in br} == {(4, 8, 3), (2, 4, 3), (4, 8, 1), (2, 4, 1)}
 
 
@@ -170,7 +170,7 @@ def test_describe_mismatch_names_the_tile():
 
 
 def test_fusable_s2_counts_tiles_on_the_output_window(monkeypatch):
-    """lic360_models._fusable_s2 restates sconv_s2_launch's tile count, on the OUTPUT window; odd interiors never go fused"""
+    """lic360_models._fusable_s2 restates sconv_plan's stride-2 tile count, on the OUTPUT window; odd interiors never go fused"""
     import lic360_models as lm
     monkeypatch.setattr(lm.lic360, "sconv3x3s2_supported", lambda cin, cout: True)
     monkeypatch.setattr(lm.lic360, "sconv1x1s2_supported", lambda cin, cout: True)
