@@ -28,7 +28,7 @@
 //     step costs no vector address arithmetic: with 4x4x1 MFMAs the VALU does not co-issue (SQ_VALU_MFMA_COEXEC_CYCLES
 //     = 0), every other VALU instruction is time taken from the matrix pipe.
 // H <= 64: lane = image row.  Taller images are cut into 64-row windows (SEG, see dc6_body).
-#define D6_GRID 256                                  // workgroups per launch: one per CU
+// D6_GRID (workgroups per launch: one per CU) is stated in need.h, where the list builder's placement pass reads it too
 #define D6_TAPE_BLOCKS 16                            // group blocks of a taped launch (ngroup <= 48)
 #define D6_TAPE_WAVES 6                              // waves per tape (tape_c <= 6 samples)
 #define D3_S0 (4 + C4_PS - 1)                         // zero rows before diagonal 0 (and after the last)
@@ -279,7 +279,8 @@ __device__ __forceinline__ void dc6_body(const Dc3Args &a, const Dc3Tape *tape, 
     auto nth_task = [&](int k) __attribute__((always_inline)) { return k * wgs_per_xcd + ((k & 1) ? wgs_per_xcd - 1 - wg_in_xcd : wg_in_xcd); };
     const int ns_x = flat ? a.N : (a.N - xcd + 7) >> 3;
     // Task order.  Decode order: group block major (heaviest first), sample minor -- with the boustrophedon walk below the
-    // static schedule balances to ~1% (sample-major order was measured: 15% less HBM traffic but 3% slower).
+    // static schedule balances to ~1% (sample-major order was measured: 15% less HBM traffic but 3% slower).  LIST launches take whatever order
+    // their builder emitted (need.h: grouped emission and the placement pass, LIC360_DC_ORDER; DESIGN 4.6 "List order").
     const int nseg = SEG ? a.nseg : 1;
     // Packing several samples into the 64 lanes of a task: lane l always reads LDS column l + k0, so all that changes is which sample's band columns
     // sit where in LDS and which (sample, row) a lane stores.  H <= 64: TAPE packing (Dc3Args, launch_cconv4v6_dc; rounds 1-4 packed two / three

@@ -978,6 +978,16 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
             c->dcl.cap = (int)(((G + 2) / 3) * 3 * (B / 8) * DCL_WAVES_PER_WINDOW(h));
             if (c->dcl_list.alloc((size_t)NEED_LAYERS * c->P * 8 * c->dcl.cap) || c->dcl_cnt.alloc((size_t)NEED_LAYERS * c->P * 8)) return 1;
             c->dcl.list = c->dcl_list; c->dcl.cnt = c->dcl_cnt;
+            // order of the lists (need.h; LIC360_DC_ORDER, read here like the switch above): "1" block major as in round 6, "1p" that order with the
+            // placement pass, "2" / "4" / "8" blocks in groups of that many, placed.  Default 8: the only order whose headline beat the block-major one by
+            // three times the spread of the runs (DESIGN 4.6 "List order")
+            c->dcl.nb = 8; c->dcl.place = true;
+            if (const char *e = getenv("LIC360_DC_ORDER")) {
+                if (!lic360_dc_order_parse(e, &c->dcl.nb, &c->dcl.place)) {
+                    lic360_set_error("LIC360_DC_ORDER=%s: expected 1, 1p, 2, 4 or 8", e);
+                    return 1;
+                }
+            }
         }
         HIP_TRY(hipMemset(c->stats, 0, 2 * NEED_LAYERS * NEED_STAT_G * sizeof(unsigned long long)));
     }

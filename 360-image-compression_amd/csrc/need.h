@@ -61,6 +61,57 @@ __host__ __device__ inline int dcl_wave_pieces(const int *lo, const int *hi, int
     return nwin;
 }
 
+// ---- decode order: which workgroup meets which record when (LIC360_DC_ORDER; DESIGN 4.6 "List order").
+// The decode kernel's static walk (cconv4v6_dc.inc: nth_task): workgroup w of an XCD's W runs, as its k-th task, the record at k W + w (k even) or
+// k W + W - 1 - w (k odd) of the XCD's list.  A ROUND is therefore W consecutive records, run side by side through one L2; the builder decides which
+// records share a round (the emission order, k_dc_tasks) and which workgroup gets which of them (the placement pass, k_dc_place).
+#define D6_GRID 256                        // workgroups per launch of the decode kernels: one per CU
+#define DCL_WGS(xcd) ((D6_GRID - (xcd) + 7) >> 3)   // workgroups of a launch that run on XCD xcd (the kernel's wgs_per_xcd)
+#define DCL_MAXW 32                        // DCL_WGS(0)
+#define DCL_MAX_NB 8                       // blocks per emission group (LIC360_DC_ORDER = 1, 2, 4, 8)
+// Work of a record = the steps of its block's longest chain (what k_dc_balance evens out between the XCDs); a workgroup's load in the placement pass
+// counts DCL_TASK_SWITCH more per task (setup, drain and epilogue of a task, in steps).
+#define DCL_TASK_SWITCH 3
+__host__ __device__ inline int dcl_steps(unsigned x, int G) { const int g0 = (int)(x & 127u), s = g0 + 2 + 4 + 1; return s < G ? s : G; }
+// Grouped emission: the blocks of a plane (heaviest first) in groups of nb; inside a group net, then record index r, then block -- record r of every
+// block of the group, one net, lie next to each other (neighbouring blocks of a sample read band rows that overlap in 8 of 11 diagonals).
+// -> position inside the group of record r of net `net` of the group's block jj (nrec[0..n): records per net of the group's blocks).  nb = 1: net * nrec + r.
+__host__ __device__ inline int dcl_group_pos(const int *nrec, int n, int jj, int net, int r) {
+    int tot = 0, before = 0;
+    for (int i = 0; i < n; ++i) { tot += nrec[i]; before += (nrec[i] < r ? nrec[i] : r) + (i < jj && nrec[i] > r); }
+    return net * tot + before;
+}
+// Placement of ONE round: its n <= W records (cost[i], list order) sorted by cost descending (ties: list index) go to the workgroups that have a slot
+// in this round (all of them; in a short last round those of its first n slots) by load ascending (ties: workgroup index); pos[i] = the slot of record i
+// in the round, load[w] += its cost.  Threads t0, t0 + tstep, .. share the work between `sync`s (device: the lanes of a workgroup and __syncthreads;
+// host: t0 = 0, tstep = 1 and a sync that does nothing); inv: n ints of scratch.
+template <class Sync>
+__host__ __device__ inline void dcl_place_round(const int *cost, int n, int W, int odd, int *load, int *inv, int *pos, int t0, int tstep, Sync sync) {
+    for (int t = t0; t < n; t += tstep) {
+        const int w = odd ? W - n + t : t;                                  // candidate t, ascending workgroup index
+        int rl = 0, rc = 0;
+        for (int u = 0; u < n; ++u) {
+            const int wu = odd ? W - n + u : u;
+            rl += load[wu] < load[w] || (load[wu] == load[w] && u < t);
+            rc += cost[u] > cost[t] || (cost[u] == cost[t] && u < t);
+        }
+        inv[rl] = w;
+        pos[t] = rc;
+    }
+    sync();
+    for (int t = t0; t < n; t += tstep) {
+        const int w = inv[pos[t]];
+        pos[t] = odd ? W - 1 - w : w;
+        load[w] += cost[t];
+    }
+    sync();
+}
+// The order in which the placement pass takes the rounds of a list of n records: a short last round FIRST, then the full rounds in list order.  The short
+// round's records can only go to the workgroups of its first slots; charged first, the full rounds even that out (taken last, it lands on whatever those
+// workgroups carry by then: modelled max / mean load of the smooth-mask lists' last layer at NB = 4 1.079 against 1.040 this way, block major 1.072).
+__host__ __device__ inline int dcl_place_order(int it, int n, int W) { return n % W == 0 ? it : (it == 0 ? (n - 1) / W : it - 1); }
+__host__ __device__ inline int dcl_max(const int *v, int n) { int m = 0; for (int i = 0; i < n; ++i) m = v[i] > m ? v[i] : m; return m; }
+
 // units per block of the encode kernels' task order (c16_fill_args and the list builder must agree): 16 measured best without lists (DESIGN 4.1 a);
 // LIC360_EC_GBK overrides it for A/B runs
 #include <cstdlib>
@@ -83,5 +134,14 @@ struct lic360_dc_lists {                   // decode order
     uint4 *list = nullptr;                 // [12][P][8][cap]
     int *cnt = nullptr;                    // [12][P][8]
     int cap = 0, P = 0;
+    int nb = 1;                            // blocks per emission group (1: block major, the order of round 6)
+    bool place = false;                    // the placement pass after the XCD balancing
 };
+// LIC360_DC_ORDER: "1" (nb 1, no placement), "1p" (nb 1, placed), "2" / "4" / "8" (groups of nb blocks, placed); 0 = not one of these
+static inline int lic360_dc_order_parse(const char *e, int *nb, bool *place) {
+    const int v = e && e[0] >= '1' && e[0] <= '8' ? e[0] - '0' : 0;
+    if (!v || (v & (v - 1)) || (e[1] && !(v == 1 && e[1] == 'p' && !e[2]))) return 0;
+    *nb = v; *place = v > 1 || e[1] == 'p';
+    return 1;
+}
 int lic360_dc_lists_build(void *stream, const signed char *need_d, int B, int G, int H, int W, const lic360_dc_lists &l, unsigned long long *stats);

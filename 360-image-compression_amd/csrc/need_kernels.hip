@@ -10,6 +10,7 @@
 #include "common.h"
 #include "need.h"
 #include <cstdlib>
+#include <vector>
 
 // ------------------------------------------------------------------------------------------------ need maps
 // one workgroup per image; layer l is computed from layer l + 1 of the same image, a workgroup barrier between the layers
@@ -201,7 +202,9 @@ int lic360_ec_lists_build(void *stream, const signed char *tmax, int B, int G, i
 // One workgroup per (XCD, plane, layer): the group blocks of the plane as launch_cconv4v6_dc sees them (three groups on the staggered diagonals
 // s0, s0 - 1, s0 - 2); per block and image of the XCD's list the hull of the rows that need one of the block's groups; per block, net and chunk of
 // <= 8 samples the windows packed into waves (dcl_wave_pieces) -- or one plain record per live sample where packing saves nothing (plain tasks are
-// cheaper to set up).  Order: group block major (heaviest first), net, chunk: the launch order of the unpacked kernel.
+// cheaper to set up).  Order: group block major (heaviest first), net, chunk: the launch order of the unpacked kernel -- or, with a.nb > 1, the blocks
+// in groups of a.nb and inside a group net, record, block (need.h: dcl_group_pos), so that the records a round of workgroups runs side by side share
+// band rows.
 #define DCL_MAXB 24                                                         // group blocks of a plane (ngroup <= 72)
 #define DCL_MAXM 64                                                         // images of an XCD's list (B <= 512)
 struct DcListArgs {
@@ -209,7 +212,7 @@ struct DcListArgs {
     uint4 *list;
     int *cnt;
     unsigned long long *stats;
-    int cap, l0, npb, G, H, W, P;
+    int cap, l0, npb, G, H, W, P, nb;
 };
 __global__ __launch_bounds__(128) void k_dc_tasks(const DcListArgs a) {
     __shared__ short wlo[DCL_MAXB][DCL_MAXM], whi[DCL_MAXB][DCL_MAXM];
@@ -277,7 +280,10 @@ __global__ __launch_bounds__(128) void k_dc_tasks(const DcListArgs a) {
     // pass 2 (one thread per block and net): the records
     if (tid < n_gbv * 3) {
         const int j = tid / 3, net = tid - j * 3, g0 = (n_gb - 1 - j) * 3, s0 = p - g0;
-        int o = offs[j] + net * nrec[j];
+        // where record r of this block and net goes: the blocks in groups of a.nb, inside a group net, record index, block (need.h: dcl_group_pos)
+        const int j0 = j - j % a.nb, jn = n_gbv - j0 < a.nb ? n_gbv - j0 : a.nb;
+        auto slot = [&](int r) { return offs[j0] + dcl_group_pos(nrec + j0, jn, j - j0, net, r); };
+        int r = 0;
         int cells[3] = {0, 0, 0};
         int dlo[3], dhi[3];
         for (int q = 0; q < 3; ++q) {
@@ -297,8 +303,8 @@ __global__ __launch_bounds__(128) void k_dc_tasks(const DcListArgs a) {
                 for (int k = 0; k < c; ++k)
                     if (hi[k] >= lo[k]) {
                         const unsigned gm = wgm[j][c0 + k];
+                        const int o = slot(r++);
                         if (o < a.cap) out[o] = make_uint4((unsigned)g0 | (unsigned)(nb + 8 * k) << 10, gm << 22, 0u, 0u);
-                        ++o;
                         count(0, H - 1, (int)gm);
                     }
             } else {
@@ -307,8 +313,8 @@ __global__ __launch_bounds__(128) void k_dc_tasks(const DcListArgs a) {
                 while (k < c && dcl_wave_pieces(lo, hi, H, c, k, slo, pc) > 0) {
                     unsigned gm = 0u;                                       // groups live in ANY of the record's samples (bits 22..24 of the first piece word)
                     for (int i = 0; i < 3; ++i) if (pc[i]) gm |= wgm[j][c0 + (pc[i] & 7)];
+                    const int o = slot(r++);
                     if (o < a.cap) out[o] = make_uint4((unsigned)g0 | 4u << 7 | (unsigned)nb << 10, pc[0] | gm << 22, pc[1], pc[2]);
-                    ++o;
                     for (int i = 0; i < 3; ++i) if (pc[i]) count(dcl_piece_slo(pc[i]), dcl_piece_shi(pc[i]), (int)gm);
                 }
             }
@@ -333,7 +339,7 @@ __global__ __launch_bounds__(64) void k_dc_balance(const DcListArgs a) {
     __shared__ int w[8], n[8];
     const int p = blockIdx.x, l = a.l0 + blockIdx.y, tid = threadIdx.x;
     const long li = ((long)l * a.P + p) * 8;
-    auto steps = [&](unsigned x) { const int g0 = (int)(x & 127u), s = g0 + 2 + 4 + 1; return s < a.G ? s : a.G; };
+    auto steps = [&](unsigned x) { return dcl_steps(x, a.G); };
     if (tid < 8) {
         const int c = a.cnt[li + tid];
         const uint4 *r = a.list + (li + tid) * a.cap;
@@ -357,17 +363,55 @@ __global__ __launch_bounds__(64) void k_dc_balance(const DcListArgs a) {
     for (int x = 0; x < 8; ++x) a.cnt[li + x] = n[x];
 }
 
+// Placement (need.h: dcl_place_round), after the balancing: per round of W = DCL_WGS(xcd) records the heaviest record goes to the least loaded workgroup,
+// so that a grouped emission order keeps the balance the boustrophedon walk has on the block-major one.  A record moves inside its round only.
+// A short last round can only go to the workgroups of its first slots, so it is charged first (need.h: dcl_place_order).  The rule stays greedy, and
+// on a few lists it still leaves the most loaded workgroup heavier than the list as emitted does.  So a first pass only adds up both sets of loads, and a list
+// is rewritten (second pass) only if its placed maximum is no larger than its maximum as emitted.  One workgroup per (XCD, plane, layer).
+__global__ __launch_bounds__(64) void k_dc_place(const DcListArgs a) {
+    __shared__ int cost[DCL_MAXW], load[DCL_MAXW], asis[DCL_MAXW], inv[DCL_MAXW], pos[DCL_MAXW];
+    const int xcd = blockIdx.x, p = blockIdx.y, l = a.l0 + blockIdx.z, tid = threadIdx.x, W = DCL_WGS(xcd);
+    const long li = ((long)l * a.P + p) * 8 + xcd;
+    uint4 *list = a.list + li * a.cap;
+    const int n = a.cnt[li];
+    if (n <= 1) return;
+    for (int pass = 0; pass < 2; ++pass) {
+        __syncthreads();                                                    // (the first pass's sums have been read)
+        if (tid < W) load[tid] = asis[tid] = 0;
+        for (int it = 0; it * W < n; ++it) {
+            const int k = dcl_place_order(it, n, W), r0 = k * W, m = n - r0 < W ? n - r0 : W;
+            uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+            __syncthreads();
+            if (tid < m) {
+                rec = list[r0 + tid];
+                cost[tid] = dcl_steps(rec.x, a.G) + DCL_TASK_SWITCH;
+                asis[(k & 1) ? W - 1 - tid : tid] += cost[tid];
+            }
+            __syncthreads();
+            dcl_place_round(cost, m, W, k & 1, load, inv, pos, tid, 64, [] { __syncthreads(); });
+            if (pass && tid < m) list[r0 + pos[tid]] = rec;
+        }
+        __syncthreads();
+        if (!pass && dcl_max(load, W) > dcl_max(asis, W)) return;           // (the same for every thread)
+    }
+}
+
 // layers 1..11 (cin = 4: hidden and last layers; the first layer keeps its full task list)
 int lic360_dc_lists_build(void *stream, const signed char *need_d, int B, int G, int H, int W, const lic360_dc_lists &l, unsigned long long *stats) {
     ARG_CHECK(need_d && l.list && l.cnt && B > 0 && B % 8 == 0 && B / 8 <= DCL_MAXM && H <= DCL_MAX_H && G <= 3 * DCL_MAXB && l.P == H + W + G - 2);
     ARG_CHECK(l.cap >= ((G + 2) / 3 < DCL_MAXB ? (G + 2) / 3 : DCL_MAXB) * 3 * (B / 8) * DCL_WAVES_PER_WINDOW(H) && 3L * B < (1L << 22));
     DcListArgs a;
-    a.need_d = need_d; a.list = l.list; a.cnt = l.cnt; a.stats = stats; a.cap = l.cap; a.l0 = 1; a.npb = B; a.G = G; a.H = H; a.W = W; a.P = l.P;
+    a.need_d = need_d; a.list = l.list; a.cnt = l.cnt; a.stats = stats; a.cap = l.cap; a.l0 = 1; a.npb = B; a.G = G; a.H = H; a.W = W; a.P = l.P; a.nb = l.nb;
+    ARG_CHECK(l.nb >= 1 && l.nb <= DCL_MAX_NB);
     hipLaunchKernelGGL(k_dc_tasks, dim3(8, l.P, NEED_LAYERS - 1), dim3(128), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK();
     static const bool balance = !getenv("LIC360_NOBALANCE");                // (A/B switch of the XCD balancing pass)
     if (balance) {
         hipLaunchKernelGGL(k_dc_balance, dim3(l.P, NEED_LAYERS - 1), dim3(64), 0, (hipStream_t)stream, a);
+        LAUNCH_CHECK();
+    }
+    if (l.place) {
+        hipLaunchKernelGGL(k_dc_place, dim3(8, l.P, NEED_LAYERS - 1), dim3(64), 0, (hipStream_t)stream, a);
         LAUNCH_CHECK();
     }
     return 0;
@@ -401,5 +445,41 @@ LIC360_API int lic360_dcl_pack_layout(int h, int c, const int *lo, const int *hi
         ++nw;
     }
     *n_waves = nw;
+    return 0;
+}
+
+// Host-only view of the list order (no GPU work): where the records of ONE XCD's list of one (layer, plane) go.  The list has n_blocks blocks in list
+// order (heaviest first), block j with first group g0[j] and nrec[j] records per net; record (j, net, r) has the identity id = 3 * (records per net of the
+// blocks before j) + net * nrec[j] + r -- its position in the block-major order.  emit[id] = its position after the grouped emission (groups of nb blocks;
+// nb = 1: id), slot[id] = after the placement pass over rounds of w records as well (place = 0: emit[id]).  For tests of the order on the CPU
+// (tests/test_dc_order_cpu.py).
+LIC360_API int lic360_dcl_order_layout(int n_blocks, const int *g0, const int *nrec, int ngroup, int nb, int place, int w, int *emit, int *slot) {
+    ARG_CHECK(n_blocks >= 0 && n_blocks <= DCL_MAXB && (n_blocks == 0 || (g0 && nrec)) && ngroup > 0 && ngroup <= 3 * DCL_MAXB && emit && slot);
+    ARG_CHECK(nb >= 1 && nb <= DCL_MAX_NB && w >= 1 && w <= DCL_MAXW);
+    for (int j = 0; j < n_blocks; ++j) ARG_CHECK(nrec[j] >= 0 && g0[j] >= 0 && g0[j] < ngroup);
+    int offs[DCL_MAXB + 1] = {0};
+    for (int j = 0; j < n_blocks; ++j) offs[j + 1] = offs[j] + 3 * nrec[j];
+    const int n = offs[n_blocks];
+    std::vector<int> cost(n);
+    for (int j = 0; j < n_blocks; ++j) {
+        const int j0 = j - j % nb, jn = n_blocks - j0 < nb ? n_blocks - j0 : nb;
+        for (int net = 0; net < 3; ++net)
+            for (int r = 0; r < nrec[j]; ++r) {
+                const int id = offs[j] + net * nrec[j] + r, e = offs[j0] + dcl_group_pos(nrec + j0, jn, j - j0, net, r);
+                emit[id] = slot[id] = e;
+                cost[e] = dcl_steps((unsigned)g0[j], ngroup) + DCL_TASK_SWITCH;
+            }
+    }
+    if (!place) return 0;
+    int load[DCL_MAXW] = {0}, asis[DCL_MAXW] = {0}, inv[DCL_MAXW], pos[DCL_MAXW];
+    std::vector<int> to(n);
+    for (int it = 0; it * w < n; ++it) {
+        const int k = dcl_place_order(it, n, w), r0 = k * w, m = n - r0 < w ? n - r0 : w;
+        for (int i = 0; i < m; ++i) asis[(k & 1) ? w - 1 - i : i] += cost[r0 + i];
+        dcl_place_round(cost.data() + r0, m, w, k & 1, load, inv, pos, 0, 1, [] {});
+        for (int i = 0; i < m; ++i) to[r0 + i] = r0 + pos[i];
+    }
+    if (dcl_max(load, w) > dcl_max(asis, w)) return 0;                      // (k_dc_place leaves such a list as emitted)
+    for (int id = 0; id < n; ++id) slot[id] = to[emit[id]];
     return 0;
 }

@@ -500,6 +500,14 @@ int lic360_need_maps(void *stream, const float *mask, int b, int g, int h, int w
  * (k | (slo & 63) << 3 | (shi & 63) << 9 | a0 << 15 | 1 << 21 | (slo >> 6) << 25 | (shi >> 6) << 26, 0 = none; room for 6 c words, 9 c words where
  * h > 64: a window taller than a wave is cut over up to three), *n_waves = waves used.  tests/test_dcl_pack.py, tests/test_dc_tall_cpu.py. */
 int lic360_dcl_pack_layout(int h, int c, const int *lo, const int *hi, unsigned *pieces, int *n_waves);
+/* Host-only (no GPU work): the order of ONE XCD's decode list of one (layer, plane) -- LIC360_DC_ORDER, read when a codec is created: "1" block major
+ * (heaviest three-group block first, then net, then record), "2" / "4" / "8" the blocks in groups of nb and inside a group net, record, block, followed by
+ * the placement pass (per round of w records -- what the XCD's w workgroups run side by side -- the heaviest record to the least loaded workgroup; a
+ * record stays in its round; "8" is the default), "1p" the block-major order with the placement pass.  The list's n_blocks blocks in list order: first group g0[j], nrec[j]
+ * records per net; record (j, net, r) is id = 3 * (nrec[0] + .. + nrec[j - 1]) + net * nrec[j] + r, its block-major position.  emit[id] = its position after
+ * the grouped emission, slot[id] = after the placement too (place = 0: emit[id]).  ngroup: the latent's groups (cost of a record =
+ * min(g0 + 7, ngroup) steps + 3 per task); 1 <= nb <= 8, 1 <= w <= 32, n_blocks <= 24.  tests/test_dc_order_cpu.py. */
+int lic360_dcl_order_layout(int n_blocks, const int *g0, const int *nrec, int ngroup, int nb, int place, int w, int *emit, int *slot);
 /* enable > 0: the following encodes / decodes count what they execute (0: stop; < 0: leave as it is).  out (host, 2 * 12 * 64 values, may be NULL; reading clears):
  * [0][layer][group block] live (tile, group block) pairs of the encode-order launches (64 positions x the block's groups, per sample),
  * [1][layer][group] cells the decode-order launches stored.  *skip_active_out (may be NULL): 0 the codec does not skip (generic kernels or
