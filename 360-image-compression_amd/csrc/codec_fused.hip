@@ -149,6 +149,13 @@ struct lic360_codec {
     // would have to wait for the whole importance map instead of running behind it).  LIC360_NOSKIP=1 (read at create) turns it off;
     // LIC360_DC_NOTALL=1 keeps the decode-order lists to images of at most 64 rows.
     bool skip = false;
+    // What keeps a skipped cell finite: every encode that skips clears the two ping-pong buffers that layers 1..10 write sparsely, for
+    // its 3 B samples, so a stale cell it reads is a zero or a value of THIS call -- at most 11 layers deep.  Without it a dead cell that a live
+    // task computes can read, in a tile that this call skips, what a LATER layer of the previous call left there, and the next call reads the
+    // result: a recurrence of about eight layers per call with the weights' gain (tests/skip_age_cases.py).  LIC360_NOCLEAR=1 (read at create)
+    // leaves the clear out, for A/B runs; lic360_codec_debug_fill suppresses it once, so that the next encode sees the fill.
+    bool clear = true, filled = false;
+    DevBuf<unsigned> dbg;                      // lic360_codec_debug_absmax's 15 maxima (float bits) and 15 counts
     DevBuf<signed char> need, need_d, tmax;
     lic360_ec_lists ecl;                       // views of ecl_list / ecl_cnt and dcl_list / dcl_cnt for the launchers
     lic360_dc_lists dcl;
@@ -961,6 +968,7 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     if (c->d_tab.alloc(2 * B * (size_t)c->tab_pitch)) return 1;                 // two uint4 per symbol (dec_pack8)
     if (const char *hc = getenv("LIC360_HOST_CODER")) c->coder_mode = hc[0] == '0' ? 0 : (hc[0] == '1' ? 1 : 2);
     c->skip = c->use4 && !getenv("LIC360_NOSKIP");
+    c->clear = !getenv("LIC360_NOCLEAR");
     if (c->skip) {
         const size_t S = c->S, nt = (size_t)((h + 3) / 4) * ((w + 15) / 16);
         if (c->need.alloc(B * NEED_LAYERS * HW) || c->need_d.alloc(B * NEED_LAYERS * S * h) || c->tmax.alloc(B * NEED_LAYERS * nt) ||
@@ -1037,6 +1045,13 @@ LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *c
     hipLaunchKernelGGL(k_enc_prep, dim3(lic360_blocks(total, 4)), dim3(256), 0, s, code, mask, c->e_x0, total, H, W, c->e_hp, c->e_wp, c->e_off);
     LAUNCH_CHECK();
     if (c->skip) {                                                      // need maps of this batch's masks, the live tasks of layers 1..11
+        // layers 1..10 leave the cells of skipped tasks as they are: zeros, then, not what an earlier call left there (a fill of the test hook stays, once)
+        if (c->clear && !c->filled) {
+            const size_t bytes = (size_t)3 * B * 4 * G * c->e_hp * c->e_wp * sizeof(float);
+            HIP_TRY(hipMemsetAsync(c->e_buf[1], 0, bytes, s));
+            HIP_TRY(hipMemsetAsync(c->e_buf[2], 0, bytes, s));
+        }
+        c->filled = false;
         if (lic360_need_build(stream, mask, B, G, H, W, c->need, c->need_d, c->tmax)) return 1;
         if (lic360_ec_lists_build(stream, c->tmax, B, G, H, W, c->ecl, c->stats_on ? c->stats : nullptr)) return 1;
     }
@@ -1743,6 +1758,56 @@ LIC360_API int lic360_codec_debug_fill(void *stream, lic360_codec *c, float valu
     }
     hipLaunchKernelGGL(k_fill_dec, dim3(lic360_blocks(3 * B * 3 * G * c->HW, 4)), dim3(256), 0, s, c->d_y, 3 * B * 3 * G, c->H, c->W, c->sk, value);
     LAUNCH_CHECK();
+    c->filled = true;                                                   // the next encode keeps the fill: it does not clear its two buffers
+    return 0;
+}
+// Test hook: the largest |v| among the finite interior cells of every activation buffer and the number of Inf / NaN cells (the cells debug_fill fills;
+// out[0..15): maxima as float bits -- non-negative floats order as their bits do --, out[15..30): counts).  A grid-stride pass, one pair of atomics per thread.
+__device__ __forceinline__ void absmax_take(float v, unsigned &m, unsigned &bad) {
+    const unsigned a = __float_as_uint(v) & 0x7fffffffu;
+    if (a >= 0x7f800000u) ++bad;
+    else m = a > m ? a : m;
+}
+__device__ __forceinline__ void absmax_put(unsigned *out, int slot, unsigned m, unsigned bad) {
+    if (m) atomicMax(out + slot, m);
+    if (bad) atomicAdd(out + 15 + slot, bad);
+}
+__global__ void k_absmax_enc(const float *buf, long planes, int H, int W, int hp, int wp, int off, unsigned *out, int slot) {
+    unsigned m = 0, bad = 0;
+    GRID_STRIDE(i, planes * H * W) {
+        const int x = (int)(i % W), y = (int)((i / W) % H);
+        absmax_take(buf[(i / ((long)H * W)) * hp * wp + e_cell(y, x, wp, off)], m, bad);
+    }
+    absmax_put(out, slot, m, bad);
+}
+__global__ void k_absmax_dec(const float *buf, long planes, int H, int W, DcLayout sk, unsigned *out, int slot) {
+    unsigned m = 0, bad = 0;
+    GRID_STRIDE(i, planes * H * W) {
+        const int x = (int)(i % W), y = (int)((i / W) % H);
+        absmax_take(buf[(i / ((long)H * W)) * sk.plane() + sk.cell(y, x)], m, bad);
+    }
+    absmax_put(out, slot, m, bad);
+}
+LIC360_API int lic360_codec_debug_absmax(void *stream, lic360_codec *c, float *absmax, int *nonfinite) {
+    ARG_CHECK(c && absmax && nonfinite);
+    hipStream_t s = (hipStream_t)stream;
+    const long B = c->maxB, G = c->G;
+    if (!c->dbg && c->dbg.alloc(30)) return 1;
+    HIP_TRY(hipMemsetAsync(c->dbg, 0, 30 * sizeof(unsigned), s));
+    for (int i = 0; i < 3; ++i) {
+        hipLaunchKernelGGL(k_absmax_enc, dim3(lic360_blocks(3 * B * 4 * G * c->HW, 4)), dim3(256), 0, s, c->e_buf[i], 3 * B * 4 * G, c->H, c->W, c->e_hp, c->e_wp, c->e_off, c->dbg, i);
+        LAUNCH_CHECK();
+    }
+    for (int i = 0; i < 11; ++i) {
+        hipLaunchKernelGGL(k_absmax_dec, dim3(lic360_blocks(3 * B * 4 * G * c->HW, 4)), dim3(256), 0, s, c->d_act[i], 3 * B * 4 * G, c->H, c->W, c->sk, c->dbg, 3 + i);
+        LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_absmax_dec, dim3(lic360_blocks(3 * B * 3 * G * c->HW, 4)), dim3(256), 0, s, c->d_y, 3 * B * 3 * G, c->H, c->W, c->sk, c->dbg, 14);
+    LAUNCH_CHECK();
+    unsigned host[30];
+    HIP_TRY(hipMemcpyAsync(host, c->dbg, sizeof(host), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < 15; ++i) { memcpy(absmax + i, host + i, sizeof(float)); nonfinite[i] = (int)host[15 + i]; }
     return 0;
 }
 // Test hook: what the last encode / decode of the codec scheduled, copied to the host.  which 0: need maps [maxB][12][H][W] int8; 1: encode list counts

@@ -9,7 +9,9 @@
 //   need_l(q)   = min(G - 1, max over p in q + [-2, 2]^2 of need_{l+1}(p) + (p_y - q_y) + (p_x - q_x))   (need_{l+1}(p) >= 0 only; < 0: -1)
 // i.e. "plane of the last consumer" t = need + y + x is dilated 5 x 5 per layer.  The reference computes the dead cells too; skipping them
 // changes no bitstream and no decoded symbol (they are only read by chains whose own outputs are dead, or with zero weights: the cells
-// hold finite values -- outputs of earlier passes -- and fma(0, finite, acc) == acc).
+// hold finite values and fma(0, finite, acc) == acc.  Finite because a cell is never more than 12 layers away from real symbols: the decode order
+// has one buffer per layer, the encode order clears its two sparsely written ping-pong buffers at the start of every call -- DESIGN 4.6,
+// tests/skip_age_cases.py).
 #pragma once
 #include <cstdint>
 

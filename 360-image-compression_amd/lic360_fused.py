@@ -166,6 +166,16 @@ class FusedCodec(_FusedBase):
     def debug_fill(self, value):
         _chk(_lib.lic360_codec_debug_fill(_stream(self.device), self._h, C.c_float(float(value))))
 
+    ABSMAX_BUFFERS = ["e_buf%d" % i for i in range(3)] + ["d_act%d" % i for i in range(11)] + ["d_y"]
+
+    def debug_absmax(self):
+        """-> (absmax float32 [15], nonfinite int32 [15]) in the order of ABSMAX_BUFFERS: the largest |v| among the finite interior cells of every
+        activation buffer and the number of its Inf / NaN cells, once the stream's work is done"""
+        import numpy as np
+        absmax, bad = np.zeros(15, np.float32), np.zeros(15, np.int32)
+        _chk(_lib.lic360_codec_debug_absmax(_stream(self.device), self._h, absmax.ctypes.data_as(C.c_void_p), bad.ctypes.data_as(C.c_void_p)))
+        return absmax, bad
+
     def debug_lists(self, which):
         """what the last encode / decode scheduled (which: see lic360_codec_debug_lists) as a flat numpy array + the list capacity"""
         import numpy as np

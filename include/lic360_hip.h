@@ -517,6 +517,10 @@ int lic360_codec_skip_stats(lic360_codec *codec, int enable, unsigned long long 
  * (which 0: need maps, 1 / 2: encode-order list counts / entries, 3 / 4: decode-order list counts / records; see csrc/codec_fused.hip) */
 int lic360_codec_debug_fill(void *stream, lic360_codec *codec, float value);
 int lic360_codec_debug_lists(lic360_codec *codec, int which, void *host_out, long bytes, int *cap_out);
+/* test hook: what the codec's activation buffers hold once the stream's work is done, over the interior cells that lic360_codec_debug_fill fills.  15 values
+ * each (host), in the order e_buf[0..2] (encode order's ping-pong buffers), d_act[0..10] (decode order's layers), d_y: absmax = the largest |v| among the
+ * finite cells, nonfinite = the number of Inf / NaN cells.  tests/test_gpu_skip_age.py: a skipped cell must stay bounded across calls. */
+int lic360_codec_debug_absmax(void *stream, lic360_codec *codec, float *absmax, int *nonfinite);
 
 /* calibration for bench.py (no reference counterpart): the fp32 MFMA rate (v_mfma_f32_16x16x4_f32, 8 waves per CU) this device sustains right now, in
  * TFLOP/s, and its compute-unit count; ~50 ms.  bench.py prints it beside the headline so that figures of different boxes of a pool can be normalised. */
