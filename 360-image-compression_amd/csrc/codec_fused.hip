@@ -15,6 +15,7 @@
 #include "lic360_exact_math.h"
 #include "gmm_tables.h"
 #include "need.h"
+#include "rate.h"
 #include <vector>
 #include <cstring>
 #include <algorithm>
@@ -139,6 +140,9 @@ struct lic360_codec {
     DevBuf<int> d_idx, d_pidx, d_plane_start;
     DevBuf<float> e_x0, e_buf[3];
     DevBuf<uint2> e_rec;
+    int rec_B = 0;                             // images whose records the most recent encode / estimate left in e_rec (0: none since create)
+    DevBuf<unsigned long long> rate_tab;       // rate estimation (csrc/rate_kernels.hip): the cost table and the (group, row) bins of every coding position
+    DevBuf<unsigned> rate_bkt;
     DevBuf<float> d_x0, d_act[11], d_y;
     DevBuf<AcDevState> d_state;
     DevBuf<uint4> d_tab;                       // per-plane CDF tables [maxB][tab_pitch][2] (k_dec_tables -> k_dec_plane)
@@ -950,6 +954,7 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     if (acc != ngroup * c->HW) { lic360_set_error("internal: plane schedule does not cover the latent"); return 1; }
     if (c->d_plane_start.alloc(c->h_plane_start.size())) return 1;
     HIP_TRY(hipMemcpy(c->d_plane_start, c->h_plane_start.data(), c->h_plane_start.size() * 4, hipMemcpyHostToDevice));
+    if (lic360_rate_table_upload(c->rate_tab) || lic360_rate_buckets_upload(ngroup, h, w, c->h_pidx.data(), c->h_plane_start.data(), c->rate_bkt)) return 1;
     c->sk = DcLayout::plain(h, w);
     if (c->use4 && lic360_dc4_layout(h, w, &c->sk.rows, &c->sk.pitch, &c->sk.row0, &c->sk.col0)) return 1;
     const size_t B = max_batch, G = ngroup, HW = c->HW, SK = (size_t)c->sk.plane(), TAIL = (size_t)lic360_conv4_buffer_floats(0, 1, h, w) - SK;   // slack for the band fetches of the last plane
@@ -1034,12 +1039,11 @@ LIC360_API int lic360_codec_set_coder(lic360_codec *c, int mode) {
     return 0;
 }
 
-LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *code, const float *mask, int B,
-                                   uint8_t *bytes, long cap, int *nbytes, int *err) {
-    if (check_ready(c, B)) return 2;
-    ARG_CHECK(code && mask && nbytes && err);
-    if (check_slot(bytes, cap)) return 2;
+// What an encode and a rate estimate share, everything up to and including the records: prep, need maps and lists under the skip, the twelve layers,
+// the fused or separate table kernel.  e_rec then holds B images of G * H * W records in coding order.
+static int codec_records(void *stream, lic360_codec *c, const float *code, const float *mask, int B) {
     hipStream_t s = (hipStream_t)stream;
+    c->rec_B = 0;
     const int G = c->G, H = c->H, W = c->W;
     const long total = (long)B * G * c->HW;
     hipLaunchKernelGGL(k_enc_prep, dim3(lic360_blocks(total, 4)), dim3(256), 0, s, code, mask, c->e_x0, total, H, W, c->e_hp, c->e_wp, c->e_off);
@@ -1085,6 +1089,18 @@ LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *c
                                                        c->d_plane_start, c->e_rec, B, G, H, W, c->e_hp, c->e_wp, c->e_off));
         LAUNCH_CHECK();
     }
+    c->rec_B = B;
+    return 0;
+}
+
+LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *code, const float *mask, int B,
+                                   uint8_t *bytes, long cap, int *nbytes, int *err) {
+    if (check_ready(c, B)) return 2;
+    ARG_CHECK(code && mask && nbytes && err);
+    if (check_slot(bytes, cap)) return 2;
+    hipStream_t s = (hipStream_t)stream;
+    const int G = c->G;
+    if (const int rc = codec_records(stream, c, code, mask, B)) return rc;
     // the serial coder: host threads, or one wave per image
     if (coder_on_host(c, B)) {
         int rc = 0;
@@ -1094,6 +1110,25 @@ LIC360_API int lic360_codec_encode(void *stream, lic360_codec *c, const float *c
     PROF(c, PROF_AC_ENCODE, s, hipLaunchKernelGGL(k_ac_encode, dim3(B), dim3(128), 0, s, c->e_rec, (long)G * c->HW, bytes, cap, nbytes, err));
     LAUNCH_CHECK();
     return 0;
+}
+
+// The rate of a batch without its bitstreams: the records as an encode leaves them, then their integer code length (csrc/rate_kernels.hip) instead
+// of the coder -- no D2H copy, no host threads, whatever the coder mode.
+static int codec_rate(void *stream, lic360_codec *c, int B, unsigned long long *bits_q32, unsigned long long *nsym, unsigned long long *group_q32,
+                      unsigned long long *row_q32) {
+    return lic360_rate_sum((hipStream_t)stream, c->e_rec, c->rate_bkt, c->rate_tab, (long)c->G * c->HW, B, c->G, c->H, bits_q32, nsym, group_q32, row_q32);
+}
+LIC360_API int lic360_codec_estimate(void *stream, lic360_codec *c, const float *code, const float *mask, int B, unsigned long long *bits_q32,
+                                     unsigned long long *nsym, unsigned long long *group_q32, unsigned long long *row_q32) {
+    if (check_ready(c, B)) return 2;
+    ARG_CHECK(code && mask && bits_q32 && nsym);
+    if (const int rc = codec_records(stream, c, code, mask, B)) return rc;
+    return codec_rate(stream, c, B, bits_q32, nsym, group_q32, row_q32);
+}
+LIC360_API int lic360_codec_rate_last(void *stream, lic360_codec *c, int B, unsigned long long *bits_q32, unsigned long long *nsym,
+                                      unsigned long long *group_q32, unsigned long long *row_q32) {
+    ARG_CHECK(c && bits_q32 && nsym && B > 0 && B <= c->rec_B);        // (rec_B: 0 until an encode or an estimate has left records)
+    return codec_rate(stream, c, B, bits_q32, nsym, group_q32, row_q32);
 }
 
 // the checks a latent decode starts with (lic360_codec_decode_gated runs them before it consumes its ticket)
@@ -1224,6 +1259,9 @@ struct lic360_impcodec {
     DevBuf<int> d_idx, d_pidx;
     DevBuf<float> e_x0, e_buf[3];
     DevBuf<uint2> e_rec;
+    int rec_B = 0;                              // as in lic360_codec: the images of the most recent encode / estimate, the cost table, the row bins
+    DevBuf<unsigned long long> rate_tab;
+    DevBuf<unsigned> rate_bkt;
     DevBuf<float> d_x0, d_act[11], d_y;
     // leaf-resident 16x16x4 kernels for the 144-channel layers (csrc/cconv144_kernels.hip): encode on zero-haloed NCHW planes,
     // decode on zero-padded diagonal-major planes (sk)
@@ -1401,6 +1439,7 @@ LIC360_API int lic360_impcodec_create(int h, int w, int hidden_channels, int nsy
     if (c->e_x0.alloc(B * HW)) return 1;
     for (DevBuf<float> &b : c->e_buf) if (b.alloc(B * CE * HW)) return 1;
     if (c->e_rec.alloc(B * HW)) return 1;
+    if (lic360_rate_table_upload(c->rate_tab) || lic360_rate_buckets_upload(1, h, w, c->h_pidx.data(), nullptr, c->rate_bkt)) return 1;
     // 144-channel layers on the leaf-resident 16x16x4 kernels (other widths keep the generic kernels)
     c->use144 = lic360_conv144_supported(c->w.plan[1].get()) && lic360_conv144_supported(c->w.plan[2].get());
     c->sk = DcLayout::plain(h, w);
@@ -1428,11 +1467,10 @@ LIC360_API int lic360_impcodec_set_layer(void *stream, lic360_impcodec *c, int l
     return c->w.set(stream, layer, weight, bias, act, [&](const lic360_conv_plan *p, int k) { return x144 && k == 0 ? lic360_conv144_packed_floats(p) : 0; },
                     [&](lic360_conv_plan *p) { return x144 && lic360_conv144_pack(stream, p, weight, c->w.xpack[0][layer]); });
 }
-LIC360_API int lic360_impcodec_encode(void *stream, lic360_impcodec *c, const float *levels, int B, uint8_t *bytes, long cap, int *nbytes, int *err) {
-    if (check_ready(c, B)) return 2;
-    ARG_CHECK(levels && nbytes && err);
-    if (check_slot(bytes, cap)) return 2;
+// what an encode and a rate estimate of the maps share: prep, the twelve layers, the table kernel; e_rec then holds B maps of H * W records
+static int impcodec_records(void *stream, lic360_impcodec *c, const float *levels, int B) {
     hipStream_t s = (hipStream_t)stream;
+    c->rec_B = 0;
     const int H = c->H, W = c->W;
     const long total = (long)B * c->HW;
     hipLaunchKernelGGL(k_imp_prep, dim3(lic360_blocks(total, 4)), dim3(256), 0, s, levels, c->e_x0, total, c->sc);
@@ -1457,9 +1495,31 @@ LIC360_API int lic360_impcodec_encode(void *stream, lic360_impcodec *c, const fl
         hipLaunchKernelGGL(k_imp_enc_tables<decltype(fast)::value>, dim3(lic360_blocks(total, 1)), dim3(64), 0, s, y, levels, c->d_pidx, c->e_rec, B, H, W, c->nsym);
     });
     LAUNCH_CHECK();
+    c->rec_B = B;
+    return 0;
+}
+LIC360_API int lic360_impcodec_encode(void *stream, lic360_impcodec *c, const float *levels, int B, uint8_t *bytes, long cap, int *nbytes, int *err) {
+    if (check_ready(c, B)) return 2;
+    ARG_CHECK(levels && nbytes && err);
+    if (check_slot(bytes, cap)) return 2;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = impcodec_records(stream, c, levels, B)) return rc;
     hipLaunchKernelGGL(k_ac_encode, dim3(B), dim3(128), 0, s, c->e_rec, (long)c->HW, bytes, cap, nbytes, err);
     LAUNCH_CHECK();
     return 0;
+}
+// the maps' rate: one group, so a row breakdown only
+LIC360_API int lic360_impcodec_estimate(void *stream, lic360_impcodec *c, const float *levels, int B, unsigned long long *bits_q32,
+                                        unsigned long long *nsym, unsigned long long *row_q32) {
+    if (check_ready(c, B)) return 2;
+    ARG_CHECK(levels && bits_q32 && nsym);
+    if (const int rc = impcodec_records(stream, c, levels, B)) return rc;
+    return lic360_rate_sum((hipStream_t)stream, c->e_rec, c->rate_bkt, c->rate_tab, (long)c->HW, B, 1, c->H, bits_q32, nsym, nullptr, row_q32);
+}
+LIC360_API int lic360_impcodec_rate_last(void *stream, lic360_impcodec *c, int B, unsigned long long *bits_q32, unsigned long long *nsym,
+                                         unsigned long long *row_q32) {
+    ARG_CHECK(c && bits_q32 && nsym && B > 0 && B <= c->rec_B);
+    return lic360_rate_sum((hipStream_t)stream, c->e_rec, c->rate_bkt, c->rate_tab, (long)c->HW, B, 1, c->H, bits_q32, nsym, nullptr, row_q32);
 }
 // mask_out cells of the map positions idx[start .. start+len): Dtow(stride)(Imp2mask(levels)) restricted to them --
 //   tmask(tc, th, tw) = tc < int(level + 1e-5) * cpn                                 (extension/imp2mask_cuda.cu:31)
@@ -1644,6 +1704,24 @@ LIC360_API int lic360_devcoder_encode(void *stream, const int *tables, int ncode
     }
     hipLaunchKernelGGL(k_ac_encode, dim3(1), dim3(128), 0, s, rec, n, bytes, cap, nbytes, err);
     LAUNCH_CHECK();
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+// The twin of lic360_devcoder_encode for the rate: the same record construction (k_test_records) for B images of n symbols each, then k_rate_sum
+// without a breakdown, so that frequencies the nets never produce (f = 1, f = 65536) reach the kernel.
+LIC360_API int lic360_rate_records(void *stream, const int *tables, int ncode, const int *labels, const float *mask, long n, int B,
+                                   unsigned long long *bits_q32, unsigned long long *nsym) {
+    ARG_CHECK(ncode >= 1 && n >= 0 && B > 0 && n < (1L << 40) / B && bits_q32 && nsym && (n == 0 || (tables && labels)));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf<uint2> rec;
+    DevBuf<unsigned long long> tab;
+    if (rec.alloc((size_t)n * B) || lic360_rate_table_upload(tab)) return 1;
+    if (n) {
+        hipLaunchKernelGGL(k_test_records, dim3(lic360_blocks(n * B, 1)), dim3(256), 0, s, tables, ncode, labels, mask, n * B, rec);
+        LAUNCH_CHECK();
+    }
+    if (lic360_rate_sum(s, rec, nullptr, tab, n, B, 0, 0, bits_q32, nsym, nullptr, nullptr)) return 1;
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }

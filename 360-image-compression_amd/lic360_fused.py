@@ -5,12 +5,19 @@ inputs, activations, CDF tables, coder state and bitstreams all stay in HBM; the
 kernels.  Bitstreams are byte-identical to the per-plane drivers in lic360_codec.py and to the oracle.
 torch is used for device buffers and streams only.
 """
+import collections
 import ctypes as C
 
 import torch
 
 import lic360
 from lic360 import _lib, _chk, _p, _stream, Lic360Error
+
+
+RateEstimate = collections.namedtuple("RateEstimate", "bits symbols group_bits row_bits q32")
+RateEstimate.__doc__ = """The ideal code length of a batch (include/lic360_hip.h, rate estimation): q32 int64 [b], exact, in units of 2^-32 bit;
+bits float64 [b] = q32 / 2^32; symbols int64 [b], the coded symbols; group_bits float64 [b, G] and row_bits float64 [b, H], the same bits by group
+and by latitude row (None unless asked for)."""
 
 
 def _net_modules(drv):
@@ -68,6 +75,22 @@ class _FusedBase(object):
         if int(self.err[:b].abs().sum().item()):
             raise Lic360Error("arithmetic decoder fault (corrupt stream?): %s" % self.err[:b].cpu().tolist())
         return out
+
+    def _rate(self, b, shapes, call):
+        """the outputs of a rate reduction of b images: q32 and symbols, then one int64 [b, n] (or None) per entry of `shapes`;
+        call(q32, symbols, *breakdowns) enqueues it -> RateEstimate of device tensors"""
+        dev = "cuda:%d" % self.device
+        q32, sym = (torch.empty((b,), dtype=torch.int64, device=dev) for _ in range(2))
+        parts = [None if n is None else torch.empty((b, n), dtype=torch.int64, device=dev) for n in shapes]
+        call(q32, sym, *parts)
+        scale = 1.0 / 4294967296.0
+        group, row = ([None] * (2 - len(parts)) + [None if p is None else p.double() * scale for p in parts])
+        return RateEstimate(q32.double() * scale, sym, group, row, q32)
+
+    @staticmethod
+    def _rate_cpu(r):
+        """a RateEstimate on the host, once the stream's work is done"""
+        return RateEstimate(*(None if t is None else t.cpu() for t in r))
 
 
 class FusedCodec(_FusedBase):
@@ -140,6 +163,24 @@ class FusedCodec(_FusedBase):
     def decode(self, streams, mask):
         b = self._stage_streams(streams)
         return self._decoded(self.decode_async(mask, b), b)
+
+    # ---- rate without the coder (csrc/rate_kernels.hip) ------------------------------------------------
+    def estimate_async(self, code, mask, groups=False, rows=False):
+        """Queue everything an encode does up to the per-symbol CDF records, then their exact code length instead of the coder: no
+        bitstream is written.  -> RateEstimate of device tensors (group_bits / row_bits only where asked for)."""
+        self._check(code, "code")
+        self._check(mask, "mask")
+        return self._rate(code.shape[0], (self.G if groups else None, self.H if rows else None), lambda q, n, g, r: _chk(
+            _lib.lic360_codec_estimate(_stream(self.device), self._h, _p(code), _p(mask), code.shape[0], _p(q), _p(n), _p(g), _p(r))))
+
+    def estimate(self, code, mask, groups=False, rows=False):
+        return self._rate_cpu(self.estimate_async(code, mask, groups, rows))
+
+    def rate_last(self, b, groups=False, rows=False):
+        """the RateEstimate (host) of the first b images of this codec's most recent encode or estimate, from the records it left on the
+        device: for callers who want the streams and the breakdown.  Raises unless that call held at least b images."""
+        return self._rate_cpu(self._rate(int(b), (self.G if groups else None, self.H if rows else None), lambda q, n, g, r: _chk(
+            _lib.lic360_codec_rate_last(_stream(self.device), self._h, int(b), _p(q), _p(n), _p(g), _p(r)))))
 
     def set_coder(self, mode):
         """where the serial coder phases run: "device" (one wave per image), "host" (one host thread per image, <= 64 images per call), "auto"
@@ -259,6 +300,19 @@ class FusedImpCodec(_FusedBase):
 
     def encode(self, levels):
         return self._read_streams(self.encode_async(levels))
+
+    def estimate_async(self, levels, rows=False):
+        """the maps' exact code length without the coder (FusedCodec.estimate_async; one group: group_bits is always None)"""
+        self._check(levels)
+        return self._rate(levels.shape[0], (self.H if rows else None,), lambda q, n, r: _chk(
+            _lib.lic360_impcodec_estimate(_stream(self.device), self._h, _p(levels), levels.shape[0], _p(q), _p(n), _p(r))))
+
+    def estimate(self, levels, rows=False):
+        return self._rate_cpu(self.estimate_async(levels, rows))
+
+    def rate_last(self, b, rows=False):
+        return self._rate_cpu(self._rate(int(b), (self.H if rows else None,), lambda q, n, r: _chk(
+            _lib.lic360_impcodec_rate_last(_stream(self.device), self._h, int(b), _p(q), _p(n), _p(r)))))
 
     def decode(self, streams):
         b = self._stage_streams(streams)

@@ -483,6 +483,33 @@ int lic360_devcoder_encode(void *stream, const int *tables, int ncode, const int
 int lic360_devcoder_decode(void *stream, const int *tables, int ncode, const float *mask, long n, int chunk,
                            const uint8_t *bytes, long cap, const int *nbytes, float *out, int *err);
 
+/* ---- rate estimation: the exact ideal code length of what the fused codecs would write, without running the coder (csrc/rate_kernels.hip; no
+ * reference counterpart -- the reference's evaluation loop, train/trainDDP_IMP_ENT.py:54-88, reports a float entropy estimate beside the real rate).
+ * Both codecs end their encode-order pass with one record (cdf[sym], cdf[sym + 1]) per symbol in coding order, (0, 0) for a symbol the coder skips.  A
+ * coded symbol of frequency f = hi - lo in [1, 65536] costs cost(f) = round(2^32 (16 - log2 f)) Q32 bits, an unsigned 64-bit integer (cost(2^k) =
+ * (16 - k) 2^32 exactly, cost(65536) = 0); a record with hi == lo costs 0 and is not counted.  An image's code length is the integer sum of its symbols'
+ * costs: independent of the reduction order, below 2^55 for 393 216 symbols, so every output fits int64.  All outputs are device memory, one unsigned
+ * 64-bit integer per entry, and are zeroed in the stream before the launch: bits_q32[b], nsym[b] (coded symbols), and where the pointer is not NULL
+ * group_q32[b][g], row_q32[b][h] -- the same bits by group and by latitude row of the latent (each sums to bits_q32[b]).
+ * lic360_rate_table: the 65 537 costs by f (entry 0 = 0), host memory, built in double precision; host-only, needs no GPU.
+ * lic360_rate_records: test hook, the twin of lic360_devcoder_encode -- raw tables [b n][ncode + 1], labels and an optional mask for b images of n
+ *   symbols through the same record construction, then the reduction without a breakdown; synchronises the stream before returning.
+ * lic360_codec_estimate / lic360_impcodec_estimate: everything lic360_codec_encode / lic360_impcodec_encode do up to and including the records, then the
+ *   reduction instead of the coder (no bitstream, no D2H copy, no host threads whatever the coder mode).  The maps have one group: a row breakdown only.
+ * lic360_codec_rate_last / lic360_impcodec_rate_last: the same reduction over the records the codec's most recent encode or estimate left, for callers
+ *   who want the streams and the breakdown; refused (argument error, no launch) unless that call held at least b images. */
+int lic360_rate_table(unsigned long long *out);
+int lic360_rate_records(void *stream, const int *tables, int ncode, const int *labels, const float *mask, long n, int b,
+                        unsigned long long *bits_q32, unsigned long long *nsym);
+int lic360_codec_estimate(void *stream, lic360_codec *codec, const float *code, const float *mask, int b, unsigned long long *bits_q32,
+                          unsigned long long *nsym, unsigned long long *group_q32, unsigned long long *row_q32);
+int lic360_codec_rate_last(void *stream, lic360_codec *codec, int b, unsigned long long *bits_q32, unsigned long long *nsym,
+                           unsigned long long *group_q32, unsigned long long *row_q32);
+int lic360_impcodec_estimate(void *stream, lic360_impcodec *codec, const float *levels, int b, unsigned long long *bits_q32,
+                             unsigned long long *nsym, unsigned long long *row_q32);
+int lic360_impcodec_rate_last(void *stream, lic360_impcodec *codec, int b, unsigned long long *bits_q32, unsigned long long *nsym,
+                              unsigned long long *row_q32);
+
 /* Where the serial arithmetic-coder phases of the fused latent codec run.  The reference runs its coder on the CPU (extension/coder.cpp:70-113, called per
  * plane from test/lic360_demo.py:139-140,234); the fused codec keeps it on the GPU (one wave per image) where many images per call hide it, and hands it
  * to host threads -- records D2H / per-plane tables through pinned memory, polled flags -- when a call holds few images.  mode 0: device, 1: host

@@ -38,6 +38,7 @@ def main():
     ap.add_argument("--gdn-precision", choices=("fp32", "bf16x3"), default="fp32", help="arithmetic of the transforms' one-pass GDNs (bf16x3: the split-bf16 form)")
     ap.add_argument("--gate", choices=("library", "fused"), default="library", help="tail of the attention blocks (fused: 1x1 convolution + sigmoid + product + sum in one launch)")
     ap.add_argument("--small", choices=("library", "narrow"), default="library", help="layers with too few workgroups for the wide kernels (narrow: on narrow workgroups, e.g. the 132 x 260 stage of one image)")
+    ap.add_argument("--rows", action="store_true", help="print the share of the estimated latent bits that every latitude row gets")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     import lic360_container as box
@@ -76,6 +77,8 @@ def main():
         streams, istreams = fc.encode(code.contiguous(), mask.contiguous()), ic.encode(levels.contiguous())
         torch.cuda.synchronize()
         t1 = time.time()
+        # the rate without the coder: the exact code length of the records those encodes left on the device, latent + importance map
+        est, iest = fc.rate_last(n, rows=args.rows), ic.rate_last(n)
         files = []
         for i in range(n):
             f = os.path.join(args.out, "img%03d.lic360" % i)
@@ -92,9 +95,12 @@ def main():
         vmse, vssim = vmse.mean(dim=1).tolist(), vssim.mean(dim=1).tolist()
     for i in range(n):
         mse = float(torch.mean((x[i] - rec[i]) ** 2))
-        print("%s  %.3f bpp  PSNR %.2f dB  viewport PSNR %.2f dB  viewport SSIM %.4f" % (
-            files[i], os.path.getsize(files[i]) * 8 / (512.0 * 1024.0), 10 * math.log10(1.0 / max(mse, 1e-12)), 10 * math.log10(1.0 / max(vmse[i], 1e-12)),
-            vssim[i]))
+        print("%s  %.3f bpp (estimated %.3f)  PSNR %.2f dB  viewport PSNR %.2f dB  viewport SSIM %.4f" % (
+            files[i], os.path.getsize(files[i]) * 8 / (512.0 * 1024.0), (float(est.bits[i]) + float(iest.bits[i])) / (512.0 * 1024.0),
+            10 * math.log10(1.0 / max(mse, 1e-12)), 10 * math.log10(1.0 / max(vmse[i], 1e-12)), vssim[i]))
+        if args.rows:
+            share = (est.row_bits[i] / max(float(est.bits[i]), 1.0) * 100.0).tolist()
+            print("    latent bits by latitude row, %% of %.0f: %s" % (float(est.bits[i]), " ".join("%.1f" % v for v in share)))
         np.save(os.path.join(args.out, "img%03d_decoded.npy" % i), (rec[i].permute(1, 2, 0).cpu().numpy() * 255).astype(np.uint8))
     print("encode %.1f ms, decode %.1f ms for %d image(s) (first call: includes library autotuning)" % ((t1 - t0) * 1e3, (t3 - t2) * 1e3, n))
 
