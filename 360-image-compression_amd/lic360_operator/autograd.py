@@ -2,6 +2,7 @@
 no-grad path for inference and one of these functions when a gradient is being recorded.  Buffer semantics are the native ops'
 (outputs and gradients are op-owned and reused by the next call of the same op), as with the reference's own wrappers."""
 import torch
+from torch.autograd.function import once_differentiable
 
 
 def _c(t):
@@ -86,3 +87,26 @@ class QuantFn(torch.autograd.Function):
         x, y = ctx.saved_tensors
         gx, gw, cnt = ctx.op.backward([_c(g) for g in grads], x, y)
         return gx, gw, cnt.clone().detach(), None, None
+
+
+class ViewportQualityFn(torch.autograd.Function):
+    """(a, b) -> (mse, ssim) [n, 14] of lic360.viewport_quality_coef, which keeps coefficient maps only for the sides that need a gradient;
+    backward: lic360.viewport_quality_backward from a, b and those maps (no projected view is written in either direction)"""
+    @staticmethod
+    def forward(ctx, a, b, op, taps):
+        import lic360
+        ctx.op, ctx.taps, ctx.need = op, taps, tuple(ctx.needs_input_grad[:2])
+        mse, ssim, coefs = lic360.viewport_quality_coef(op, a, b, taps, need_a=ctx.need[0], need_b=ctx.need[1])
+        ctx.kept = tuple(t is not None for t in coefs)
+        ctx.save_for_backward(a, b, *[t for t in coefs if t is not None])
+        return mse, ssim
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_mse, g_ssim):
+        import lic360
+        a, b, *maps = ctx.saved_tensors
+        maps = iter(maps)
+        coefs = tuple(next(maps) if kept else None for kept in ctx.kept)
+        ga, gb = lic360.viewport_quality_backward(ctx.op, a, b, ctx.taps, coefs, _c(g_mse), _c(g_ssim), need_a=ctx.need[0], need_b=ctx.need[1])
+        return ga, gb, None, None

@@ -212,15 +212,27 @@ class ViewportQuality(nn.Module):
     per-cell SSIM [14*n, c, h, w], viewport-major.  Anything else -- CPU tensors, other dtypes, strided tensors, a pass that records
     gradients -- goes through MultiProject + SSIM + torch.mean and is reduced per (image, viewport) there: the module takes tensors of any
     placement and dtype, but the projection is native in both paths, so a HIP device is needed either way (CPU tensors are projected on
-    `device_id` and the results come back to the CPU)."""
+    `device_id` and the results come back to the CPU).
+    grad: where a pass that records gradients goes.  "library" (the default): the library path above, as before.  "fused" (opt-in): fp32
+    contiguous device tensors without return_map take autograd.ViewportQualityFn -- the fused forward that also keeps four coefficient maps, and
+    one fused backward kernel (lic360.viewport_quality_coef / viewport_quality_backward); everything else still takes the library path.  The
+    attribute can be switched between calls."""
+    GRAD_MODES = ("library", "fused")
 
-    def __init__(self, h, w, fov=0.5, near=False, device_id=0, window_size=11):
+    def __init__(self, h, w, fov=0.5, near=False, device_id=0, window_size=11, grad="library"):
         super().__init__()
+        self.grad = self._grad_mode(grad)
         self.project = MultiProject(h, w, fov, near, device_id)
         self.window_size = int(window_size)
         self.ssim = SSIM(self.window_size, 3)
         self.taps = _gauss_taps(self.window_size).tolist()
         self.device_id = device_id if isinstance(device_id, int) else list(device_id)[0]
+
+    @classmethod
+    def _grad_mode(cls, mode):
+        if mode not in cls.GRAD_MODES:
+            raise ValueError("ViewportQuality: grad must be one of %s, got %r" % (", ".join(repr(m) for m in cls.GRAD_MODES), mode))
+        return mode
 
     def _views(self, t, dev):
         """the op owns its output -- the next call rewrites it (the caller clones) -- and a recorded pass leaves its graph node on that tensor"""
@@ -231,9 +243,13 @@ class ViewportQuality(nn.Module):
         if a.shape != b.shape or a.dim() != 4:
             raise ValueError("ViewportQuality takes two [n, c, h, w] tensors of one shape")
         import lic360
-        fused = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and not self.project._recording(t) for t in (a, b))
-        if fused and a.device == b.device and a.device.index in self.project.op:
+        native = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (a, b)) and a.device == b.device and a.device.index in self.project.op
+        recording = self.project._recording(a, b)
+        if native and not recording:
             return lic360.viewport_quality(self.project.op[a.device.index], a, b, self.taps, return_map=return_map)
+        if native and not return_map and self._grad_mode(getattr(self, "grad", "library")) == "fused":
+            from .autograd import ViewportQualityFn
+            return ViewportQualityFn.apply(a, b, self.project.op[a.device.index], self.taps)
         dev = a.device if a.is_cuda and a.device.index in self.project.op else torch.device("cuda:%d" % self.device_id)
         n = a.shape[0]
         va, vb = self._views(a, dev).clone(), self._views(b, dev)                               # [14 n, c, h, w], viewport-major

@@ -319,6 +319,23 @@ int lic360_projects_backward(void *stream, const float *top_diff, const float *t
 long lic360_viewport_quality_scratch_bytes(int n, int h_out, int w_out);
 int lic360_viewport_quality(void *stream, const float *a, const float *b, const float *tf, int n, int c, int h, int w, int h_out, int w_out,
                             int nearest, const float *taps, int window, void *scratch, float *mse, float *ssim, float *ssim_map);
+/* The differentiable form of the fused viewport metrics, in two launches.  lic360_viewport_quality_coef: the arguments, checks and mse / ssim (bit
+ * for bit) of lic360_viewport_quality without the map; it also stores, per view cell, the derivatives of the cell's SSIM with respect to its five
+ * window sums: coef_q (E_aa and E_bb), coef_r (E_ab), coef_pa (mu_a), coef_pb (mu_b), each [14][n][c][h_out][w_out] fp32.  coef_q and coef_r are
+ * required, and at least one of coef_pa / coef_pb (the sides that will be differentiated); all buffers must be disjoint.
+ * lic360_viewport_quality_backward: from a, b, tf, taps of that call, its maps and the upstream gradients grad_mse, grad_ssim [n][14] (device), the
+ * gradients grad_a / grad_b [n][c][h][w] of the ERP batches.  At least one of grad_a / grad_b; coef_pa is required exactly when grad_a is given,
+ * coef_pb when grad_b is.  The entry zeroes grad_a / grad_b in the stream, then adds with float atomics (their last bits can differ from run to
+ * run).  grad_views_a / grad_views_b: NULL, or [14][n][c][h_out][w_out] for the gradients of the projected views before the scatter (a side's
+ * views need that side's grad; these are bit-reproducible).  Nothing written may overlap anything read or written.
+ * Both refuse (2) before anything is launched, and both trust tf as lic360_viewport_quality does. */
+int lic360_viewport_quality_coef(void *stream, const float *a, const float *b, const float *tf, int n, int c, int h, int w, int h_out, int w_out,
+                                 int nearest, const float *taps, int window, void *scratch, float *mse, float *ssim, float *coef_pa,
+                                 float *coef_pb, float *coef_q, float *coef_r);
+int lic360_viewport_quality_backward(void *stream, const float *a, const float *b, const float *tf, int n, int c, int h, int w, int h_out,
+                                     int w_out, int nearest, const float *taps, int window, const float *coef_pa, const float *coef_pb,
+                                     const float *coef_q, const float *coef_r, const float *grad_mse, const float *grad_ssim, float *grad_a,
+                                     float *grad_b, float *grad_views_a, float *grad_views_b);
 
 /* CppOp: ERP -> Craster parabolic projection.  lic360_cpp_rows fills the per-row column window ws [h][2] = (first column, count) and the
  * row angle theta [h] (host computes, device write); lic360_cpp_forward resamples x [nc][h][w] row by row, zero outside the window; mask
