@@ -801,6 +801,23 @@ static void hl_encode_all(void *ud) {                                   // (a st
     for (std::thread &t : th) t.join();
     delete j;
 }
+// The streams of an encode, from the pinned slots (pitch hcap) to the caller's (pitch cap): bytes [0, min(len, cap)) of every stream, its length
+// and its error word, and nothing else -- what the caller's slot holds past the stream stays as it was, as under k_ac_encode (copying whole slots
+// replaced it with whatever an earlier encode had left in the pinned ones).  HL_PUT_WG workgroups per image (every load is a read of host memory:
+// a stream's loads are all in flight at once instead of one after the other); the slots are 4-byte aligned on both sides, no more.
+#define HL_PUT_WG 32
+__global__ __launch_bounds__(256) void k_hl_put_streams(const uint8_t *__restrict__ bytes_h, long hcap, const int *__restrict__ nbytes_h,
+                                                        const int *__restrict__ err_h, uint8_t *__restrict__ bytes, long cap,
+                                                        int *__restrict__ nbytes, int *__restrict__ err) {
+    const int b = blockIdx.x, t = blockIdx.y * 256 + threadIdx.x;
+    const int len = nbytes_h[b];
+    const long w = len < 0 ? 0 : ((long)len < cap ? (long)len : cap);
+    const uint8_t *src = bytes_h + (long)b * hcap;
+    uint8_t *dst = bytes + (long)b * cap;
+    for (long i = t; i < w / 4; i += HL_PUT_WG * 256) ((uint32_t *)dst)[i] = ((const uint32_t *)src)[i];
+    if (t < w % 4) dst[w / 4 * 4 + t] = src[w / 4 * 4 + t];
+    if (t == 0) { nbytes[b] = len; err[b] = err_h[b]; }
+}
 static int hl_encode(lic360_codec *c, hipStream_t s, int B, uint8_t *bytes, long cap, int *nbytes, int *err) {
     HostLeg *h;
     if (hl_get(c, B, cap, &h)) return 1;
@@ -809,9 +826,8 @@ static int hl_encode(lic360_codec *c, hipStream_t s, int B, uint8_t *bytes, long
     std::unique_ptr<HlEncJob> job(new HlEncJob{h, B, n, cap});
     HIP_TRY(hipLaunchHostFunc(s, hl_encode_all, job.get()));
     job.release();                                                      // (hl_encode_all deletes it)
-    HIP_TRY(hipMemcpy2DAsync(bytes, (size_t)cap, h->bytes_h, (size_t)h->cap, (size_t)cap, (size_t)B, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(nbytes, h->nbytes_h, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(err, h->err_h, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_hl_put_streams, dim3(B, HL_PUT_WG), dim3(256), 0, s, h->bytes_h, h->cap, h->nbytes_h, h->err_h, bytes, cap, nbytes, err);
+    LAUNCH_CHECK();
     return 0;
 }
 

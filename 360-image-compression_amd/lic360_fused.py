@@ -98,8 +98,9 @@ class FusedCodec(_FusedBase):
 
     def __init__(self, ngroup, h, w, max_batch, device=0, cap_bytes=None):
         self.G, self.H, self.W, self.maxB, self.device = int(ngroup), int(h), int(w), int(max_batch), int(device)
-        # worst case of this coder is < 2.1 bytes/symbol (16-bit CDF, frequency >= 1); 1 byte/symbol is ample for
-        # any real table and overflow is reported through err[] rather than written out of bounds
+        # worst case of this coder is < 2.1 bytes/symbol (16-bit CDF, frequency >= 1; measured on the CPU oracle: 4000 frequency-1
+        # symbols -> 8001 bytes = 2.00025 bytes/symbol, tests/slot_cases.py); 1 byte/symbol is ample for any real table and overflow
+        # is reported through err[] (bit 16, nbytes = the true length) rather than written out of bounds
         dev = self._open(_lib.lic360_codec_create, (self.G, self.H, self.W, self.maxB), cap_bytes or max(4096, self.G * self.H * self.W))
         self.code_out = torch.zeros((self.maxB, self.G, self.H, self.W), dtype=torch.float32, device=dev)
 
