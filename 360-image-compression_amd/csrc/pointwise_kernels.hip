@@ -251,6 +251,9 @@ LIC360_API int lic360_sphere_cut_edge(void *stream, const float *x, float *out, 
 }
 // ---- training-side gradients of the sphere ops.  One output element per thread; the reference's order of additions.
 // STRIDED: the interior of a padded tensor (in-place form), pitch = w + 2 pad
+// DOMAIN: 2 * pad <= H and 2 * pad <= W (both entry points check it).  The rule gives an interior cell at most one wrap column, one
+// pole row and one corner; once 2 * pad > H a row is the source of a top AND a bottom apron row (columns likewise once 2 * pad > W) and
+// the rule, the reference's, drops one of them: it is no longer the adjoint of the forward.  The forward itself goes up to pad <= min(H, W).
 template <bool INPLACE>
 __global__ void k_sphere_pad_backward(float *__restrict__ in_diff, const float *top_diff, long total, int H, int W, int pad) {
     const int Ho = H + 2 * pad, Wo = W + 2 * pad;
@@ -279,14 +282,14 @@ __global__ void k_sphere_pad_backward(float *__restrict__ in_diff, const float *
     }
 }
 LIC360_API int lic360_sphere_pad_backward(void *stream, float *in_diff, const float *top_diff, int nc, int h, int w, int pad) {
-    ARG_CHECK(in_diff && top_diff && nc > 0 && pad >= 0 && h >= pad && w >= pad && h > 0 && w > 0);
+    ARG_CHECK(in_diff && top_diff && nc > 0 && pad >= 0 && h >= 2 * pad && w >= 2 * pad && h > 0 && w > 0);
     const long total = (long)nc * h * w;
     hipLaunchKernelGGL(k_sphere_pad_backward<false>, dim3(lic360_blocks(total, 4)), dim3(256), 0, (hipStream_t)stream, in_diff, top_diff, total, h, w, pad);
     LAUNCH_CHECK();
     return 0;
 }
 LIC360_API int lic360_sphere_pad_backward_inplace(void *stream, float *diff, int nc, int hp, int wp, int pad) {
-    ARG_CHECK(diff && nc > 0 && pad >= 0 && hp > 2 * pad && wp > 2 * pad && hp - 2 * pad >= pad && wp - 2 * pad >= pad);
+    ARG_CHECK(diff && nc > 0 && pad >= 0 && hp > 2 * pad && wp > 2 * pad && hp - 2 * pad >= 2 * pad && wp - 2 * pad >= 2 * pad);
     const int h = hp - 2 * pad, w = wp - 2 * pad;
     const long total = (long)nc * h * w;
     hipLaunchKernelGGL(k_sphere_pad_backward<true>, dim3(lic360_blocks(total, 4)), dim3(256), 0, (hipStream_t)stream, diff, diff, total, h, w, pad);

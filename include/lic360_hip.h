@@ -38,7 +38,8 @@ int lic360_sphere_trim(void *stream, float *x, int nc, int h, int w, int pad);
 /* SphereCutEdgeOp.forward                    extension/sphere_cut_edge_cuda.cu:43-62 */
 int lic360_sphere_cut_edge(void *stream, const float *x, float *out, int nc, int h, int w, int pad);
 /* SpherePadOp.backward: gradient of the un-padded tensor [nc][h][w] from top_diff [nc][h+2p][w+2p]: own cell + wrap column + mirrored pole
- * row + pole corner, added in that order     extension/sphere_pad_cuda.cu:107-136,181-198 */
+ * row + pole corner, added in that order     extension/sphere_pad_cuda.cu:107-136,181-198
+ * Both backward forms need 2 * pad <= h and 2 * pad <= w (that rule is the adjoint of the pad only there) and fail otherwise. */
 int lic360_sphere_pad_backward(void *stream, float *in_diff, const float *top_diff, int nc, int h, int w, int pad);
 /* SpherePadOp.backward, inplace=true: interior cells of diff [nc][hp][wp] accumulate their apron copies, the apron stays
  *                                            extension/sphere_pad_cuda.cu:138-180 */

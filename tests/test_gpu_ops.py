@@ -453,6 +453,10 @@ def test_linear_ops_backward_is_the_adjoint(lic):
     x = rnd(2, 8, 6, 10)
     p = lic.SpherePadOp(2, False, 0, False)
     adjoint(lambda t: p.forward(t)[0].clone(), lambda g: p.backward(g)[0], x, None)
+    p3 = lic.SpherePadOp(3, False, 0, False)                               # 2 * pad == h: the last size at which the backward's rule is the adjoint
+    adjoint(lambda t: p3.forward(t)[0].clone(), lambda g: p3.backward(g)[0], x, None)
+    with pytest.raises(lic.Lic360Error):                                   # one step beyond it the entry point refuses (the forward does not)
+        p3.backward(p3.forward(rnd(1, 2, 5, 10))[0])
     tr = lic.SphereTrimOp(2, 0, False)
     adjoint(lambda t: tr.forward(t.clone())[0], lambda g: tr.backward(g.clone())[0], rnd(2, 8, 10, 14), None)
     ce = lic.SphereCutEdgeOp(1, 0, False)
