@@ -22,7 +22,9 @@ precision after the predicates' fallback, the wide launch's count and fill rule,
 the answer into the `lic360` call (`_names`: the one place where a function's name is put together).
 The first stage's stride-2 layers (3 input channels: no 16-channel chunk, and bound by their output, not by MFMAs), convolutions off the fused
 shapes, small maps and every recording (training) pass are library work (torch -> MIOpen); native around them:
-sphere pad / trim / cut-edge / pixel-shuffle / importance map / quantiser kernels and the one-pass GDN (csrc/gdn_kernels.hip)."""
+sphere pad / trim / cut-edge / pixel-shuffle / importance map / quantiser kernels and the one-pass GDN (csrc/gdn_kernels.hip).
+EntropyNet2 is the reference's training-time entropy model of the latent (train/EntropyNet2.py:8-74) on MaskConv2, DropGrad and GmmRateLoss: its
+`rate(x, mask)` is the rate term of the training loss, on the fused GMM rate loss with head="fused"."""
 import collections
 import functools
 import types
@@ -525,6 +527,51 @@ class CMP_Decoder(nn.Module):
 
     def forward(self, code, mask):
         return self.decoder(self.quant(self.dtw1(code), self.dtw2(mask)))
+
+
+class EntropyResidualBlock(nn.Module):
+    """two hidden group-causal 5x5 convolutions with PReLU around a skip (train/EntropyNet2.py:8-21)"""
+    def __init__(self, ngroups, cpn, device_id=0):
+        super().__init__()
+        from lic360_operator import MaskConv2
+        self.net = nn.Sequential(MaskConv2(ngroups, cpn, cpn, 5, True, device_id), nn.PReLU(ngroups * cpn),
+                                 MaskConv2(ngroups, cpn, cpn, 5, True, device_id), nn.PReLU(ngroups * cpn))
+
+    def forward(self, x):
+        return self.net(x) + x
+
+
+class EntropyNet2(nn.Module):
+    """The training-time entropy model of the latent (reference train/EntropyNet2.py:24-74): three group-causal nets give every symbol the
+    logits, sigmas and means of a `num_gaussian`-component mixture.  Same submodule and parameter names (`weight_net.N...`, `delta_net.N...`,
+    `mean_net.N...`), so lic360_codec.cast_entropy_parameter maps its state_dict (under `ent.`) onto the codec drivers; the last sigma layer's
+    bias starts at 2.  The parameter-free tail of the reference's nets (ContextReshape, Softmax, ReLU) lives in GmmRateLoss.
+    forward(x) -> the reference's per-symbol loss_vec [n * ngroups * h * w], always on the library composition.
+    rate(x, mask=None) -> GmmRateLoss's (nats [n] float64, symbols [n] int64) on the route `head` names ("library" or "fused")."""
+    def __init__(self, ngroups, cpn=4, num_gaussian=3, device_id=0, drop_flag=False, head="library"):
+        super().__init__()
+        from lic360_operator import MaskConv2, DropGrad, GmmRateLoss
+        self.drop = DropGrad(drop_flag)
+
+        def net():
+            return nn.Sequential(MaskConv2(ngroups, 1, cpn, 5, False, device_id), nn.PReLU(ngroups * cpn),
+                                 *[EntropyResidualBlock(ngroups, cpn, device_id) for _ in range(5)],
+                                 MaskConv2(ngroups, cpn, num_gaussian, 5, True, device_id))
+        self.weight_net, self.mean_net, self.delta_net = net(), net(), net()
+        self.delta_net[7].bias.data.fill_(2)
+        self.head = GmmRateLoss(ngroups, num_gaussian, head, device_id)
+
+    def _nets(self, x):
+        tx = self.drop(x)
+        return self.weight_net(tx), self.delta_net(tx), self.mean_net(tx), tx
+
+    def forward(self, x):
+        logit, sigma, mean, tx = self._nets(x)
+        return self.head.loss_vec(logit, sigma, mean, tx)
+
+    def rate(self, x, mask=None):
+        logit, sigma, mean, tx = self._nets(x)
+        return self.head(logit, sigma, mean, tx, mask)
 
 
 def transform_gflops(channels=192, code_channels=192, h=512, w=1024):

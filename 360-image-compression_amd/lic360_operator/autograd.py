@@ -110,3 +110,25 @@ class ViewportQualityFn(torch.autograd.Function):
         coefs = tuple(next(maps) if kept else None for kept in ctx.kept)
         ga, gb = lic360.viewport_quality_backward(ctx.op, a, b, ctx.taps, coefs, _c(g_mse), _c(g_ssim), need_a=ctx.need[0], need_b=ctx.need[1])
         return ga, gb, None, None
+
+
+class GmmRateFn(torch.autograd.Function):
+    """(logit, sigma, mean, label, mask) -> (nats [n] float64, symbols [n] int64) of lic360.gmm_rate; saves the inputs only.  backward:
+    lic360.gmm_rate_backward recomputes every symbol from them; the label's gradient is asked for only when the label needs one, the mask
+    never gets one."""
+    @staticmethod
+    def forward(ctx, logit, sigma, mean, label, mask):
+        import lic360
+        nats, symbols = lic360.gmm_rate(logit, sigma, mean, label, mask)
+        ctx.need_label = ctx.needs_input_grad[3]
+        ctx.save_for_backward(logit, sigma, mean, label, mask)
+        ctx.mark_non_differentiable(symbols)
+        return nats, symbols
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_nats, g_symbols):
+        import lic360
+        logit, sigma, mean, label, mask = ctx.saved_tensors
+        d = lic360.gmm_rate_backward(logit, sigma, mean, label, mask, _c(g_nats.to(torch.float32)), need_label=ctx.need_label)
+        return d[0], d[1], d[2], d[3], None

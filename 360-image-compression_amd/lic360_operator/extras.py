@@ -11,6 +11,8 @@ metric / bookkeeping utilities, and two wrappers of out-of-scope native ops) and
   MultiProject   the 14 viewports of lic360.ProjectsOp (viewport metrics)
   ViewportQuality  viewport MSE / SSIM per image and viewport: one fused native pass (lic360.viewport_quality), MultiProject + SSIM elsewhere;
                  not a name of the reference
+  GmmRateLoss    the rate term of the training loss from the three entropy nets' raw outputs: one fused native pass each way (lic360.gmm_rate,
+                 autograd.GmmRateFn), or ContextReshape + softmax + ReLU + EntropyGmm + mask + sum; not a name of the reference
   MaskConv2      torch conv2d over a weight masked by lic360.MaskConstrainOp (the training-time form of the context conv)
 """
 import math
@@ -257,6 +259,74 @@ class ViewportQuality(nn.Module):
         per_view = lambda t: t.mean(dim=(1, 2, 3)).view(14, n).t().contiguous().to(a.device)
         mse, ssim = per_view((va - vb) ** 2), per_view(m)
         return (mse, ssim, m.to(a.device)) if return_map else (mse, ssim)
+
+
+class GmmRateLoss(nn.Module):
+    """The rate term of the training objective from the raw outputs of the three entropy nets (reference train/EntropyNet2.py:67-74 and
+    train/model_zoo.py:295-296): forward(logit, sigma, mean, label, mask=None, return_map=False) -> (nats [n] float64, symbols [n] int64), plus
+    the per-symbol loss [n, g, h, w] (0 where uncoded) with return_map.  logit, sigma, mean [n, ngroup * num_gaussian, h, w]; label, mask
+    [n, ngroup, h, w]; symbol (n, g, y, x) reads channel g * num_gaussian + i of each net.
+    route "library": the composition the reference trains with on this package's modules -- ContextReshape x 3, torch.softmax, relu, + 1e-5,
+    EntropyGmm, the product with the mask, a per-image sum in float64; symbols counts mask >= 0.5.  It takes tensors of any placement and
+    dtype (they are computed in fp32 on `device_id`, the results come back to the inputs' device).
+    route "fused": fp32 contiguous device tensors take one native pass -- lic360.gmm_rate without a recording pass, autograd.GmmRateFn (which
+    saves the inputs only and runs lic360.gmm_rate_backward) with one; a symbol is coded iff mask >= 0.5, the coder's rule, which is the
+    product for 0 / 1 masks.  CPU tensors, other dtypes, strided tensors and a recording call with return_map=True take the library route.
+    The attribute can be switched between calls."""
+    ROUTES = ("library", "fused")
+
+    def __init__(self, ngroup, num_gaussian=3, route="fused", device_id=0):
+        super().__init__()
+        from .quantize import ContextReshape
+        from .tables import EntropyGmm
+        from .autograd import recording
+        self.ngroup, self.num_gaussian, self.route = int(ngroup), int(num_gaussian), self._route(route)
+        self.device_id = device_id if isinstance(device_id, int) else list(device_id)[0]
+        self._recording = recording
+        # one reshape op per net: an op owns its output, the next call of the same op rewrites it
+        self.reshape = nn.ModuleList([ContextReshape(self.ngroup, device_id) for _ in range(3)])
+        self.ent_loss = EntropyGmm(self.num_gaussian, device=device_id)
+
+    @classmethod
+    def _route(cls, route):
+        if route not in cls.ROUTES:
+            raise ValueError("GmmRateLoss: route must be one of %s, got %r" % (", ".join(repr(r) for r in cls.ROUTES), route))
+        return route
+
+    def loss_vec(self, logit, sigma, mean, label):
+        """the reference's per-symbol loss_vec [n * ngroup * h * w] of fp32 device tensors, before any mask (the library composition)"""
+        weight = torch.softmax(self.reshape[0](logit), dim=1)
+        delta = torch.relu(self.reshape[1](sigma)) + 0.00001
+        return self.ent_loss(weight, delta, self.reshape[2](mean), label.reshape(-1, 1))
+
+    def _library(self, logit, sigma, mean, label, mask, return_map):
+        dev = logit.device if logit.is_cuda else torch.device("cuda:%d" % self.device_id)
+        f = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32)
+        vec = self.loss_vec(f(logit), f(sigma), f(mean), f(label))
+        n = label.shape[0]
+        if mask is None:
+            symbols = torch.full((n,), label[0].numel() if n else 0, dtype=torch.int64, device=logit.device)
+        else:
+            vec = vec * f(mask).reshape(-1)
+            symbols = (mask.reshape(n, -1) >= 0.5).sum(1).to(logit.device)
+        nats = vec.view(n, -1).double().sum(1).to(logit.device)
+        return (nats, symbols, vec.view(label.shape).to(logit.device)) if return_map else (nats, symbols)
+
+    def forward(self, logit, sigma, mean, label, mask=None, return_map=False):
+        if label.dim() != 4 or label.shape[1] != self.ngroup or logit.dim() != 4 or logit.shape[1] != self.ngroup * self.num_gaussian or \
+                logit.shape != sigma.shape or logit.shape != mean.shape or (mask is not None and mask.shape != label.shape) or \
+                (logit.shape[0],) + tuple(logit.shape[2:]) != (label.shape[0],) + tuple(label.shape[2:]):
+            raise ValueError("GmmRateLoss takes logit, sigma, mean [n, %d, h, w] and label, mask [n, %d, h, w]" % (self.ngroup * self.num_gaussian, self.ngroup))
+        ts = [t for t in (logit, sigma, mean, label, mask) if t is not None]
+        native = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == logit.device for t in ts) and label.numel() > 0
+        recording = self._recording(logit, sigma, mean, label)
+        if self._route(getattr(self, "route", "library")) == "fused" and native and not (recording and return_map):
+            import lic360
+            if not recording:
+                return lic360.gmm_rate(logit, sigma, mean, label, mask, return_map=return_map, ngroup=self.ngroup)
+            from .autograd import GmmRateFn
+            return GmmRateFn.apply(logit, sigma, mean, label, mask)
+        return self._library(logit, sigma, mean, label, mask, return_map)
 
 
 class _MaskConstrainFn(torch.autograd.Function):

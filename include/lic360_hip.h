@@ -338,6 +338,28 @@ int lic360_viewport_quality_backward(void *stream, const float *a, const float *
                                      const float *coef_q, const float *coef_r, const float *grad_mse, const float *grad_ssim, float *grad_a,
                                      float *grad_b, float *grad_views_a, float *grad_views_b);
 
+/* Fused GMM rate loss (no reference kernel: the reference's training objective, train/EntropyNet2.py:67-74 and train/model_zoo.py:295-296, runs
+ * ContextReshape x 3, softmax, ReLU + 1e-5, EntropyGmm, a product with the mask and a sum).  logit, sigma, mean [n][g*ng][h][w] fp32: the raw
+ * outputs of the three nets; label [n][g][h][w]; mask [n][g][h][w] or NULL (every symbol coded).  Symbol (n, g, y, x) reads channel g*ng + i of
+ * each net, i < ng, and is coded iff mask >= 0.5.  A coded symbol's loss is lic360_entropy_gmm's, bit for bit, of
+ * (lic360 softmax of the logits, sigma > 0 ? sigma + 1e-5f : 1e-5f, mean, label); an uncoded symbol costs 0, counts as no symbol and gets exact
+ * zeros in every gradient whatever its parameters hold.  nats [n] double (device): the coded symbols' fp32 losses added in double in a fixed
+ * order (no atomics: the same bits on every call); symbols [n] int64 (device): their count; map: NULL or [n][g][h][w] fp32, the per-symbol loss,
+ * 0 where uncoded.  scratch: lic360_gmm_rate_scratch_bytes(n, g, h, w) bytes of device memory, 8-byte aligned, fully written before it is read
+ * (the query returns 0 for arguments the launch refuses or that hold no symbol).
+ * lic360_gmm_rate_backward: with t = grad_nats[n] (device, fp32), d_logit, d_sigma, d_mean [n][g*ng][h][w] and, unless NULL, d_label
+ * [n][g][h][w], recomputed from the inputs: d_mean = md t, d_sigma = sigma > 0 ? dd t : 0, d_label = ld t, d_logit_i = w_i (wd_i t - dot),
+ * dot = sum_i fmaf(wd_i t, w_i, dot) in index order, with wd, dd, md, ld lic360_entropy_gmm's.  Every output element is written by every call.
+ * Nothing written may overlap anything read.  Both refuse (2) before anything is launched: a negative dimension, ng outside 1..16, a null
+ * pointer, a product of the dimensions that leaves the kernels' index types.  n*g*h*w == 0 is no error and launches nothing (pointers may then
+ * be NULL; with n > 0, nats and symbols are zeroed in the stream). */
+long lic360_gmm_rate_scratch_bytes(int n, int g, int h, int w);
+int lic360_gmm_rate(void *stream, const float *logit, const float *sigma, const float *mean, const float *label, const float *mask, int n, int g,
+                    int h, int w, int ng, double *nats, long long *symbols, float *map, void *scratch);
+int lic360_gmm_rate_backward(void *stream, const float *logit, const float *sigma, const float *mean, const float *label, const float *mask,
+                             const float *grad_nats, int n, int g, int h, int w, int ng, float *d_logit, float *d_sigma, float *d_mean,
+                             float *d_label);
+
 /* CppOp: ERP -> Craster parabolic projection.  lic360_cpp_rows fills the per-row column window ws [h][2] = (first column, count) and the
  * row angle theta [h] (host computes, device write); lic360_cpp_forward resamples x [nc][h][w] row by row, zero outside the window; mask
  * (may be NULL) gets 1 inside / 0 outside     extension/CPP.hpp:6-11, CPP_cuda.cu:11-22,46-122 */

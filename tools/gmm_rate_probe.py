@@ -1,0 +1,143 @@
+"""The GMM rate loss of the training objective on the raw outputs of the three entropy nets, G = 48 groups of 64 x 128 symbols, 3 mixture
+components, at batch 8 and batch 1, with SURVEY.md 8d's smooth masks (tests/util.py:latent_smooth) and with every symbol coded:
+  library  lic360_operator.GmmRateLoss(route="library"): ContextReshape x 3, torch.softmax, relu, + 1e-5, EntropyGmm, the product with the mask
+           and a per-image float64 sum, and their autograd;
+  fused    GmmRateLoss(route="fused"): lic360.gmm_rate (k_gmm_rate, k_gmm_rate_finish) and, recording, autograd.GmmRateFn with
+           lic360.gmm_rate_backward (k_gmm_rate_backward).
+The two alternate in one process: --repeats (20) repeats of 5 calls each, each after 2 warm-up calls, timed with device events; median
+(min - max) ms per call, for the forward alone (no gradient recorded) and for forward + backward of sum(g * nats) with the three nets'
+outputs recording.  The fused form is "faster" only if its median lies below the library's by more than the two min-max ranges added.
+Also: GB/s against the bytes the algorithm must move -- 3 ng + 2 reads per symbol forward; the same reads again plus 3 ng writes backward --
+the fused kernels timed on their own, each form's peak device memory above what the inputs hold (torch.cuda.max_memory_allocated over one
+forward + backward), and how far the two forms' results lie apart.  --json FILE keeps the table (default profiles/gmm_rate_probe.json)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "360-image-compression_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+G, H, W, NG = 48, 64, 128, 3
+
+
+def timed(fn, calls=5, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def summary(v):
+    return {"median_ms": sorted(v)[len(v) // 2], "min_ms": min(v), "max_ms": max(v)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "gmm_rate_probe.json"))
+    ap.add_argument("--repeats", type=int, default=20)
+    args = ap.parse_args()
+    import lic360
+    import lic360_operator as lo
+    import util
+    dev = "cuda:0"
+    mods = {k: lo.GmmRateLoss(G, NG, k) for k in ("library", "fused")}
+    rows = []
+    for n in (8, 1):
+        for kind in ("smooth", "all_coded"):
+            rng = np.random.default_rng(n)
+            lat = [util.latent_smooth(rng, G, H, W) for _ in range(n)]
+            label = torch.from_numpy(np.concatenate([c for c, _, _ in lat]) - np.float32(3.5)).to(dev)
+            mask = torch.from_numpy(np.concatenate([m for _, m, _ in lat])).to(dev) if kind == "smooth" else torch.ones((n, G, H, W), device=dev)
+            torch.manual_seed(n)
+            logit = torch.randn((n, G * NG, H, W), device=dev)
+            sigma = torch.rand((n, G * NG, H, W), device=dev) * 1.7 + 0.3
+            mean = label.repeat_interleave(NG, 1) + 0.6 * torch.randn((n, G * NG, H, W), device=dev)
+            g = torch.rand((n,), device=dev, dtype=torch.float64) + 0.5
+            leaves = [t.requires_grad_() for t in (logit, sigma, mean)]
+
+            def forward(q):
+                with torch.no_grad():
+                    return q(logit, sigma, mean, label, mask)
+
+            def step(q):
+                for t in leaves:
+                    t.grad = None
+                nats, _ = q(logit, sigma, mean, label, mask)
+                (g * nats).sum().backward()
+                return nats.detach(), [t.grad for t in leaves]
+
+            t_f, t_s, peak, res = {k: [] for k in mods}, {k: [] for k in mods}, {}, {}
+            for _ in range(args.repeats):
+                for k, q in mods.items():
+                    t_f[k].append(timed(lambda: forward(q)))
+                for k, q in mods.items():
+                    t_s[k].append(timed(lambda: step(q)))
+            for k, q in mods.items():
+                for t in leaves:
+                    t.grad = None
+                torch.cuda.synchronize()
+                held = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                nats, grads = step(q)
+                res[k] = (nats.clone(), [x.clone() for x in grads])
+                torch.cuda.synchronize()
+                peak[k] = torch.cuda.max_memory_allocated() - held
+            with torch.no_grad():                                         # the fused kernels on their own
+                gf = g.float()
+                ld, sd, md = logit.detach(), sigma.detach(), mean.detach()
+                outs = lic360.gmm_rate_backward(ld, sd, md, label, mask, gf)
+                parts = {"forward": [], "backward": []}
+                for _ in range(args.repeats):
+                    parts["forward"].append(timed(lambda: lic360.gmm_rate(ld, sd, md, label, mask)))
+                    parts["backward"].append(timed(lambda: lic360.gmm_rate_backward(ld, sd, md, label, mask, gf, out=outs)))
+            symbols = n * G * H * W
+            bytes_f, bytes_b = (3 * NG + 2) * 4.0 * symbols, (3 * NG + 2 + 3 * NG) * 4.0 * symbols
+            row = {"batch": n, "mask": kind, "shape": [G, H, W], "ng": NG, "symbols": symbols, "coded": int((mask >= 0.5).sum()),
+                   "bytes_forward": bytes_f, "bytes_backward": bytes_b, "forward": {}, "forward_backward": {}}
+            for name, t, nbytes in (("forward", t_f, bytes_f), ("forward_backward", t_s, bytes_f + bytes_b)):
+                med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+                spread = {k: max(v) - min(v) for k, v in t.items()}
+                for k, v in t.items():
+                    row[name][k] = dict(summary(v), GBps=nbytes / med[k] / 1e6)
+                row[name]["speedup"] = med["library"] / med["fused"]
+                row[name]["fused_is_faster"] = bool(med["library"] - med["fused"] > spread["library"] + spread["fused"])
+            row["peak_bytes"] = peak
+            row["fused_parts"] = {"forward": dict(summary(parts["forward"]), GBps=bytes_f / sorted(parts["forward"])[len(parts["forward"]) // 2] / 1e6),
+                                  "backward": dict(summary(parts["backward"]), GBps=bytes_b / sorted(parts["backward"])[len(parts["backward"]) // 2] / 1e6)}
+            row["nats_apart_rel_max"] = float(((res["fused"][0] - res["library"][0]).abs() / res["library"][0].abs()).max())
+            row["gradients_apart_rel_max"] = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(res["fused"][1], res["library"][1]))
+            rows.append(row)
+            for name in ("forward", "forward_backward"):
+                r = row[name]
+                print("batch %d, %-9s %-16s library %.4f (%.4f - %.4f) ms   fused %.4f (%.4f - %.4f) ms = %.0f GB/s   %.2fx   %s" % (
+                    n, kind, name, r["library"]["median_ms"], r["library"]["min_ms"], r["library"]["max_ms"], r["fused"]["median_ms"], r["fused"]["min_ms"],
+                    r["fused"]["max_ms"], r["fused"]["GBps"], r["speedup"], "fused is faster" if r["fused_is_faster"] else "NOT faster by the rule"), flush=True)
+            fp = row["fused_parts"]
+            print("    fused kernels alone: forward %.4f (%.4f - %.4f) ms = %.0f GB/s   backward %.4f (%.4f - %.4f) ms = %.0f GB/s   peak library %.0f MB, fused %.0f MB"
+                  "   apart: nats %.2e, gradients %.2e" % (fp["forward"]["median_ms"], fp["forward"]["min_ms"], fp["forward"]["max_ms"], fp["forward"]["GBps"],
+                                                         fp["backward"]["median_ms"], fp["backward"]["min_ms"], fp["backward"]["max_ms"], fp["backward"]["GBps"],
+                                                         peak["library"] / 1e6, peak["fused"] / 1e6, row["nats_apart_rel_max"], row["gradients_apart_rel_max"]), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), forms=["library", "fused"],
+                           workload="forward (no gradient recorded) and forward + backward of sum(g * nats), the three nets' outputs recording, the label not",
+                           repeats="median of %d alternating repeats of 5 calls, each after 2 warm-up calls; device events; ms per call" % args.repeats,
+                           rule="fused_is_faster: the fused median lies below the library median by more than the two min-max ranges added",
+                           bytes="GBps: (3 ng + 2) * 4 bytes read per symbol forward; those again plus 3 ng * 4 bytes written backward; over the median time",
+                           memory="peak_bytes: torch.cuda.max_memory_allocated over one forward + backward, minus what was allocated before it",
+                           apart="largest |fused - library| over the largest |library|, per tensor", rows=rows), f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
