@@ -12,23 +12,9 @@ import torch
 import cconv144_cases as cc
 import oracle as orc
 from util import case_rng
+from gpu_support import dev, host, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    import lic360
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return lic360
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 class _Call(object):

@@ -12,17 +12,11 @@ import torch
 import cconv144_cases as cc
 import cconv144_nt1_cases as n1
 import oracle as orc
-from test_gpu_cconv144_batch import _dc_call, dev, host
+from test_gpu_cconv144_batch import _dc_call
 from util import case_rng
+from gpu_support import dev, host, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    import lic360
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return lic360
 
 
 @pytest.mark.parametrize("case", n1.DC_CASES, ids=n1.nt1_id)

@@ -7,12 +7,9 @@ import torch
 
 import ref_codec as rc
 from util import latent
+from gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 @pytest.mark.parametrize("G,H,W,seed", [(6, 8, 12, 1), (8, 6, 10, 2)])

@@ -15,19 +15,9 @@ import dc_first_nets_cases as cases
 import oracle as orc
 import ref_codec as rc
 from util import conv_params, latent
+from gpu_support import dev, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    import lic360
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return lic360
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def _first_layer_planes(lic, G, H, W, N, nb, x_mod, planes, residual, checks):

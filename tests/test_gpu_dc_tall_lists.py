@@ -16,18 +16,14 @@ import time
 
 import numpy as np
 import pytest
-import torch
 
 import dc_tall_cases as cases
 from util import latent_smooth, make_main_params
+from gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 POISON = 1.0e10
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def _codec(G, H, W, B, layers, **env):

@@ -11,25 +11,15 @@ import pytest
 import torch
 
 from gen_golden import FIXED, draw_fixed
+from gpu_support import dev, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ac_golden.npz")
 
 
 @pytest.fixture(scope="module")
-def lic():
-    import lic360
-    assert torch.cuda.is_available()
-    return lic360
-
-
-@pytest.fixture(scope="module")
 def golden():
     return np.load(GOLD)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def dev_encode(lic, tab, ncode, lab, mask):

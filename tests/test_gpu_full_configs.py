@@ -14,16 +14,12 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 from util import latent, make_latent, make_main_params, make_imp_params
+from gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def load(name):

@@ -7,16 +7,10 @@ import pytest
 import torch
 
 import gdn_bf16x3_cases as gc
+import gpu_support as gs
+from gpu_support import dev, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _seeded_gdn(c, inverse, seed=0):
@@ -25,8 +19,8 @@ def _seeded_gdn(c, inverse, seed=0):
     m = lo.GDN(c, 0, inverse).to("cuda:0")
     g, b = gc.real_params(c, seed)
     with torch.no_grad():
-        m.gamma.copy_(torch.from_numpy(g))
-        m.beta.copy_(torch.from_numpy(b))
+        m.gamma.copy_(dev(g))
+        m.beta.copy_(dev(b))
     return m
 
 
@@ -52,8 +46,8 @@ def test_single_calls_are_held_to_the_bound(lic, c, scale, inverse):
     m = _seeded_gdn(c, inverse)
     gamma, beta = _effective(m)
     assert np.allclose(gamma, gc.effective(*gc.real_params(c, 0))[0], rtol=1e-6, atol=0) and gamma.min() >= 0 and beta.min() > 0   # the data of the CPU test
-    x = torch.from_numpy(gc.real_x(c, scale)).cuda()
-    g, b = torch.from_numpy(gamma).cuda(), torch.from_numpy(beta).cuda()
+    x = dev(gc.real_x(c, scale))
+    g, b = dev(gamma), dev(beta)
     got = lic.gdn_bf16x3_forward(x, lic.gdn_bf16x3_pack(g), b, inverse)
     _held_to_the_bound("c %d, scale %g, inverse %s" % (c, scale, inverse), got, x, gamma, beta, inverse)
     fp32 = lic.gdn_forward(x, g, b, inverse)                                # and it is not the fp32 kernel under another name
@@ -142,19 +136,6 @@ def test_a_recorded_gradient_takes_the_torch_path(lic, monkeypatch):
     assert torch.allclose(y3, y.detach(), rtol=1e-4, atol=0)
 
 
-def _conv_counting(lic, monkeypatch):
-    names = [n for n in dir(lic) if n.startswith("sconv") and not n.endswith(("_pack", "_supported")) and callable(getattr(lic, n))]
-    calls = {n: 0 for n in names}
-    for name in names:
-        real = getattr(lic, name)
-
-        def fn(*a, _real=real, _name=name, **k):
-            calls[_name] += 1
-            return _real(*a, **k)
-        monkeypatch.setattr(lic, name, fn)
-    return calls
-
-
 @pytest.mark.parametrize("which", ["down", "up"])
 def test_blocks_with_a_gdn(lic, monkeypatch, which):
     """ResidualBlockDown(192, 192) / ResidualBlockUp(192) at batch 2 on maps that pass _fusable, under set_conv_precision(m, "fp32", gdn="bf16x3"): one GDN
@@ -170,20 +151,19 @@ def test_blocks_with_a_gdn(lic, monkeypatch, which):
         blk, shape = lm.ResidualBlockUp(c, 0).to("cuda:0").eval(), (2, c, 68, 132)
     g, b = gc.real_params(c, 1)
     with torch.no_grad():
-        blk.relu2.gamma.copy_(torch.from_numpy(g))
-        blk.relu2.beta.copy_(torch.from_numpy(b))
+        blk.relu2.gamma.copy_(dev(g))
+        blk.relu2.beta.copy_(dev(b))
     x = _refresh(torch.randn(shape, device="cuda:0")).contiguous()
-    seen, calls = _recording(lic, monkeypatch), _conv_counting(lic, monkeypatch)
+    seen, calls = _recording(lic, monkeypatch), gs.SconvCalls(lic, monkeypatch)
     with torch.no_grad():
         want32 = blk(x.clone())
-        calls32 = dict(calls)
+        calls32 = calls.made()
         assert seen["names"] == ["fp32"] and sum(calls32.values()) == 3 and all("bf16" not in k for k, v in calls32.items() if v), calls32
         lm.set_conv_precision(blk, "fp32", gdn="bf16x3")
-        for k in calls:
-            calls[k] = 0
+        calls.reset()
         got = blk(x.clone())
         assert seen["names"] == ["fp32", "bf16x3"] and seen["packs"] == 1
-        assert dict(calls) == calls32, (calls, calls32)
+        assert calls.made() == calls32, (calls.made(), calls32)
         xin, beta, inverse, y = seen["b3"][0]
         assert tuple(xin.shape) == (2, c, 132, 260) and inverse == (which == "up")
         gamma_e, beta_e = _effective(blk.relu2)

@@ -8,16 +8,9 @@ import pytest
 import torch
 
 import gdn_bf16x3_cases as gc
+from gpu_support import dev, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _off16(t, off):
@@ -30,7 +23,7 @@ def _off16(t, off):
 
 
 def _dev(data):
-    return tuple(torch.from_numpy(data[k]).cuda() for k in ("x", "gamma", "beta"))
+    return tuple(dev(data[k]) for k in ("x", "gamma", "beta"))
 
 
 @pytest.mark.parametrize("tier", gc.TIERS)
@@ -58,7 +51,7 @@ def test_pack_bytes(lic, c):
     rng = np.random.default_rng(c)
     gamma = (rng.standard_normal((c, c)) * 3).astype(np.float32)
     gamma[::3, ::5] = rng.integers(257, 512, gamma[::3, ::5].shape)         # integers of 256 .. 512: ties and exact values
-    packed = lic.gdn_bf16x3_pack(torch.from_numpy(gamma).cuda())
+    packed = lic.gdn_bf16x3_pack(dev(gamma))
     assert packed.dtype == torch.bfloat16 and packed.numel() == 2 * c * c and packed.data_ptr() % 16 == 0
     want = torch.from_numpy(gc.packed_layout(gamma)).bfloat16()             # (exact: the values are bf16 numbers)
     assert np.array_equal(want.float().numpy(), gc.packed_layout(gamma))
@@ -131,7 +124,7 @@ def test_operand_checks(lic):
 def test_production_shapes_repeat_on_two_streams(lic, case):
     """each production case 20 times, alternating between two streams that run side by side: every output equals the reference"""
     data = gc.make(case, "both")
-    want = torch.from_numpy(gc.reference(case, data)).cuda()
+    want = dev(gc.reference(case, data))
     x, gamma, beta = _dev(data)
     packed = lic.gdn_bf16x3_pack(gamma)
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]

@@ -8,16 +8,9 @@ import pytest
 import torch
 
 import sconv_cases as sc
+from gpu_support import dev, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _off16(t, off):
@@ -34,12 +27,12 @@ def test_gdn_is_exact(lic, case):
     data = sc.gdn_make(case)
     sc.gdn_assert_exact_domain(case, data)
     want = sc.gdn_reference(case, data)
-    x = torch.from_numpy(data["x"]).cuda()
+    x = dev(data["x"])
     if case.misaligned:
         keep, x = _off16(x, 1)
         assert x.is_contiguous() and x.data_ptr() % 16 == 4                 # gdn_forward takes such a view as it is: no copy, the scalar-access kernels
     assert (x.numel() // (case.n * case.c) % 4 == 0 and x.data_ptr() % 16 == 0) == sc.gdn_branch_of(case)[1]
-    got = lic.gdn_forward(x, torch.from_numpy(data["gamma"]).cuda(), torch.from_numpy(data["beta"]).cuda(), case.inverse).cpu().numpy()
+    got = lic.gdn_forward(x, dev(data["gamma"]), dev(data["beta"]), case.inverse).cpu().numpy()
     sq = sc.gdn_perfect_squares(data)
     assert sq.any() and np.array_equal(got[sq], want[sq]), "%s: cells with an integer norm differ" % case.name
     bad = np.argwhere(got != want)
@@ -53,9 +46,9 @@ def test_gdn_writes_nothing_outside_out(lic, name, off):
     """`out` a slice of a larger sentinel buffer, on a 16-byte boundary and 4 bytes past one: the slice is exact, the rest untouched"""
     case = next(c for c in sc.GDN_SMALL if c.name == name)
     data = sc.gdn_make(case)
-    x = torch.from_numpy(data["x"]).cuda()
+    x = dev(data["x"])
     buf, out = _off16(torch.zeros_like(x), off)
-    ret = lic.gdn_forward(x, torch.from_numpy(data["gamma"]).cuda(), torch.from_numpy(data["beta"]).cuda(), case.inverse, out=out)
+    ret = lic.gdn_forward(x, dev(data["gamma"]), dev(data["beta"]), case.inverse, out=out)
     torch.cuda.synchronize()
     assert ret.data_ptr() == out.data_ptr()
     assert np.array_equal(out.cpu().numpy(), sc.gdn_reference(case, data))
@@ -67,7 +60,7 @@ def test_gdn_operand_checks(lic):
     c = 32
     case = sc.GdnCase("checks", c, 2, 6, 10, False, False, False)
     data = sc.gdn_make(case)
-    x, gamma, beta = (torch.from_numpy(data[k]).cuda() for k in ("x", "gamma", "beta"))
+    x, gamma, beta = (dev(data[k]) for k in ("x", "gamma", "beta"))
     good = lambda: torch.full(x.shape, 777.0, device="cuda:0")
     bad_outs = {"too small": torch.full((2, c, 6, 9), 777.0, device="cuda:0"), "too large": torch.full((2, c, 6, 11), 777.0, device="cuda:0"),
                 "same size, other shape": torch.full((2, c, 10, 6), 777.0, device="cuda:0"), "float64": torch.full(x.shape, 777.0, device="cuda:0", dtype=torch.float64),

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import gmm_rate_cases as gc
+from gpu_support import host, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -15,17 +16,6 @@ F = np.float32
 GUARD_BYTES = 256                # of canary on either side: the carved view keeps the allocation's 256-byte alignment
 CANARY = {torch.float32: float(F(-6.0221e23)), torch.float64: -6.0221e23, torch.int64: -0x5A5A5A5A5A5A5A5A, torch.uint8: 0x5A}
 SENTINEL = {torch.float32: float(gc.UNWRITTEN), torch.float64: 7.7701e33, torch.int64: 0x7777777777777777, torch.uint8: 0xA5}
-
-
-@pytest.fixture(scope="module")
-def lic():
-    import lic360
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return lic360
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 class Arena(object):

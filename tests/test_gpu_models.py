@@ -6,17 +6,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gpu_support as gs
+from gpu_support import dev, lic  # noqa: F401
 from util import _block_params, _refresh
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _trim(x, pad):
@@ -124,10 +118,7 @@ def test_blocks_match_the_oracle(lic):
     with torch.no_grad():
         for cls, fn in ((lm.ResidualBlock, orc.blocks.residual), (lm.ResidualBlockV2, orc.blocks.residual_v2),
                         (lambda ch, d: lm.ResidualBlockDown(ch, ch, d), orc.blocks.residual_down), (lm.ResidualBlockUp, orc.blocks.residual_up)):
-            blk = cls(c, 0).to("cuda:0")
-            for prm in blk.parameters():                                    # PReLU slopes / GDN parameters away from their symmetric defaults
-                if prm.dim() <= 2:
-                    prm.add_(0.05 * torch.rand_like(prm))
+            blk = gs.jitter(cls(c, 0).to("cuda:0"))                         # PReLU slopes / GDN parameters away from their symmetric defaults
             got = blk(x.clone()).cpu().numpy()
             want = fn(xn.copy(), _block_params(blk))
             assert got.shape == want.shape, (got.shape, want.shape)
@@ -161,7 +152,6 @@ def test_sconv3x3_matches_the_oracle_conv(lic, case):
     want = orc.conv2d(xin, w, b, 1, 1 - crop)
     if act:
         want = orc.prelu(want, sl)
-    dev = lambda t: None if t is None else torch.from_numpy(t).cuda()
     out = torch.full((2, cout, hp - 2 * crop, wp - 2 * crop), 7.0, device="cuda:0")
     lic.sconv3x3(dev(x), lic.sconv3x3_pack(dev(w)), dev(b), dev(sl) if act else None, dev(res), out, pad=2, sphere=sphere, ring=ring, crop=crop, ring_w=ring_w)
     got = out.cpu().numpy()
@@ -184,7 +174,6 @@ def test_sconv3x3_fuses_the_pixel_shuffle(lic):
     w = (rng.standard_normal((cout, cin, 3, 3)) * 0.1).astype(np.float32)
     b, sl = rng.standard_normal(cout).astype(np.float32), rng.random(cout).astype(np.float32)
     want = orc.dtow(orc.prelu(orc.conv2d(orc.sphere_pad_inplace(x.copy(), 2), w, b, 1, 0), sl), 2, True)       # [2, 48, 2 (hp - 2), 2 (wp - 2)]
-    dev = lambda t: torch.from_numpy(t).cuda()
     out = torch.full((2, cout // 4, 2 * (hp - 2), 2 * (wp - 2)), 7.0, device="cuda:0")
     lic.sconv3x3(dev(x), lic.sconv3x3_pack(dev(w)), dev(b), dev(sl), None, out, pad=2, sphere=1, ring=2, crop=1, shuffle=True)
     got = out.cpu().numpy()
@@ -213,7 +202,6 @@ def test_sconv1x1_matches_the_oracle_conv(lic, case):
         want = orc.prelu(want, sl)
     if with_res:
         want = want + res
-    dev = lambda t: None if t is None else torch.from_numpy(t).cuda()
     out = torch.full((2, cout, hp, wp), 7.0, device="cuda:0")
     lic.sconv1x1(dev(x), lic.sconv1x1_pack(dev(w)), dev(b), dev(sl) if act else None, dev(res), out, ring=ring, ring_w=ring_w)
     got = out.cpu().numpy()
@@ -229,34 +217,28 @@ def test_fused_blocks_match_the_oracle_at_full_width(lic, monkeypatch):
     here for a small map), against the oracle's blocks: the whole output, aprons included"""
     import oracle as orc
     import lic360_models as lm
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0)
+    gs.count_rule(monkeypatch, lm)
     torch.manual_seed(6)
     c = 192
     x = _refresh(torch.randn((1, c, 12, 20), device="cuda:0")).contiguous()
     xn = x.cpu().numpy()
-    calls = []
-    real = lic.sconv3x3
-    monkeypatch.setattr(lic, "sconv3x3", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = gs.SconvCalls(lic, monkeypatch)
     with torch.no_grad():
-        for cls, fn, ncalls in ((lm.ResidualBlock, orc.blocks.residual, 1), (lm.ResidualBlockV2, orc.blocks.residual_v2, 2),
-                                (lambda ch, d: lm.ResidualBlockDown(ch, ch, d), orc.blocks.residual_down, 1), (lm.ResidualBlockUp, orc.blocks.residual_up, 2)):
-            blk = cls(c, 0).to("cuda:0")
-            for prm in blk.parameters():
-                if prm.dim() <= 2:
-                    prm.add_(0.05 * torch.rand_like(prm))
-            del calls[:]
+        for cls, fn, ncalls, n1 in ((lm.ResidualBlock, orc.blocks.residual, 1, 2), (lm.ResidualBlockV2, orc.blocks.residual_v2, 2, 0),
+                                    (lambda ch, d: lm.ResidualBlockDown(ch, ch, d), orc.blocks.residual_down, 1, 0), (lm.ResidualBlockUp, orc.blocks.residual_up, 2, 1)):
+            blk = gs.jitter(cls(c, 0).to("cuda:0"))
+            calls.reset()
             got = blk(x.clone()).cpu().numpy()
-            assert len(calls) == ncalls, (type(blk).__name__, len(calls))
+            assert calls.only(sconv3x3=ncalls, sconv1x1=n1), (type(blk).__name__, calls.made())   # (the 1x1 layers as tests/test_gpu_sconv_bf16x1.py counts them)
             want = fn(xn.copy(), _block_params(blk))
             assert np.allclose(got, want, rtol=1e-4, atol=1e-4), "%s: max abs error %g" % (type(blk).__name__, np.abs(got - want).max())
         att = lm.AttentionBlock(c, 0).to("cuda:0")
         monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 1 << 30)
         want = att(x.clone())                                                   # the library path of the same module
-        monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
-        del calls[:]
+        gs.count_rule(monkeypatch, lm)
+        calls.reset()
         got = att(x.clone())
-        assert len(calls) == 6 and torch.allclose(got, want, rtol=1e-4, atol=1e-4), float((got - want).abs().max())
+        assert calls.only(sconv3x3=6, sconv1x1=12) and torch.allclose(got, want, rtol=1e-4, atol=1e-4), float((got - want).abs().max())
 
 
 def test_state_dict_layout_is_the_references(lic):

@@ -6,36 +6,11 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_support as gs
+from gpu_support import dev, lic  # noqa: F401
 from util import _block_params, _refresh
 
 pytestmark = pytest.mark.gpu
-
-NAMES = ("sconv3x3", "sconv1x1", "sconv3x3_bf16x3", "sconv1x1_bf16x3", "sconv3x3s2", "sconv1x1s2")
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
-
-
-def _counting(lic, monkeypatch):
-    calls = dict.fromkeys(NAMES, 0)
-    for name in calls:
-        real = getattr(lic, name)
-        def fn(*a, _real=real, _name=name, **k):
-            calls[_name] += 1
-            return _real(*a, **k)
-        monkeypatch.setattr(lic, name, fn)
-    return calls
-
-
-def _reset(calls):
-    for k in calls:
-        calls[k] = 0
-
 
 @pytest.mark.parametrize("case", [(3, 192, 192, 2, 40, 56, True, False), (3, 32, 96, 1, 26, 44, False, True), (3, 16, 192, 3, 12, 20, True, True),
                                   (1, 192, 192, 2, 40, 56, False, True), (1, 32, 96, 1, 26, 44, True, False), (1, 64, 384, 3, 12, 20, True, True)],
@@ -57,7 +32,6 @@ def test_sconv_s2_matches_the_oracle_conv(lic, case):
         want = orc.prelu(want, sl)
     if with_res:
         want = want + res
-    dev = lambda t: None if t is None else torch.from_numpy(t).cuda()
     out = torch.full((n, cout, oh + 4, ow + 4), 7.0, device="cuda:0")
     if ks == 3:
         lic.sconv3x3s2(dev(x), lic.sconv3x3_pack(dev(w)), dev(b), dev(sl) if act else None, dev(res), out, pad=2, sphere=True, oring=2)
@@ -79,12 +53,7 @@ def _blocks(lm, c):
         return orc.sphere_trim(orc.conv2d(orc.sphere_pad_inplace(x.copy(), 2), p["conv.weight"], p["conv.bias"], 2, 3), 2)
     out = []
     for blk, fn in ((lm.ResidualBlockDown(c, c, 0), orc.blocks.residual_down), (lm.SphereConv2(c, c, 3, 2, 3, 0), sphere_conv2)):
-        blk = blk.to("cuda:0")
-        with torch.no_grad():
-            for prm in blk.parameters():
-                if prm.dim() <= 2:
-                    prm.add_(0.05 * torch.rand_like(prm))
-        out.append((blk, fn))
+        out.append((gs.jitter(blk.to("cuda:0")), fn))
     return out
 
 
@@ -93,22 +62,21 @@ def test_down_blocks_fused_match_the_oracle_at_full_width(lic, monkeypatch):
     output, aprons included; the launches are counted.  Then the same modules with stride-2 fusion alone switched off: no stride-2 call, the same
     result; and with every fused threshold out of reach: the whole block on the library."""
     import lic360_models as lm
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0)
-    monkeypatch.setattr(lm, "FUSED_S2_MIN_WORKGROUPS", 0)
+    gs.count_rule(monkeypatch, lm, stride2=True)
     torch.manual_seed(16)
     c = 192
     x = _refresh(torch.randn((2, c, 44, 76), device="cuda:0")).contiguous()   # interior 40 x 72 -> 20 x 36: ragged in rows and columns
     xn = x.cpu().numpy()
-    calls = _counting(lic, monkeypatch)
+    rec = gs.SconvCalls(lic, monkeypatch)
+    calls = rec.counts
     expect = {"ResidualBlockDown": dict(sconv3x3s2=1, sconv1x1s2=1, sconv3x3=1), "SphereConv2": dict(sconv3x3s2=1)}
     with torch.no_grad():
         for blk, fn in _blocks(lm, c):
             name = type(blk).__name__
-            _reset(calls)
+            rec.reset()
             xin = x.clone()
             got = blk(xin)
-            assert calls == dict(dict.fromkeys(NAMES, 0), **expect[name]), (name, calls)
+            assert rec.only(**expect[name]), (name, rec.made())
             assert torch.equal(xin, x), name + ": the fused path must not modify its input"
             got = got.cpu().numpy()
             want = fn(xn.copy(), _block_params(blk))
@@ -117,7 +85,7 @@ def test_down_blocks_fused_match_the_oracle_at_full_width(lic, monkeypatch):
             assert not got[:, :, :2].any() and not got[:, :, -2:].any() and not got[:, :, :, :2].any() and not got[:, :, :, -2:].any()
             # stride-2 fusion alone off
             monkeypatch.setattr(lm, "FUSED_S2_MIN_WORKGROUPS", 1 << 30)
-            _reset(calls)
+            rec.reset()
             lib = blk(x.clone()).cpu().numpy()
             assert calls["sconv3x3s2"] == 0 and calls["sconv1x1s2"] == 0, (name, calls)
             assert calls["sconv3x3"] == (1 if name == "ResidualBlockDown" else 0), (name, calls)     # the stride-1 conv2 stays fused
@@ -126,67 +94,65 @@ def test_down_blocks_fused_match_the_oracle_at_full_width(lic, monkeypatch):
         # the stride-1 threshold out of reach: the whole Down block goes down the library path
         blk = _blocks(lm, c)[0][0]
         monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 1 << 30)
-        _reset(calls)
+        rec.reset()
         lib = blk(x.clone())
-        assert not any(calls.values()), calls
-        monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
+        assert not rec.made(), rec.made()
+        gs.count_rule(monkeypatch, lm)
         assert torch.allclose(blk(x.clone()), lib, rtol=1e-4, atol=1e-4)
 
 
 def test_a_recorded_gradient_keeps_the_library_sequence(lic, monkeypatch):
     import lic360_models as lm
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0)
-    monkeypatch.setattr(lm, "FUSED_S2_MIN_WORKGROUPS", 0)
+    gs.count_rule(monkeypatch, lm, stride2=True)
     torch.manual_seed(17)
     c = 192
     x = _refresh(torch.randn((1, c, 20, 36), device="cuda:0")).contiguous()
-    calls = _counting(lic, monkeypatch)
+    rec = gs.SconvCalls(lic, monkeypatch)
+    calls = rec.counts
     for blk, _ in _blocks(lm, c):
         name = type(blk).__name__
         assert all(p.requires_grad for p in blk.parameters())
-        _reset(calls)
+        rec.reset()
         y = blk(x.clone())
-        assert not any(calls.values()), (name, calls)
+        assert not rec.made(), (name, rec.made())
         y.square().mean().backward()
         for pname, p in blk.named_parameters():
             assert p.grad is not None and bool(torch.isfinite(p.grad).all()), (name, pname)
         conv = blk.conv1 if name == "ResidualBlockDown" else blk.conv
         assert float(conv.weight.grad.abs().max()) > 0, name
         with torch.no_grad():                                               # and without recording the same module goes fused
-            _reset(calls)
+            rec.reset()
             y2 = blk(x.clone())
             assert calls["sconv3x3s2"] == 1, (name, calls)
             assert torch.allclose(y2, y.detach(), rtol=1e-4, atol=1e-4), name
         for p in blk.parameters():                                          # one parameter with requires_grad is enough
             p.requires_grad_(False)
         next(iter(blk.parameters())).requires_grad_(True)
-        _reset(calls)
+        rec.reset()
         blk(x.clone())
         assert calls["sconv3x3s2"] == 0 and calls["sconv1x1s2"] == 0, (name, calls)
 
 
 def test_bf16x3_mode_keeps_the_stride_2_layers_on_fp32(lic, monkeypatch):
     import lic360_models as lm
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0)
-    monkeypatch.setattr(lm, "FUSED_S2_MIN_WORKGROUPS", 0)
+    gs.count_rule(monkeypatch, lm, stride2=True)
     torch.manual_seed(18)
     c = 192
     x = _refresh(torch.randn((1, c, 20, 36), device="cuda:0")).contiguous()
-    calls = _counting(lic, monkeypatch)
+    rec = gs.SconvCalls(lic, monkeypatch)
+    calls = rec.counts
     with torch.no_grad():
         (down, fn), (sc2, _) = _blocks(lm, c)
         want = down(x.clone())
         lm.set_conv_precision(down, "bf16x3")
         lm.set_conv_precision(sc2, "bf16x3")
-        _reset(calls)
+        rec.reset()
         got = down(x.clone())
-        assert calls == dict(dict.fromkeys(NAMES, 0), sconv3x3s2=1, sconv1x1s2=1, sconv3x3_bf16x3=1), calls
+        assert rec.only(sconv3x3s2=1, sconv1x1s2=1, sconv3x3_bf16x3=1), rec.made()
         assert torch.allclose(got, want, rtol=1e-4, atol=1e-4)
-        _reset(calls)
+        rec.reset()
         sc2(x.clone())
-        assert calls == dict(dict.fromkeys(NAMES, 0), sconv3x3s2=1), calls
+        assert rec.only(sconv3x3s2=1), rec.made()
 
 
 def test_analysis_transform_with_and_without_stride_2_fusion(lic, monkeypatch):
@@ -194,7 +160,8 @@ def test_analysis_transform_with_and_without_stride_2_fusion(lic, monkeypatch):
     fusion on and off (stride-1 fusion on in both runs) agree within 1e-4 of the stage's own range -- the bound
     test_whole_codec_in_bf16x3_mode_at_the_reference_width uses between two arithmetic orders of these networks."""
     import lic360_models as lm
-    calls = _counting(lic, monkeypatch)
+    rec = gs.SconvCalls(lic, monkeypatch)
+    calls = rec.counts
     torch.manual_seed(19)
     enc = lm.EncoderV2(192, 192, 0).to("cuda:0").eval()
     stages, seen = (2, 5, 7), {}
@@ -202,13 +169,13 @@ def test_analysis_transform_with_and_without_stride_2_fusion(lic, monkeypatch):
         img = torch.rand((8, 3, 512, 1024), device="cuda:0")
         mode = ["fused"]
         hooks = [enc.net[i].register_forward_hook(lambda m, a, o, i=i: seen.setdefault((mode[0], i), o.clone())) for i in stages]
-        _reset(calls)
+        rec.reset()
         code, imp = enc(img)
         fused_calls = dict(calls)
         assert calls["sconv3x3s2"] >= 1 and calls["sconv3x3"] >= 1, calls
         monkeypatch.setattr(lm, "FUSED_S2_MIN_WORKGROUPS", 1 << 30)
         mode[0] = "library"
-        _reset(calls)
+        rec.reset()
         code_l, imp_l = enc(img)
         assert calls["sconv3x3s2"] == 0 and calls["sconv1x1s2"] == 0 and calls["sconv3x3"] >= 1, calls
         for h in hooks:

@@ -17,14 +17,11 @@ import pytest
 import torch
 
 from util import latent, latent_smooth, make_main_params
+from gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 POISON = 1.0e10
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def brute_need(mask):

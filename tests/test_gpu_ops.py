@@ -8,23 +8,9 @@ import torch
 
 import oracle as orc
 from util import conv_params, latent, case_rng
+from gpu_support import dev, host, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    import lic360
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return lic360
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 # ------------------------------------------------------------------ masked convolution, encode order

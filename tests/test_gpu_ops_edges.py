@@ -9,6 +9,7 @@ import torch
 
 import oracle as orc
 import ops_edge_cases as oe
+from gpu_support import host, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -16,17 +17,6 @@ F = np.float32
 GUARD = 64                       # floats (256 bytes) of canary on either side: the carved view keeps the allocation's 256-byte alignment
 CANARY = float(F(-6.0221e23))
 SENTINEL = float(F(7.7701e33))
-
-
-@pytest.fixture(scope="module")
-def lic():
-    import lic360
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return lic360
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def dev(a):

@@ -3,19 +3,15 @@ restatement over the oracle's tables (tests/rate_cases.py) -- bit for bit, whate
 latitude row; estimating disturbs nothing; and the real streams lie within the slack measured on the CPU."""
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch
 
 import rate_cases as rt
+from gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -0x0123456789ABCDEF
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def _sentinel(*shape):

@@ -19,22 +19,15 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_support as gs
 import sconv_bf16x1_cases as b1
 import sconv_cases as sc
+from gpu_support import lic  # noqa: F401
 from util import _refresh
 
 pytestmark = pytest.mark.gpu
 
 STRIDE1 = ("sconv3x3", "sconv1x1", "sconv3x3_bf16x3", "sconv1x1_bf16x3", "sconv3x3_bf16x1", "sconv1x1_bf16x1")
-STRIDE2 = ("sconv3x3s2", "sconv1x1s2")
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _window(c):
@@ -44,29 +37,17 @@ def _window(c):
 
 
 def _criterion(case, data, got, what, frame=True):
-    """one call against the float64 convolution of its bf16-rounded operands (1e-4), 16x closer to it than the fp32 convolution is; frame untouched"""
-    ref16, ref32 = b1.reference(case, data), sc.reference(case, data)
-    win = _window(case)
-    err, gap = float(np.abs(got[win] - ref16[win]).max()), float(np.abs(ref16[win] - ref32[win]).max())
-    print("%s: max |got - ref_bf16| = %.3g, max |ref_bf16 - ref_fp32| = %.3g, max |ref_bf16| = %.3g" % (what, err, gap, float(np.abs(ref16[win]).max())))
-    assert np.allclose(got[win], ref16[win], rtol=1e-4, atol=1e-4), "%s: max abs error %g" % (what, err)
-    assert 16 * err <= gap, "%s: %g from the single-pass bf16 statement, which is only %g from fp32" % (what, err, gap)
-    if frame:
-        rest = np.ones(got.shape, bool)
-        rest[win] = False
-        assert np.all(got[rest] == sc.SENTINEL), what
-    return err, gap
+    """gs.bf16x1_criterion against the float64 convolutions of the call's operands, rounded to bf16 and as given"""
+    return gs.bf16x1_criterion(b1.reference(case, data), sc.reference(case, data), got, _window(case), sc.SENTINEL, what, frame)
 
 
 def _call(lic, case, data):
-    dev = lambda t: None if t is None else torch.from_numpy(t).cuda()
     name = "sconv%dx%d_bf16x1" % (case.ks, case.ks)
     kw = dict(ring=case.ring, ring_w=case.ring_w, crop=case.crop, shuffle=case.shuffle)
     if case.ks == 3:
         kw.update(pad=case.pad, sphere=case.sphere)
-    out = torch.full(sc.out_shape(case), sc.SENTINEL, device="cuda:0")
-    getattr(lic, name)(dev(data["x"]), getattr(lic, name + "_pack")(dev(data["w"])), dev(data["b"]), dev(data["slope"]), dev(data["res"]), out, **kw)
-    return out.cpu().numpy()
+    ops = (gs.dev(data["x"]), getattr(lic, name + "_pack")(gs.dev(data["w"])), gs.dev(data["b"]), gs.dev(data["slope"]), gs.dev(data["res"]))
+    return gs.sentinel_call(lambda out: getattr(lic, name)(*ops, out, **kw), sc.out_shape(case), sc.SENTINEL)
 
 
 def _real_data(case, seed, wscale):
@@ -130,49 +111,10 @@ def test_each_form_takes_only_its_own_pack(lic):
     assert not lic.sconv3x3_bf16x1_supported(16, 192) and not lic.sconv1x1_bf16x1_supported(48, 96)
 
 
-class _Instrument(object):
-    """wraps lic360's convolutions and packs: counts the calls, keeps the weight behind every pack, records bf16x1 calls (operands cloned at call time,
-    output cloned behind it) when `record` is on, and -- when `emulate` is on -- rounds x and the weight to bf16 in front of the fp32 stride-1 calls"""
-    def __init__(self, lic, monkeypatch):
-        self.calls, self.records, self.record, self.emulate = dict.fromkeys(STRIDE1 + STRIDE2, 0), [], False, False
-        self.weights, self.rounded_packs = {}, {}                          # pack's data_ptr -> (pack, weight); -> the fp32 pack of the rounded weight
-        for name in STRIDE1:
-            real_pack = getattr(lic, name + "_pack")
-            monkeypatch.setattr(lic, name + "_pack", lambda w, _real=real_pack: self._pack(_real, w))
-            real = getattr(lic, name)
-            monkeypatch.setattr(lic, name, lambda *a, _real=real, _name=name, _pack=real_pack, **k: self._conv(_real, _name, _pack, a, k))
-        for name in STRIDE2:
-            real = getattr(lic, name)
-            monkeypatch.setattr(lic, name, lambda *a, _real=real, _name=name, **k: self._count(_real, _name, a, k))
-
-    def reset(self):
-        for k in self.calls:
-            self.calls[k] = 0
-        self.records = []
-
-    def _pack(self, real, w):
-        pk = real(w)
-        self.weights[pk.data_ptr()] = (pk, w.detach().clone())
-        return pk
-
-    def _count(self, real, name, a, k):
-        self.calls[name] += 1
-        return real(*a, **k)
-
-    def _conv(self, real, name, real_pack, a, k):
-        self.calls[name] += 1
-        x, packed = a[0], a[1]
-        if self.emulate and name in ("sconv3x3", "sconv1x1"):
-            key = packed.data_ptr()
-            if key not in self.rounded_packs:
-                self.rounded_packs[key] = real_pack(self.weights[key][1].bfloat16().float())
-            return real(x.bfloat16().float(), self.rounded_packs[key], *a[2:], **k)
-        if self.record and name.endswith("_bf16x1"):
-            keep = [None if t is None else t.detach().clone() for t in (x,) + tuple(a[2:5])]
-            out = real(*a, **k)
-            self.records.append((name, keep, self.weights[packed.data_ptr()][1], dict(k), out.detach().clone()))
-            return out
-        return real(*a, **k)
+def _instrument(lic, monkeypatch):
+    """the recorder with the weight behind every pack, bf16x1 calls recorded while `recording` and -- while `emulating` -- x and the weight rounded to bf16 in
+    front of the fp32 stride-1 calls"""
+    return gs.SconvCalls(lic, monkeypatch, emulate=("sconv3x3", "sconv1x1"), record=True)
 
 
 def _check_record(rec, what):
@@ -190,65 +132,46 @@ def _check_record(rec, what):
     return _criterion(case, data, out.cpu().numpy(), what, frame=False)
 
 
-def _rms(a):
-    return float(a.double().pow(2).mean().sqrt())
-
-
-def _ratio(out_b1, out_emu, out_32, what):
-    num, den = _rms(out_b1 - out_32), _rms(out_emu - out_32)
-    print("%s: rms(bf16x1 - fp32) = %.4g, rms(emulated - fp32) = %.4g, ratio %.4f; rms(fp32) = %.4g" % (what, num, den, num / den, _rms(out_32)))
-    assert den > 0 and 0.9 <= num / den <= 1.1, (what, num, den)
-    return num / den
-
-
-def _small_maps(monkeypatch):
-    import lic360_models as lm
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0)
-    return lm
-
-
 def test_fused_blocks_in_bf16x1_mode(lic, monkeypatch):
     """ResidualBlock / V2 / Down / Up at 192 channels (fused path forced on a small map): every stride-1 fused layer on its bf16x1 form and none on the
     others; every recorded call within the single-call criterion on its own input; the block's rms deviation from fp32 that of the emulated run"""
-    lm = _small_maps(monkeypatch)
-    ins = _Instrument(lic, monkeypatch)
+    import lic360_models as lm
+    gs.count_rule(monkeypatch, lm)
+    ins = _instrument(lic, monkeypatch)
     torch.manual_seed(6)
     c = 192
     x = _refresh(torch.randn((1, c, 12, 20), device="cuda:0")).contiguous()
     with torch.no_grad():
         for cls, n3, n1 in ((lm.ResidualBlock, 1, 2), (lm.ResidualBlockV2, 2, 0), (lambda ch, d: lm.ResidualBlockDown(ch, ch, d), 1, 0), (lm.ResidualBlockUp, 2, 1)):
-            blk = cls(c, 0).to("cuda:0")
-            for prm in blk.parameters():
-                if prm.dim() <= 2:
-                    prm.add_(0.05 * torch.rand_like(prm))
+            blk = gs.jitter(cls(c, 0).to("cuda:0"))
             name = type(blk).__name__
             ins.reset()
             out32 = blk(x.clone())
-            assert {k: ins.calls[k] for k in STRIDE1} == dict(dict.fromkeys(STRIDE1, 0), sconv3x3=n3, sconv1x1=n1), (name, ins.calls)
+            assert ins.only(sconv3x3=n3, sconv1x1=n1), (name, ins.made())
             ins.reset()
-            ins.emulate = True
+            ins.emulating = True
             emu = blk(x.clone())
-            ins.emulate = False
-            assert {k: ins.calls[k] for k in STRIDE1} == dict(dict.fromkeys(STRIDE1, 0), sconv3x3=n3, sconv1x1=n1), (name, ins.calls)
+            ins.emulating = False
+            assert ins.only(sconv3x3=n3, sconv1x1=n1), (name, ins.made())
             lm.set_conv_precision(blk, "bf16x1")
             ins.reset()
-            ins.record = True
+            ins.recording = True
             got = blk(x.clone())
-            ins.record = False
-            assert {k: ins.calls[k] for k in STRIDE1} == dict(dict.fromkeys(STRIDE1, 0), sconv3x3_bf16x1=n3, sconv1x1_bf16x1=n1), (name, ins.calls)
+            ins.recording = False
+            assert ins.only(sconv3x3_bf16x1=n3, sconv1x1_bf16x1=n1), (name, ins.made())
             assert len(ins.records) == n3 + n1
             for i, rec in enumerate(ins.records):
                 _check_record(rec, "%s call %d (%s)" % (name, i, rec[0]))
             assert got.shape == out32.shape and bool(torch.isfinite(got).all()) and not torch.equal(got, out32)
-            _ratio(got, emu, out32, name)
+            gs.bf16x1_ratio(got, emu, out32, name)
 
 
 def test_mode_switching(lic, monkeypatch):
     """fp32 -> bf16x1 -> bf16x3 -> fp32 -> bf16x1 on one block: each mode's output equals its own earlier output bit for bit (each precision's pack is
     cached apart) and differs from the others'; the default is fp32; unknown names raise"""
-    lm = _small_maps(monkeypatch)
-    ins = _Instrument(lic, monkeypatch)
+    import lic360_models as lm
+    gs.count_rule(monkeypatch, lm)
+    ins = _instrument(lic, monkeypatch)
     torch.manual_seed(7)
     c = 192
     x = _refresh(torch.randn((1, c, 12, 20), device="cuda:0")).contiguous()
@@ -262,7 +185,7 @@ def test_mode_switching(lic, monkeypatch):
             ins.reset()
             out = blk(x.clone())
             suffix = "" if mode == "fp32" else "_" + mode
-            assert {k: ins.calls[k] for k in STRIDE1} == dict(dict.fromkeys(STRIDE1, 0), **{"sconv3x3" + suffix: 2, "sconv1x1" + suffix: 1}), (mode, ins.calls)
+            assert ins.only(**{"sconv3x3" + suffix: 2, "sconv1x1" + suffix: 1}), (mode, ins.made())
             if mode in first:
                 assert torch.equal(out, first[mode]), mode
             else:
@@ -270,7 +193,7 @@ def test_mode_switching(lic, monkeypatch):
                     assert not torch.equal(out, o), (mode, other)
                 first[mode] = out
         assert set(first) == {"fp32", "bf16x1", "bf16x3"}
-        assert _rms(first["bf16x3"] - first["fp32"]) * 16 < _rms(first["bf16x1"] - first["fp32"])
+        assert gs.rms(first["bf16x3"] - first["fp32"]) * 16 < gs.rms(first["bf16x1"] - first["fp32"])
     for bad in ("bf16", "FP32", None):
         with pytest.raises(ValueError):
             lm.set_conv_precision(blk, bad)
@@ -289,7 +212,7 @@ def test_whole_codec_in_bf16x1_mode_at_the_reference_width(lic, monkeypatch):
     import lic360_models as lm
     from lic360_fused import FusedCodec, FusedImpCodec
     from util import make_main_params, make_imp_params
-    ins = _Instrument(lic, monkeypatch)
+    ins = _instrument(lic, monkeypatch)
     torch.manual_seed(12)
     C, G = 192, 48
     enc, dec = lm.CMP_Encoder(C, C, 8, 0).to("cuda:0").eval(), lm.CMP_Decoder(C, C, 8, 0).to("cuda:0").eval()
@@ -298,7 +221,7 @@ def test_whole_codec_in_bf16x1_mode_at_the_reference_width(lic, monkeypatch):
         dec.quant.weight.copy_(enc.quant.weight)
         img = torch.rand((2, 3, 512, 1024), device="cuda:0")
         code, mask, levels = enc(img)
-    calls = ins.calls
+    calls = ins.counts
     assert calls["sconv3x3_bf16x1"] > 0 and calls["sconv1x1_bf16x1"] > 0, calls
     assert calls["sconv3x3"] == 0 and calls["sconv1x1"] == 0 and calls["sconv3x3_bf16x3"] == 0 and calls["sconv1x1_bf16x3"] == 0, calls
     assert calls["sconv3x3s2"] > 0 and calls["sconv1x1s2"] > 0, calls        # the stride-2 layers: the fp32 stride-2 kernels, as in bf16x3 mode
@@ -327,9 +250,9 @@ def test_whole_codec_in_bf16x1_mode_at_the_reference_width(lic, monkeypatch):
         assert calls["sconv3x3"] > 0 and calls["sconv3x3_bf16x1"] == 0, calls
         n32 = dict(calls)
         ins.reset()
-        run["label"], ins.emulate = "emulated", True
+        run["label"], ins.emulating = "emulated", True
         dec(code2, mask2)
-        ins.emulate = False
+        ins.emulating = False
         assert dict(calls) == n32
         lm.set_conv_precision(dec, "bf16x1")
         ins.reset()
@@ -348,6 +271,6 @@ def test_whole_codec_in_bf16x1_mode_at_the_reference_width(lic, monkeypatch):
             assert torch.equal(seen[("bf16x1", i)], seen[("fp32", i)]) and torch.equal(seen[("emulated", i)], seen[("fp32", i)]), i
             continue
         assert not torch.equal(seen[("bf16x1", i)], seen[("fp32", i)]), i
-        _ratio(seen[("bf16x1", i)], seen[("emulated", i)], seen[("fp32", i)], "synthesis stage %d" % i)
+        gs.bf16x1_ratio(seen[("bf16x1", i)], seen[("emulated", i)], seen[("fp32", i)], "synthesis stage %d" % i)
     assert all(upstream[("bf16x1", i)] > 0 for i in (5, 8, 9)), upstream
     print("whole codec: max |bf16x1 - fp32| at the image = %g, max |fp32| = %g" % (float((rec - rec32).abs().max()), float(rec32.abs().max())))

@@ -8,17 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_support as gs
 import sconv_bf16x1_cases as b1
+from gpu_support import lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _fns(lic, case):
@@ -26,28 +20,23 @@ def _fns(lic, case):
     return getattr(lic, name), getattr(lic, name + "_pack")
 
 
-def _operands(lic, case, data):
-    """the call's device operands and keyword arguments (everything but `out`)"""
-    dev = lambda t: None if t is None else torch.from_numpy(t).cuda()
+def _call(lic, case, data):
+    """call(out) of a case on `data`: its entry point, device operands and keyword arguments"""
     conv, pack = _fns(lic, case)
+    ops = (gs.dev(data["x"]), pack(gs.dev(data["w"])), gs.dev(data["b"]), gs.dev(data["slope"]), gs.dev(data["res"]))
     kw = dict(ring=case.ring, ring_w=case.ring_w, crop=case.crop, shuffle=case.shuffle)
     if case.ks == 3:
         kw.update(pad=case.pad, sphere=case.sphere)
-    return conv, (dev(data["x"]), pack(dev(data["w"])), dev(data["b"]), dev(data["slope"]), dev(data["res"])), kw
-
-
-_REFS = {}                                                                  # case -> float32 reference of a production case's xrnd tier: shared with the repeatability test
+    return lambda out: conv(*ops, out, **kw)
 
 
 def _reference(case, tier, data):
-    if (case.name, tier) in _REFS:
-        return _REFS[case.name, tier]
-    want64 = b1.reference(case, data)
-    want = want64.astype(np.float32)
-    assert np.array_equal(want, want64)                                     # the expected values are fp32 numbers
-    if case.prod and tier == "xrnd":
-        _REFS[case.name, tier] = want
-    return want
+    """a production case's xrnd reference is kept: shared with the repeatability test"""
+    return gs.fp32_reference(lambda: b1.reference(case, data), ("sconv_bf16x1", case.name, tier) if case.prod and tier == "xrnd" else None)
+
+
+def _describe(case):
+    return lambda got, want: b1.describe_mismatch(case, True, got, want).replace("bf16x3", "bf16x1")
 
 
 PARAMS = [(c, tier) for c in b1.CASES_B1 for tier in b1.TIERS]
@@ -59,12 +48,9 @@ def test_sconv_bf16x1_is_exact(lic, case, tier):
     data = b1.make_case(case, tier)
     bound = b1.assert_exact_domain(case, data)
     want = _reference(case, tier, data)
-    conv, ops, kw = _operands(lic, case, data)
-    out = torch.full(b1.out_shape(case), b1.SENTINEL, device="cuda:0")
-    conv(*ops, out, **kw)
-    got = out.cpu().numpy()
+    got = gs.sentinel_call(_call(lic, case, data), b1.out_shape(case), b1.SENTINEL)
     print("%s / %s: branch %s, |b| + 4 |res| + sum |w~||x~| <= %g" % (case.name, tier, tuple(b1.branch_of(case, True)), bound))
-    assert np.array_equal(got, want), b1.describe_mismatch(case, True, got, want).replace("bf16x3", "bf16x1")
+    gs.check_whole_output(got, want, _describe(case))
 
 
 def test_the_pack_is_the_rounded_weight_in_operand_order(lic):
@@ -91,59 +77,27 @@ REPEATS = [c for c in b1.CASES_B1 if c.prod]
 def test_production_rows_repeat_bit_for_bit(lic, case):
     """20 launches, alternately on two streams into two outputs refilled with the sentinel before each launch: every output equals the reference"""
     data = b1.make_case(case, "xrnd")
-    want = torch.from_numpy(_reference(case, "xrnd", data)).cuda()
-    conv, ops, kw = _operands(lic, case, data)
-    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-    outs = [torch.empty(b1.out_shape(case), device="cuda:0") for _ in streams]
-    torch.cuda.synchronize()
-    try:
-        for rep in range(0, 20, 2):
-            for k, s in enumerate(streams):
-                with torch.cuda.stream(s):
-                    outs[k].fill_(b1.SENTINEL)
-                    conv(*ops, outs[k], **kw)
-            for k, s in enumerate(streams):
-                s.synchronize()
-                if not torch.equal(outs[k], want):
-                    got = outs[k].cpu().numpy()
-                    pytest.fail("launch %d (stream %d): %s" % (rep + k, k, b1.describe_mismatch(case, True, got, want.cpu().numpy())))
-    finally:
-        torch.cuda.synchronize()
+    gs.repeat_on_two_streams(_call(lic, case, data), b1.out_shape(case), _reference(case, "xrnd", data), b1.SENTINEL, _describe(case))
 
 
 def test_past_4gib(lic):
     """192 -> 192 at 516 x 1028, n = 22 (9 GB in, 9 GB out): image 10's planes straddle byte offset 2^32, image 21's element 2^31.  Images i and i + 11
     get the same input: they must give the same output, and no two others may; images 0 and 10 (and their twins) are compared with the float64 reference,
     the frame of every image with the sentinel."""
-    free = torch.cuda.mem_get_info()[0]
-    if free < 32 << 30:
-        print("test_past_4gib SKIPPED: %.1f GiB of device memory free, 32 needed" % (free / 2.0 ** 30))
-        pytest.skip("%.1f GiB of device memory free, 32 needed" % (free / 2.0 ** 30))
+    gs.skip_below_free_memory(32)
     case = b1.PAST_4GIB
     c1 = case._replace(n=1)
     half = case.n // 2
     xm = b1.TIERS["xrnd"][0]
     data = b1.make_case(c1, "xrnd")                                         # w, b, slope (its one image is not used)
     b1.assert_exact_domain(c1, dict(data, x=np.full((1, case.cin, 1, 1), xm, np.float32)))
-    g = torch.Generator(device="cuda:0")
-    g.manual_seed(17)
-    base = torch.randint(-xm, xm + 1, (half, case.cin, case.hp, case.wp), device="cuda:0", generator=g, dtype=torch.float32)
-    x = torch.empty((case.n,) + tuple(base.shape[1:]), device="cuda:0")
-    x[:half], x[half:] = base, base
-    del base
-    assert x.numel() * 4 > 2 ** 33 and x.numel() > 2 ** 31
+    x = gs.doubled(xm, 17, half, (case.cin, case.hp, case.wp))
     conv, pack = _fns(lic, case)
-    dev = lambda t: torch.from_numpy(t).cuda()
     out = torch.full(b1.out_shape(case), b1.SENTINEL, device="cuda:0")
-    conv(x, pack(dev(data["w"])), dev(data["b"]), dev(data["slope"]), None, out, pad=case.pad, sphere=case.sphere, ring=case.ring, ring_w=case.ring_w)
+    conv(x, pack(gs.dev(data["w"])), gs.dev(data["b"]), gs.dev(data["slope"]), None, out, pad=case.pad, sphere=case.sphere, ring=case.ring, ring_w=case.ring_w)
     torch.cuda.synchronize()
-    assert torch.equal(out[:half], out[half:]), "image i and image i + %d differ" % half
-    for i in range(half):
-        for j in range(i + 1, half):
-            assert not torch.equal(out[i], out[j]), "images %d and %d are equal" % (i, j)
-    r0, r1, c0, c1_ = case.ring, case.hp - case.ring, case.ring_w, case.wp - case.ring_w
-    s = b1.SENTINEL
-    assert bool((out[:, :, :r0] == s).all() and (out[:, :, r1:] == s).all() and (out[:, :, :, :c0] == s).all() and (out[:, :, :, c1_:] == s).all())
+    gs.pairs_check(out, "sconv3x3_bf16x1")
+    assert gs.frame_is_untouched(out, case.ring, case.hp - case.ring, case.ring_w, case.wp - case.ring_w, b1.SENTINEL)
     for img in (0, half - 1):
         xi = x[img:img + 1].cpu().numpy()
         assert b1.rounding_classes(xi) == {"exact", "down", "up", "tie_down", "tie_up"}

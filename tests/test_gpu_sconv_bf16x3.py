@@ -9,17 +9,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gpu_support as gs
+from gpu_support import dev, lic  # noqa: F401
 from util import _block_params, _refresh
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _bf16(a):
@@ -70,7 +64,6 @@ def test_sconv3x3_bf16x3_matches_the_oracle_conv(lic, case):
         want, want16 = orc.prelu(want, sl), np.where(want16 > 0, want16, want16 * sl[None, :, None, None])
     if with_res:
         want, want16 = want + res, want16 + res
-    dev = lambda t: None if t is None else torch.from_numpy(t).cuda()
     out = torch.full((2, cout, hp - 2 * crop, wp - 2 * crop), 7.0, device="cuda:0")
     lic.sconv3x3_bf16x3(dev(x), lic.sconv3x3_bf16x3_pack(dev(w)), dev(b), dev(sl) if act else None, dev(res), out, pad=2, sphere=sphere, ring=ring,
                         crop=crop, ring_w=ring_w)
@@ -90,7 +83,6 @@ def test_sconv3x3_bf16x3_fuses_the_pixel_shuffle(lic):
     want = orc.dtow(orc.prelu(orc.conv2d(xp, w, b, 1, 0), sl), 2, True)
     c16 = _conv_bf16(xp, w, b, 0)
     want16 = orc.dtow(np.where(c16 > 0, c16, c16 * sl[None, :, None, None]).astype(np.float32), 2, True)
-    dev = lambda t: torch.from_numpy(t).cuda()
     out = torch.full((2, cout // 4, 2 * (hp - 2), 2 * (wp - 2)), 7.0, device="cuda:0")
     lic.sconv3x3_bf16x3(dev(x), lic.sconv3x3_bf16x3_pack(dev(w)), dev(b), dev(sl), None, out, pad=2, sphere=1, ring=2, crop=1, shuffle=True)
     got = out.cpu().numpy()
@@ -113,7 +105,6 @@ def test_sconv1x1_bf16x3_matches_the_oracle_conv(lic, case):
         want, want16 = orc.prelu(want, sl), np.where(want16 > 0, want16, want16 * sl[None, :, None, None])
     if with_res:
         want, want16 = want + res, want16 + res
-    dev = lambda t: None if t is None else torch.from_numpy(t).cuda()
     out = torch.full((2, cout, hp, wp), 7.0, device="cuda:0")
     lic.sconv1x1_bf16x3(dev(x), lic.sconv1x1_bf16x3_pack(dev(w)), dev(b), dev(sl) if act else None, dev(res), out, ring=ring, ring_w=ring_w)
     _check(out.cpu().numpy(), want, want16, (slice(None), slice(None), slice(ring, hp - ring), slice(ring_w, wp - ring_w)))
@@ -131,7 +122,6 @@ def test_sconv1x1_bf16x3_shuffled_shortcut(lic):
     xc = np.ascontiguousarray(x[..., 1:-1, 1:-1])
     want = orc.dtow(orc.conv2d(xc, w, b, 1, 0), 2, True) + res
     want16 = orc.dtow(_conv_bf16(xc, w, b, 0).astype(np.float32), 2, True) + res
-    dev = lambda t: torch.from_numpy(t).cuda()
     out = torch.full(res.shape, 7.0, device="cuda:0")
     lic.sconv1x1_bf16x3(dev(x), lic.sconv1x1_bf16x3_pack(dev(w)), dev(b), None, dev(res), out, ring=2, crop=1, shuffle=True)
     _check(out.cpu().numpy(), want, want16, (slice(None), slice(None), slice(2, 2 * (hp - 2) - 2), slice(2, 2 * (wp - 2) - 2)))
@@ -199,42 +189,26 @@ def test_pack_layout_and_operand_checks(lic):
             assert not bool((out == 777.0).all())
 
 
-def _counting(lic, monkeypatch):
-    calls = {"sconv3x3": 0, "sconv1x1": 0, "sconv3x3_bf16x3": 0, "sconv1x1_bf16x3": 0}
-    for name in calls:
-        real = getattr(lic, name)
-        def fn(*a, _real=real, _name=name, **k):
-            calls[_name] += 1
-            return _real(*a, **k)
-        monkeypatch.setattr(lic, name, fn)
-    return calls
-
-
 def test_fused_blocks_in_bf16x3_mode_match_the_oracle(lic, monkeypatch):
     """ResidualBlock / V2 / Down / Up at 192 channels in bf16x3 mode (fused path forced on a small map): the oracle's blocks to 1e-4, 16x closer
     than the oracle's blocks with bf16-rounded conv weights; every fused convolution runs on its bf16x3 form, none on lic360.sconv3x3"""
     import oracle as orc
     import lic360_models as lm
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0)
+    gs.count_rule(monkeypatch, lm)
     torch.manual_seed(6)
     c = 192
     x = _refresh(torch.randn((1, c, 12, 20), device="cuda:0")).contiguous()
     xn = x.cpu().numpy()
-    calls = _counting(lic, monkeypatch)
+    rec = gs.SconvCalls(lic, monkeypatch)
     with torch.no_grad():
         for cls, fn, n3, n1 in ((lm.ResidualBlock, orc.blocks.residual, 1, 2), (lm.ResidualBlockV2, orc.blocks.residual_v2, 2, 0),
                                 (lambda ch, d: lm.ResidualBlockDown(ch, ch, d), orc.blocks.residual_down, 1, 0), (lm.ResidualBlockUp, orc.blocks.residual_up, 2, 1)):
-            blk = cls(c, 0).to("cuda:0")
-            for prm in blk.parameters():
-                if prm.dim() <= 2:
-                    prm.add_(0.05 * torch.rand_like(prm))
+            blk = gs.jitter(cls(c, 0).to("cuda:0"))
             lm.set_conv_precision(blk, "bf16x3")
-            for k in calls:
-                calls[k] = 0
+            rec.reset()
             got = blk(x.clone()).cpu().numpy()
             name = type(blk).__name__
-            assert calls == {"sconv3x3": 0, "sconv1x1": 0, "sconv3x3_bf16x3": n3, "sconv1x1_bf16x3": n1}, (name, calls)
+            assert rec.only(sconv3x3_bf16x3=n3, sconv1x1_bf16x3=n1), (name, rec.made())
             p = _block_params(blk)
             want = fn(xn.copy(), p)
             p16 = {k: (_bf16(v) if k.endswith("weight") and np.ndim(v) == 4 else v) for k, v in p.items()}
@@ -246,12 +220,11 @@ def test_fused_blocks_in_bf16x3_mode_match_the_oracle(lic, monkeypatch):
 
 def test_default_is_fp32_and_the_mode_switches_back(lic, monkeypatch):
     import lic360_models as lm
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0)
+    gs.count_rule(monkeypatch, lm)
     torch.manual_seed(7)
     c = 192
     x = _refresh(torch.randn((1, c, 12, 20), device="cuda:0")).contiguous()
-    calls = _counting(lic, monkeypatch)
+    calls = gs.SconvCalls(lic, monkeypatch).counts
     with torch.no_grad():
         torch.manual_seed(8)
         ref = lm.ResidualBlockUp(c, 0).to("cuda:0")
@@ -281,7 +254,7 @@ def test_whole_codec_in_bf16x3_mode_at_the_reference_width(lic, monkeypatch):
     import lic360_models as lm
     from lic360_fused import FusedCodec, FusedImpCodec
     from util import make_main_params, make_imp_params
-    calls = _counting(lic, monkeypatch)
+    calls = gs.SconvCalls(lic, monkeypatch).counts
     torch.manual_seed(12)
     C, G = 192, 48
     enc, dec = lm.CMP_Encoder(C, C, 8, 0).to("cuda:0").eval(), lm.CMP_Decoder(C, C, 8, 0).to("cuda:0").eval()

@@ -12,17 +12,11 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_support as gs
 import sconv_cases as sc
+from gpu_support import lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _fns(lic, case, b3):
@@ -30,29 +24,19 @@ def _fns(lic, case, b3):
     return getattr(lic, name), getattr(lic, name + "_pack")
 
 
-def _operands(lic, case, b3, data):
-    """the call's device operands and keyword arguments (everything but `out`)"""
-    dev = lambda t: None if t is None else torch.from_numpy(t).cuda()
+def _call(lic, case, b3, data):
+    """call(out) of a case on `data`: its entry point, device operands and keyword arguments"""
     conv, pack = _fns(lic, case, b3)
+    ops = (gs.dev(data["x"]), pack(gs.dev(data["w"])), gs.dev(data["b"]), gs.dev(data["slope"]), gs.dev(data["res"]))
     kw = dict(ring=case.ring, ring_w=case.ring_w, crop=case.crop, shuffle=case.shuffle)
     if case.ks == 3:
         kw.update(pad=case.pad, sphere=case.sphere)
-    return conv, (dev(data["x"]), pack(dev(data["w"])), dev(data["b"]), dev(data["slope"]), dev(data["res"])), kw
-
-
-_REFS = {}                                                                  # (case, tier) -> float32 reference of a production case: shared with the repeatability test
+    return lambda out: conv(*ops, out, **kw)
 
 
 def _reference(case, tier, data):
-    key = (case.name, tier)
-    if key not in _REFS:
-        want64 = sc.reference(case, data)
-        want = want64.astype(np.float32)
-        assert np.array_equal(want, want64)                                 # the expected values are fp32 numbers
-        if not case.prod or tier not in ("fp32", "xlo"):
-            return want
-        _REFS[key] = want
-    return _REFS[key]
+    """a production case's fp32 / xlo reference is kept: shared with the repeatability test"""
+    return gs.fp32_reference(lambda: sc.reference(case, data), ("sconv", case.name, tier) if case.prod and tier in ("fp32", "xlo") else None)
 
 
 PARAMS = [(c, b3, tier) for c in sc.CASES for b3, tier in sc.forms_of(c)]
@@ -64,12 +48,9 @@ def test_sconv_is_exact(lic, case, b3, tier):
     data = sc.make_case(case, tier)
     bound = sc.assert_exact_domain(case, data, tier)
     want = _reference(case, tier, data)
-    conv, ops, kw = _operands(lic, case, b3, data)
-    out = torch.full(sc.out_shape(case), sc.SENTINEL, device="cuda:0")
-    conv(*ops, out, **kw)
-    got = out.cpu().numpy()
+    got = gs.sentinel_call(_call(lic, case, b3, data), sc.out_shape(case), sc.SENTINEL)
     print("%s / %s: branch %s, |b| + 4 |res| + sum |w||x| <= %g" % (case.name, tier, tuple(sc.branch_of(case, b3)), bound))
-    assert np.array_equal(got, want), sc.describe_mismatch(case, b3, got, want)
+    gs.check_whole_output(got, want, lambda g, w: sc.describe_mismatch(case, b3, g, w))
 
 
 @pytest.mark.parametrize("ks", [3, 1])
@@ -85,17 +66,12 @@ def test_bf16_mfma_adds_integers_exactly_up_to_2_24(lic, ks):
                 b=np.zeros(192, np.float32), slope=None, res=None)
     assert all(not p[1].any() for p in (sc.bf16_split(data["x"]), sc.bf16_split(data["w"])))     # 8 significant bits: the hi product alone
     bound = sc.assert_exact_domain(case, data, "hi")
-    want64 = sc.reference(case, data)
-    want = want64.astype(np.float32)
-    assert np.array_equal(want, want64)
+    want = gs.fp32_reference(lambda: sc.reference(case, data))
     win = want[:, :, 2:-2, 2:-2]
     print("bf16 MFMA adder probe %dx%d: sums %g .. %g, bound %g" % (ks, ks, win.min(), win.max(), bound))
     assert win.min() > 2.0 ** 23 and bound < sc.EXACT_BELOW
-    conv, ops, kw = _operands(lic, case, True, data)
-    out = torch.full(sc.out_shape(case), sc.SENTINEL, device="cuda:0")
-    conv(*ops, out, **kw)
-    got = out.cpu().numpy()
-    assert np.array_equal(got, want), sc.describe_mismatch(case, True, got, want)
+    got = gs.sentinel_call(_call(lic, case, True, data), sc.out_shape(case), sc.SENTINEL)
+    gs.check_whole_output(got, want, lambda g, w: sc.describe_mismatch(case, True, g, w))
 
 
 REPEATS = [(c, b3, tier) for c in sc.PRODUCTION for b3, tier in sc.forms_of(c) if tier in ("fp32", "xlo")]
@@ -106,69 +82,28 @@ def test_production_cases_repeat_bit_for_bit(lic, case, b3, tier):
     """20 launches, alternately on two streams into two outputs refilled with the sentinel before each launch: every output equals the
     reference.  Determinism under ordinary use (two streams, ordinary arguments); stops at the first difference."""
     data = sc.make_case(case, tier)
-    want = torch.from_numpy(_reference(case, tier, data)).cuda()
-    conv, ops, kw = _operands(lic, case, b3, data)
-    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-    outs = [torch.empty(sc.out_shape(case), device="cuda:0") for _ in streams]
-    torch.cuda.synchronize()
-    try:
-        for rep in range(0, 20, 2):
-            for k, s in enumerate(streams):
-                with torch.cuda.stream(s):
-                    outs[k].fill_(sc.SENTINEL)
-                    conv(*ops, outs[k], **kw)
-            for k, s in enumerate(streams):
-                s.synchronize()
-                if not torch.equal(outs[k], want):
-                    got = outs[k].cpu().numpy()
-                    pytest.fail("launch %d (stream %d): %s" % (rep + k, k, sc.describe_mismatch(case, b3, got, want.cpu().numpy())))
-    finally:
-        torch.cuda.synchronize()
-
-
-def _frame_is_untouched(out, r0, r1, c0, c1):
-    return bool((out[:, :, :r0] == sc.SENTINEL).all() and (out[:, :, r1:] == sc.SENTINEL).all() and
-                (out[:, :, :, :c0] == sc.SENTINEL).all() and (out[:, :, :, c1:] == sc.SENTINEL).all())
+    gs.repeat_on_two_streams(_call(lic, case, b3, data), sc.out_shape(case), _reference(case, tier, data), sc.SENTINEL,
+                             lambda g, w: sc.describe_mismatch(case, b3, g, w))
 
 
 def test_past_4gib(lic):
     """192 -> 192 at 516 x 1028, n = 22: image 10's planes straddle byte offset 2^32, image 21's element 2^31.  Images i and i + 11 get the same
     input: they must give the same output, and no two others may; images 0, 10 and 21 are compared with the float64 reference, the frame of every
     image with the sentinel.  Then gdn_forward on a tensor of the same shape, checked the same way."""
-    free = torch.cuda.mem_get_info()[0]
-    if free < 32 << 30:
-        print("test_past_4gib SKIPPED: %.1f GiB of device memory free, 32 needed" % (free / 2.0 ** 30))
-        pytest.skip("%.1f GiB of device memory free, 32 needed" % (free / 2.0 ** 30))
+    gs.skip_below_free_memory(32)
     case = sc.PAST_4GIB
     c1 = case._replace(n=1)
     half = case.n // 2
-    g = torch.Generator(device="cuda:0")
-
-    def doubled(bound, seed):
-        g.manual_seed(seed)
-        base = torch.randint(-bound, bound + 1, (half, case.cin, case.hp, case.wp), device="cuda:0", generator=g, dtype=torch.float32)
-        x = torch.empty((case.n,) + tuple(base.shape[1:]), device="cuda:0")
-        x[:half], x[half:] = base, base
-        return x
-
-    def pairs_check(out, what):
-        assert torch.equal(out[:half], out[half:]), "%s: image i and image i + %d differ" % (what, half)
-        for i in range(half):
-            for j in range(i + 1, half):
-                assert not torch.equal(out[i], out[j]), "%s: images %d and %d are equal" % (what, i, j)
-
     for b3, tier in ((False, "fp32"), (True, "xlo")):
         data = sc.make_case(c1, tier)                                       # w, b, slope (its one image is not used)
         sc.assert_exact_domain(c1, dict(data, x=np.full((1, case.cin, 1, 1), sc.TIERS[tier][0], np.float32)), tier)
-        x = doubled(sc.TIERS[tier][0], 11 + b3)
-        assert x.numel() * 4 > 2 ** 33 and x.numel() > 2 ** 31
+        x = gs.doubled(sc.TIERS[tier][0], 11 + b3, half, (case.cin, case.hp, case.wp))
         conv, pack = _fns(lic, case, b3)
-        dev = lambda t: torch.from_numpy(t).cuda()
         out = torch.full(sc.out_shape(case), sc.SENTINEL, device="cuda:0")
-        conv(x, pack(dev(data["w"])), dev(data["b"]), dev(data["slope"]), None, out, pad=case.pad, sphere=case.sphere, ring=case.ring, ring_w=case.ring_w)
+        conv(x, pack(gs.dev(data["w"])), gs.dev(data["b"]), gs.dev(data["slope"]), None, out, pad=case.pad, sphere=case.sphere, ring=case.ring, ring_w=case.ring_w)
         torch.cuda.synchronize()
-        pairs_check(out, "sconv3x3" + ("_bf16x3" if b3 else ""))
-        assert _frame_is_untouched(out, case.ring, case.hp - case.ring, case.ring_w, case.wp - case.ring_w)
+        gs.pairs_check(out, "sconv3x3" + ("_bf16x3" if b3 else ""))
+        assert gs.frame_is_untouched(out, case.ring, case.hp - case.ring, case.ring_w, case.wp - case.ring_w, sc.SENTINEL)
         for img in (0, half - 1):
             want = sc.reference(c1, dict(data, x=x[img:img + 1].cpu().numpy())).astype(np.float32)
             for i in (img, img + half):
@@ -178,10 +113,10 @@ def test_past_4gib(lic):
     torch.cuda.empty_cache()
     gcase = sc.GdnCase("past_4gib", case.cin, case.n, case.hp, case.wp, False, False, True)
     gdata = sc.gdn_make(gcase, n=1)
-    x = doubled(15, 13)
-    out = lic.gdn_forward(x, torch.from_numpy(gdata["gamma"]).cuda(), torch.from_numpy(gdata["beta"]).cuda())
+    x = gs.doubled(15, 13, half, (case.cin, case.hp, case.wp))
+    out = lic.gdn_forward(x, gs.dev(gdata["gamma"]), gs.dev(gdata["beta"]))
     torch.cuda.synchronize()
-    pairs_check(out, "gdn_forward")
+    gs.pairs_check(out, "gdn_forward")
     for img in (0, half - 1):
         want = sc.gdn_reference(gcase, dict(gdata, x=x[img:img + 1].cpu().numpy()))
         for i in (img, img + half):

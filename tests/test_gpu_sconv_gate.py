@@ -7,17 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_support as gs
 import sconv_gate_cases as gc
+from gpu_support import lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _name(form):
@@ -28,14 +22,13 @@ def _name(form):
 def test_single_calls_are_held_to_the_bound(lic, name):
     case = gc.BY_NAME[name]
     d = gc.real_data(case)
-    dev = {k: torch.from_numpy(v).cuda() for k, v in d.items()}
+    dev = {k: gs.dev(v) for k, v in d.items()}
     win = gc.window(case)
     outs = {}
     for form in gc.FORMS:
         sfx = "" if form == "fp32" else "_" + form
-        out = torch.full(d["trunk"].shape, gc.SENTINEL, device="cuda:0")
-        getattr(lic, _name(form))(dev["x"], getattr(lic, "sconv1x1%s_pack" % sfx)(dev["w"]), dev["b"], dev["trunk"], dev["res"], out, ring=case.ring, ring_w=case.ring_w)
-        got = out.cpu().numpy()
+        ops = (dev["x"], getattr(lic, "sconv1x1%s_pack" % sfx)(dev["w"]), dev["b"], dev["trunk"], dev["res"])
+        got = gs.sentinel_call(lambda out: getattr(lic, _name(form))(*ops, out, ring=case.ring, ring_w=case.ring_w), d["trunk"].shape, gc.SENTINEL)
         want = gc.gate64(d["x"], d["w"], d["b"], d["trunk"], d["res"], form)
         excess = gc.parity_excess(got[win], want[win], d["trunk"][win], d["res"][win])
         print("%s / %s: max |out - ref| %.3g, excess over 1e-4 |trunk| + 1e-6 (1 + |residual|): %.3g" % (name, form, np.abs(got[win] - want[win]).max(), excess))
@@ -47,45 +40,17 @@ def test_single_calls_are_held_to_the_bound(lic, name):
     assert not np.array_equal(outs["fp32"], outs["bf16x1"])                 # the forms are really distinct
 
 
-class _Calls(object):
-    """counts every lic360.sconv* call and keeps the operands of the gate calls"""
-    def __init__(self, lic, monkeypatch):
-        self.counts, self.gates = {}, []
-        for name in [n for n in dir(lic) if n.startswith("sconv") and not n.endswith(("_pack", "_supported")) and callable(getattr(lic, n))]:
-            self.counts[name] = 0
-
-            def fn(*a, _real=getattr(lic, name), _name=name, **k):
-                self.counts[_name] += 1
-                if "_gate" in _name:
-                    self.gates.append((_name, a, k))
-                return _real(*a, **k)
-            monkeypatch.setattr(lic, name, fn)
-
-    def reset(self):
-        for k in self.counts:
-            self.counts[k] = 0
-        del self.gates[:]
-
-    def gate_calls(self):
-        return {k: v for k, v in self.counts.items() if "_gate" in k and v}
-
-    def others(self):
-        return {k: v for k, v in self.counts.items() if "_gate" not in k}
+def _gate_calls(calls):
+    return {k: v for k, v in calls.made().items() if "_gate" in k}
 
 
-def _force(monkeypatch, lm, on=True):
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0 if on else 1 << 30)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0)
+def _others(calls):
+    return {k: v for k, v in calls.counts.items() if "_gate" not in k}
 
 
 def _block(lm, c=192, seed=21):
     torch.manual_seed(seed)
-    att = lm.AttentionBlock(c, 0).to("cuda:0").eval()
-    with torch.no_grad():
-        for prm in att.parameters():
-            if prm.dim() <= 2:
-                prm.add_(0.05 * torch.rand_like(prm))
-    return att
+    return gs.jitter(lm.AttentionBlock(c, 0).to("cuda:0").eval())
 
 
 def _apron(t):
@@ -98,10 +63,10 @@ def _apron(t):
 def test_the_block_takes_the_fused_tail(lic, monkeypatch, precision):
     import lic360_models as lm
     from util import _refresh
-    _force(monkeypatch, lm)
+    gs.count_rule(monkeypatch, lm)
     att = _block(lm)
     x = _refresh(torch.randn((2, 192, 20, 36), device="cuda:0")).contiguous()
-    calls = _Calls(lic, monkeypatch)
+    calls = gs.SconvCalls(lic, monkeypatch, gates=True)
     entered = []
     att.attention[3].register_forward_hook(lambda *a: entered.append(1))
     with torch.no_grad():
@@ -110,8 +75,8 @@ def test_the_block_takes_the_fused_tail(lic, monkeypatch, precision):
         calls.reset()
         del entered[:]
         want = att(x.clone())
-        lib_counts = dict(calls.others())
-        assert not calls.gate_calls() and len(entered) == 1 and sum(lib_counts.values()) == 18, calls.counts
+        lib_counts = dict(_others(calls))
+        assert not _gate_calls(calls) and len(entered) == 1 and sum(lib_counts.values()) == 18, calls.counts
         if never_set is not None:
             assert torch.equal(want, never_set)                             # "library" gives the parent's bits
         lm.set_conv_precision(att, precision, gate="fused")
@@ -119,8 +84,8 @@ def test_the_block_takes_the_fused_tail(lic, monkeypatch, precision):
         del entered[:]
         xin = x.clone()
         got = att(xin)
-        assert calls.gate_calls() == {_name(precision): 1}, calls.counts   # one launch, of the form the precision names
-        assert calls.others() == lib_counts and not entered
+        assert _gate_calls(calls) == {_name(precision): 1}, calls.counts   # one launch, of the form the precision names
+        assert _others(calls) == lib_counts and not entered
         # the call's own operands through the float64 reference give the block's interior
         _, (a, packed, bias, trunk, residual, out), kw = calls.gates[0]
         assert kw == dict(ring=2) and out.data_ptr() == got.data_ptr() and residual.data_ptr() == xin.data_ptr() and bias.data_ptr() == att.attention[3].bias.data_ptr()
@@ -145,10 +110,10 @@ def test_the_block_takes_the_fused_tail(lic, monkeypatch, precision):
 def test_the_library_tail_runs_outside_the_conditions(lic, monkeypatch):
     import lic360_models as lm
     from util import _refresh
-    _force(monkeypatch, lm)
+    gs.count_rule(monkeypatch, lm)
     att = lm.set_conv_precision(_block(lm), "fp32", gate="fused")
     x = _refresh(torch.randn((2, 192, 20, 36), device="cuda:0")).contiguous()
-    calls = _Calls(lic, monkeypatch)
+    calls = gs.SconvCalls(lic, monkeypatch, gates=True)
     entered = []
     att.attention[3].register_forward_hook(lambda *a: entered.append(1))
 
@@ -156,12 +121,12 @@ def test_the_library_tail_runs_outside_the_conditions(lic, monkeypatch):
         calls.reset()
         del entered[:]
         out = run()
-        assert not calls.gate_calls() and len(entered) == 1, calls.counts
+        assert not _gate_calls(calls) and len(entered) == 1, calls.counts
         return out
 
     with torch.no_grad():
         got = att(x.clone())
-        assert calls.gate_calls() == {"sconv1x1_gate": 1} and not entered   # (the conditions hold here)
+        assert _gate_calls(calls) == {"sconv1x1_gate": 1} and not entered   # (the conditions hold here)
     # a recorded gradient on x, on every parameter, on one parameter outside the first bottleneck
     library(lambda: att(x.clone().requires_grad_()))
     library(lambda: att(x.clone()))
@@ -169,11 +134,11 @@ def test_the_library_tail_runs_outside_the_conditions(lic, monkeypatch):
         prm.requires_grad_(False)
     att.attention[3].bias.requires_grad_(True)
     fused_convs = library(lambda: att(x.clone()))
-    assert sum(calls.others().values()) == 18                               # (the bottlenecks stay fused: only the tail asks for the whole block's parameters)
+    assert sum(_others(calls).values()) == 18                               # (the bottlenecks stay fused: only the tail asks for the whole block's parameters)
     att.attention[3].bias.requires_grad_(False)
     calls.reset()
     del entered[:]
-    assert torch.equal(att(x.clone()), got) and calls.gate_calls() == {"sconv1x1_gate": 1} and not entered       # nothing records: fused again, with grad enabled
+    assert torch.equal(att(x.clone()), got) and _gate_calls(calls) == {"sconv1x1_gate": 1} and not entered       # nothing records: fused again, with grad enabled
     assert torch.allclose(fused_convs.detach(), got, rtol=1e-4, atol=1e-4)
     with torch.no_grad():
         # a non-contiguous x
@@ -187,17 +152,17 @@ def test_the_library_tail_runs_outside_the_conditions(lic, monkeypatch):
         library(lambda: att(x.clone()))
         att.attention[3].bias = bias
         # a map that _fusable refuses
-        _force(monkeypatch, lm, on=False)
+        monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 1 << 30)
         out = library(lambda: att(x.clone()))
         assert sum(calls.counts.values()) == 0 and torch.allclose(out, got, rtol=1e-4, atol=1e-4)
-        _force(monkeypatch, lm)
+        gs.count_rule(monkeypatch, lm)
         # a 48-channel block
         small = lm.set_conv_precision(_block(lm, 48), "fp32", gate="fused")
         hits = []
         small.attention[3].register_forward_hook(lambda *a: hits.append(1))
         calls.reset()
         small(_refresh(torch.randn((2, 48, 20, 36), device="cuda:0")).contiguous())
-        assert not calls.gate_calls() and len(hits) == 1
+        assert not _gate_calls(calls) and len(hits) == 1
 
 
 def test_whole_transforms_with_the_fused_gate(lic, monkeypatch):
@@ -206,8 +171,8 @@ def test_whole_transforms_with_the_fused_gate(lic, monkeypatch):
     import lic360_models as lm
     from lic360_fused import FusedCodec, FusedImpCodec
     from util import make_main_params, make_imp_params
-    _force(monkeypatch, lm)
-    calls = _Calls(lic, monkeypatch)
+    gs.count_rule(monkeypatch, lm)
+    calls = gs.SconvCalls(lic, monkeypatch, gates=True)
     torch.manual_seed(12)
     C, G = 192, 48
     enc = lm.set_conv_precision(lm.CMP_Encoder(C, C, 8, 0).to("cuda:0").eval(), "bf16x1", stride2="bf16x1", gdn="bf16x3", gate="fused")
@@ -215,7 +180,7 @@ def test_whole_transforms_with_the_fused_gate(lic, monkeypatch):
     with torch.no_grad():
         img = torch.rand((1, 3, 512, 1024), device="cuda:0")
         code, mask, levels = enc(img)
-        assert calls.gate_calls() == {"sconv1x1_gate_bf16x1": 2}, calls.counts
+        assert _gate_calls(calls) == {"sconv1x1_gate_bf16x1": 2}, calls.counts
         assert tuple(code.shape) == (1, G, 64, 128) and tuple(levels.shape) == (1, 1, 32, 64) and bool(torch.isfinite(code).all())
         fc = FusedCodec(G, 64, 128, max_batch=1)
         fc.load_layers(make_main_params(5, G))
@@ -229,5 +194,5 @@ def test_whole_transforms_with_the_fused_gate(lic, monkeypatch):
         assert torch.equal(code2, code * mask)
         calls.reset()
         image = dec(code2, mask2)
-        assert calls.gate_calls() == {"sconv1x1_gate_bf16x1": 2}, calls.counts
+        assert _gate_calls(calls) == {"sconv1x1_gate_bf16x1": 2}, calls.counts
         assert tuple(image.shape) == (1, 3, 512, 1024) and bool(torch.isfinite(image).all())

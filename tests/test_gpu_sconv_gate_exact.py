@@ -7,17 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_support as gs
 import sconv_gate_cases as gc
+from gpu_support import lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _fns(lic, form):
@@ -26,9 +20,12 @@ def _fns(lic, form):
 
 
 def _operands(lic, case, form, data):
-    dev = lambda t: torch.from_numpy(np.ascontiguousarray(t)).cuda()
     fn, pack = _fns(lic, form)
-    return fn, (dev(data["x"]), pack(dev(data["w"])), dev(data["b"]), dev(data["trunk"]), dev(data["res"])), dict(ring=case.ring, ring_w=case.ring_w)
+    return fn, (gs.dev(data["x"]), pack(gs.dev(data["w"])), gs.dev(data["b"]), gs.dev(data["trunk"]), gs.dev(data["res"])), dict(ring=case.ring, ring_w=case.ring_w)
+
+
+def _describe(case, form):
+    return lambda got, want: gc.describe_mismatch(case, form != "fp32", got, want).replace("bf16x3", form)
 
 
 @pytest.mark.parametrize("p", gc.PARAMS, ids=gc.ident)
@@ -37,11 +34,9 @@ def test_the_gate_is_exact(lic, p):
     data, want = gc.shared(case, form, tier)
     gc.assert_exact_domain(case, form, tier, data)
     fn, ops, kw = _operands(lic, case, form, data)
-    out = torch.full(want.shape, gc.SENTINEL, device="cuda:0")
-    assert fn(*ops, out, **kw) is out
-    got = out.cpu().numpy()
+    got = gs.sentinel_call(lambda out: fn(*ops, out, **kw), want.shape, gc.SENTINEL)
     print("%s: kernel %s, branch %s" % (gc.ident(p), gc.instantiation(case, form), tuple(gc.branch_of(case, form != "fp32"))))
-    assert np.array_equal(got, want), gc.describe_mismatch(case, form != "fp32", got, want).replace("bf16x3", form)
+    gs.check_whole_output(got, want, _describe(case, form))
     if case.name == "g_saturate":
         win = gc.window(case)
         t, r, g = data["trunk"][win], data["res"][win], got[win]
@@ -96,7 +91,7 @@ def test_the_wrappers_refuse_wrong_operands(lic, form):
     for other in gc.FORMS:                                                  # another form's pack
         if other != form:
             with pytest.raises(E):
-                fn(x, _fns(lic, other)[1](torch.from_numpy(data["w"]).cuda()), b, t, r, out, **kw)
+                fn(x, _fns(lic, other)[1](gs.dev(data["w"])), b, t, r, out, **kw)
     with pytest.raises(E):
         fn(x, pk, b, t, r, t, **kw)                                         # out overlapping an input
     with pytest.raises(E):
@@ -115,21 +110,6 @@ def test_the_wrappers_refuse_wrong_operands(lic, form):
 def test_the_production_map_repeats_bit_for_bit(lic, form):
     """10 launches, alternately on two streams into two outputs refilled with the sentinel before each launch: every output equals the reference"""
     case = gc.BY_NAME["g_prod_132x260"]
-    data, want_np = gc.shared(case, form, gc.TIERS[form][-1])
-    want = torch.from_numpy(want_np).cuda()
+    data, want = gc.shared(case, form, gc.TIERS[form][-1])
     fn, ops, kw = _operands(lic, case, form, data)
-    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-    outs = [torch.empty(want.shape, device="cuda:0") for _ in streams]
-    torch.cuda.synchronize()
-    try:
-        for rep in range(0, 10, 2):
-            for k, s in enumerate(streams):
-                with torch.cuda.stream(s):
-                    outs[k].fill_(gc.SENTINEL)
-                    fn(*ops, outs[k], **kw)
-            for k, s in enumerate(streams):
-                s.synchronize()
-                if not torch.equal(outs[k], want):
-                    pytest.fail("launch %d (stream %d): %s" % (rep + k, k, gc.describe_mismatch(case, form != "fp32", outs[k].cpu().numpy(), want_np)))
-    finally:
-        torch.cuda.synchronize()
+    gs.repeat_on_two_streams(lambda out: fn(*ops, out, **kw), want.shape, want, gc.SENTINEL, _describe(case, form), launches=10)

@@ -8,6 +8,8 @@ the wide kernel takes makes no narrow call; whole transforms at batch 1 with eve
 import pytest
 import torch
 
+import gpu_support as gs
+from gpu_support import lic  # noqa: F401
 from util import _refresh
 
 pytestmark = pytest.mark.gpu
@@ -16,48 +18,9 @@ FORMS = ("fp32", "bf16x3", "bf16x1")
 NARROW = ("sconv3x3_narrow", "sconv1x1_narrow", "sconv1x1_gate_narrow")
 
 
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
-
-
-class _Calls(object):
-    """counts every lic360.sconv* call (keeping the narrow calls' keywords) and every nn.Conv2d forward that reaches the library"""
-    def __init__(self, lic, monkeypatch):
-        self.counts, self.kw, self.library = {}, [], []
-        for name in [n for n in dir(lic) if n.startswith("sconv") and not n.endswith(("_pack", "_supported")) and callable(getattr(lic, n))]:
-            self.counts[name] = 0
-
-            def fn(*a, _real=getattr(lic, name), _name=name, **k):
-                self.counts[_name] += 1
-                if _name in NARROW:
-                    self.kw.append((_name, k["form"], k["cpw"]))
-                return _real(*a, **k)
-            monkeypatch.setattr(lic, name, fn)
-        real = torch.nn.Conv2d.forward
-
-        def conv_forward(mod, x):
-            self.library.append((mod.in_channels, mod.out_channels, mod.kernel_size[0], mod.stride[0]))
-            return real(mod, x)
-        monkeypatch.setattr(torch.nn.Conv2d, "forward", conv_forward)
-
-    def reset(self):
-        for k in self.counts:
-            self.counts[k] = 0
-        del self.kw[:]
-        del self.library[:]
-
-    def made(self):
-        return {k: v for k, v in self.counts.items() if v}
-
-
-def _wide(monkeypatch, lm, on):
-    """drop (or restore) the count rule: with it dropped and small="library" every layer runs on the wide kernels"""
-    monkeypatch.setattr(lm, "FUSED_MIN_WORKGROUPS", 0 if on else 256)
-    monkeypatch.setattr(lm, "FUSED_MIN_FILL", 0.0 if on else 0.8)
+def _calls(lic, monkeypatch):
+    """every lic360.sconv* call counted, the narrow calls' keywords, and every nn.Conv2d forward that reaches the library"""
+    return gs.SconvCalls(lic, monkeypatch, narrow=True, library=True)
 
 
 def _make(lm, kind, seed=31):
@@ -65,11 +28,7 @@ def _make(lm, kind, seed=31):
     c = 192
     blk = {"ResidualBlock": lambda: lm.ResidualBlock(c, 0), "ResidualBlockV2": lambda: lm.ResidualBlockV2(c, 0), "AttentionBlock": lambda: lm.AttentionBlock(c, 0),
            "ResidualBlockUp": lambda: lm.ResidualBlockUp(c, 0), "ResidualBlockDown": lambda: lm.ResidualBlockDown(c, c, 0)}[kind]().to("cuda:0").eval()
-    with torch.no_grad():
-        for prm in blk.parameters():
-            if prm.dim() <= 2:
-                prm.add_(0.05 * torch.rand_like(prm))
-    return blk
+    return gs.jitter(blk)
 
 
 def _sfx(p):
@@ -110,7 +69,7 @@ def test_the_blocks_route_small_launches_to_narrow_workgroups(lic, monkeypatch, 
     torch.manual_seed(5)
     x = _input(kind, n)
     blk = _make(lm, kind)
-    calls = _Calls(lic, monkeypatch)
+    calls = _calls(lic, monkeypatch)
     with torch.no_grad():
         never_set = blk(x.clone())
         library_convs = list(calls.library)
@@ -140,12 +99,12 @@ def test_the_blocks_route_small_launches_to_narrow_workgroups(lic, monkeypatch, 
             assert not stride1, stride1                                     # no library convolution for the routed layers
             assert [c for c in calls.library if c[3] == 2] == ([] if others or kind != "ResidualBlockDown" else [(192, 192, 1, 2), (192, 192, 3, 2)])
             # the wide kernels on the same map: the same bits
-            _wide(monkeypatch, lm, True)
+            gs.count_rule(monkeypatch, lm)                                  # dropped: with small="library" every layer runs on the wide kernels
             lm.set_conv_precision(blk, precision, gate="fused")
             calls.reset()
             wide = blk(x.clone())
             assert not any(calls.counts[k] for k in NARROW) and sum(calls.counts.values()) == sum(narrow.values()) + sum(others.values()), calls.made()
-            _wide(monkeypatch, lm, False)
+            gs.count_rule(monkeypatch, lm, on=False)
             assert torch.equal(got, wide), (kind, n, precision, float((got - wide).abs().max()))
             if precision == "fp32":
                 assert torch.allclose(got, lib, rtol=1e-4, atol=1e-4), float((got - lib).abs().max())
@@ -161,7 +120,7 @@ def test_the_library_path_runs_outside_the_other_conditions(lic, monkeypatch):
     import lic360_models as lm
     x = _input("ResidualBlockV2", 8)                                        # 36 x 68 at batch 8: both layers at cpw 48 in fp32
     blk = lm.set_conv_precision(_make(lm, "ResidualBlockV2"), "fp32", small="narrow")
-    calls = _Calls(lic, monkeypatch)
+    calls = _calls(lic, monkeypatch)
 
     def library(run):
         calls.reset()
@@ -205,7 +164,7 @@ def test_whole_transforms_at_batch_1_with_every_keyword(lic, monkeypatch):
     import lic360_models as lm
     from lic360_fused import FusedCodec, FusedImpCodec
     from util import make_main_params, make_imp_params
-    calls = _Calls(lic, monkeypatch)
+    calls = _calls(lic, monkeypatch)
     torch.manual_seed(12)
     C, G = 192, 48
     kw = dict(stride2="bf16x1", gdn="bf16x3", gate="fused", small="narrow")

@@ -8,20 +8,9 @@ import torch
 
 import sconv_gate_cases as gc
 import sconv_narrow_cases as nc
+from gpu_support import check_whole_output, dev as _dev, lic, repeat_on_two_streams, sentinel_call  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
-
-
-def _dev(t):
-    return None if t is None else torch.from_numpy(np.ascontiguousarray(t, np.float32)).cuda()
 
 
 def _sfx(form):
@@ -56,11 +45,9 @@ def test_the_narrow_convolutions_are_exact(lic, p):
     data, want = nc.shared(n.case, form, tier)
     nc.assert_exact_domain(n.case, form, tier, data)
     narrow, _ = _conv_call(lic, n.case, form, data)
-    out = torch.full(want.shape, nc.SENTINEL, device="cuda:0")
-    assert narrow(out, cpw) is out
-    got = out.cpu().numpy()
+    got = sentinel_call(lambda out: narrow(out, cpw), want.shape, nc.SENTINEL)
     print("%s: branch %s" % (nc.ident(p), tuple(nc.branch_of(n.case, form, cpw))))
-    assert np.array_equal(got, want), nc.describe_mismatch(n.case, form != "fp32", got, want).replace("bf16x3", form) + " (channel terms are the wide kernel's)"
+    check_whole_output(got, want, lambda g, w: nc.describe_mismatch(n.case, form != "fp32", g, w).replace("bf16x3", form) + " (channel terms are the wide kernel's)")
 
 
 @pytest.mark.parametrize("p", nc.gate_params(), ids=nc.ident)
@@ -69,10 +56,8 @@ def test_the_narrow_gate_is_exact(lic, p):
     data, want = gc.shared(case, form, tier)
     gc.assert_exact_domain(case, form, tier, data)
     narrow, _ = _gate_call(lic, case, form, data)
-    out = torch.full(want.shape, gc.SENTINEL, device="cuda:0")
-    assert narrow(out, cpw) is out
-    got = out.cpu().numpy()
-    assert np.array_equal(got, want), gc.describe_mismatch(case, form != "fp32", got, want).replace("bf16x3", form)
+    got = sentinel_call(lambda out: narrow(out, cpw), want.shape, gc.SENTINEL)
+    check_whole_output(got, want, lambda g, w: gc.describe_mismatch(case, form != "fp32", g, w).replace("bf16x3", form))
 
 
 @pytest.mark.parametrize("n", nc.CASES, ids=lambda n: n.case.name)
@@ -134,21 +119,7 @@ def test_the_production_layers_repeat_bit_for_bit(lic, n):
         cpw = n.cpws[0]
         if not nc.supported(form, n.case.ks, n.case.cin, n.case.cout, cpw):
             continue
-        data, want_np = nc.shared(n.case, form, nc.TIERS[form][-1])
-        want = torch.from_numpy(want_np).float().cuda()
+        data, want = nc.shared(n.case, form, nc.TIERS[form][-1])
         narrow, _ = _conv_call(lic, n.case, form, data)
-        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-        outs = [torch.empty(want.shape, device="cuda:0") for _ in streams]
-        torch.cuda.synchronize()
-        try:
-            for rep in range(0, 10, 2):
-                for k, s in enumerate(streams):
-                    with torch.cuda.stream(s):
-                        outs[k].fill_(nc.SENTINEL)
-                        narrow(outs[k], cpw)
-                for k, s in enumerate(streams):
-                    s.synchronize()
-                    if not torch.equal(outs[k], want):
-                        pytest.fail("%s launch %d (stream %d): %s" % (form, rep + k, k, nc.describe_mismatch(n.case, form != "fp32", outs[k].cpu().numpy(), want_np)))
-        finally:
-            torch.cuda.synchronize()
+        repeat_on_two_streams(lambda out: narrow(out, cpw), want.shape, want, nc.SENTINEL,
+                              lambda g, w: "%s: %s" % (form, nc.describe_mismatch(n.case, form != "fp32", g, w)), launches=10)

@@ -17,15 +17,11 @@ Measured on an MI355X, largest |cell| of e_buf[1] / e_buf[2] after each call (de
     regression test of bytes, symbols and finiteness; only the 12-group sequence can show the recurrence."""
 import numpy as np
 import pytest
-import torch
 
 import skip_age_cases as cases
+from gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 _batches = {}

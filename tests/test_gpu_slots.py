@@ -18,21 +18,11 @@ import torch
 import ref_codec as rc
 import slot_cases as sc
 from util import latent
+from gpu_support import dev, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 CASES = sc.raw_cases()
 G, H, W, B = 12, 8, 12, 4
-
-
-@pytest.fixture(scope="module")
-def lic():
-    import lic360
-    assert torch.cuda.is_available()
-    return lic360
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def i32(n=1, v=0):

@@ -8,16 +8,9 @@ import pytest
 import torch
 
 import viewport_quality_cases as vq
+from gpu_support import lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _op(lic, case):

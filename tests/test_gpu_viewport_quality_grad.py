@@ -13,17 +13,10 @@ import torch
 
 import viewport_quality_cases as vq
 import viewport_quality_grad_cases as vg
+from gpu_support import lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 IDS = [c.name for c in vg.CASES]
-
-
-@pytest.fixture(scope="module")
-def lic():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import lic360
-    return lic360
 
 
 def _op(lic, case):
