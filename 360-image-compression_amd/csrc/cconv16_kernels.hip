@@ -36,6 +36,7 @@
 #include "cconv_tree.h"
 #include "gmm_tables.h"
 #include "need.h"
+#include "codec_switches.h"
 
 #define C16_SLOTS 28                       // weight slots per lane class and step (cin = 4: 25 taps; cin = 1: 4 sub-quads x 7 taps)
 #define C16_TH 4                           // tile rows
@@ -1068,7 +1069,7 @@ __global__ __launch_bounds__(C16_THREADS, 2) void k_cconv16s(C16Args a) {
     }
 }
 
-static int c16_fill_args(C16Args &a, const lic360_conv_plan *p, int h, int w, int tpt = C16_TPT) {
+static int c16_fill_args(C16Args &a, const lic360_conv_plan *p, int h, int w, int gbk, int tpt = C16_TPT) {
     a.G = p->ngroup; a.cout = p->cout; a.hidden = p->constrain == 5 ? 0 : 1; a.H = h; a.W = w;
     if (lic360_ec16_layout(h, w, &a.hp, &a.wp)) return 2;
     a.n_gb = conv16_ngb(p);
@@ -1076,7 +1077,7 @@ static int c16_fill_args(C16Args &a, const lic360_conv_plan *p, int h, int w, in
     a.ntiles = a.ntx * ((h + C16_TH - 1) / C16_TH);
     a.n_chunks = (a.ntiles + tpt - 1) / tpt;
     a.NS = conv16_nsteps_max(p);
-    a.gbk = lic360_ec_gbk();                                                // task-order block size: 16 (blocks of 4 .. all measured: DESIGN 4.1 a)
+    a.gbk = gbk;                                                            // task-order block size: 16 (blocks of 4 .. all measured: DESIGN 4.1 a)
     a.code = a.mask = nullptr; a.pidx = a.plane_start = nullptr; a.rec = nullptr;
     a.list = a.cnt = nullptr; a.list_cap = 0;
     return 0;
@@ -1084,16 +1085,17 @@ static int c16_fill_args(C16Args &a, const lic360_conv_plan *p, int h, int w, in
 
 // x / residual / out: [n][C | nout][hp][wp] zero-haloed planes (lic360_ec16_layout).  ctr: 8 ints of device scratch.
 // list / cnt / cap: the layer's live tasks per XCD (need.h, lic360_ec_lists_build: [8][cap] entries, [8] counts), or NULL = every task.  The cells of
-// a skipped (tile, group block) are not written.  Internal entry (hidden visibility): the fused codec's dead-cone skip.
+// a skipped (tile, group block) are not written.  gbk: units per block of the task order, the one the list was built with (need.h: lic360_ec_lists).
+// Internal entry (hidden visibility): the fused codec's dead-cone skip.
 int lic360_cconv16_ec_list(void *stream, const lic360_conv_plan *p, const float *x, const float *packed16, const float *bias,
                            const float *act, const float *residual, float *out, int n, int h, int w, int nb, int x_mod, int *ctr,
-                           const int *list, const int *cnt, int cap) {
-    ARG_CHECK(p && conv16_ok(p) && x && packed16 && bias && out && ctr && n > 0 && h > 0 && w > 0 && nb > 0 && n % nb == 0 && x_mod > 0 && x_mod <= n);
+                           const int *list, const int *cnt, int cap, int gbk) {
+    ARG_CHECK(p && conv16_ok(p) && x && packed16 && bias && out && ctr && gbk > 0 && n > 0 && h > 0 && w > 0 && nb > 0 && n % nb == 0 && x_mod > 0 && x_mod <= n);
     ARG_CHECK((list != nullptr) == (cnt != nullptr) && (!list || (cap > 0 && p->cin == 4)));
     C16Args a;
     a.x = x; a.packed = packed16; a.bias = bias; a.act = act; a.residual = residual; a.out = out; a.ctr = ctr;
     a.npb = n / nb; a.x_mod = x_mod; a.N = n;
-    if (c16_fill_args(a, p, h, w)) return 2;
+    if (c16_fill_args(a, p, h, w, gbk)) return 2;
     a.list = list; a.cnt = cnt; a.list_cap = cap;
     ARG_CHECK((long)((n + 7) / 8) * a.n_chunks * a.n_gb < C16_TASK_END);
     hipStream_t s = (hipStream_t)stream;
@@ -1108,7 +1110,7 @@ int lic360_cconv16_ec_list(void *stream, const lic360_conv_plan *p, const float 
 }
 LIC360_API int lic360_cconv16_ec(void *stream, const lic360_conv_plan *p, const float *x, const float *packed16, const float *bias,
                                  const float *act, const float *residual, float *out, int n, int h, int w, int nb, int x_mod, int *ctr) {
-    return lic360_cconv16_ec_list(stream, p, x, packed16, bias, act, residual, out, n, h, w, nb, x_mod, ctr, nullptr, nullptr, 0);
+    return lic360_cconv16_ec_list(stream, p, x, packed16, bias, act, residual, out, n, h, w, nb, x_mod, ctr, nullptr, nullptr, 0, lic360_process_switches().ec_gbk);
 }
 
 // Last layer of the latent entropy model fused with the CDF-table build (SURVEY.md §7 `k_cconv_ec_last_gmm`; replaces the last
@@ -1121,14 +1123,14 @@ LIC360_API int lic360_cconv16_ec(void *stream, const lic360_conv_plan *p, const 
 // NOT written -- all its symbols are masked, their records are (0, 0): the caller clears `rec` before a launch with a list.
 int lic360_cconv16_ec_tables_list(void *stream, const lic360_conv_plan *p, const float *x, const float *packed16, const float *bias,
                                   const float *code, const float *mask, const int *pidx_dev, const int *plane_start_dev,
-                                  void *rec, int images, int h, int w, int *ctr, const int *list, const int *cnt, int cap) {
+                                  void *rec, int images, int h, int w, int *ctr, const int *list, const int *cnt, int cap, int gbk) {
     ARG_CHECK(p && conv16_ok(p) && p->cin == 4 && p->cout == 3 && x && packed16 && bias && code && mask && pidx_dev && plane_start_dev && rec &&
-              ctr && images > 0 && h > 0 && w > 0);
+              ctr && gbk > 0 && images > 0 && h > 0 && w > 0);
     ARG_CHECK((list != nullptr) == (cnt != nullptr) && (!list || cap > 0));
     C16Args a;
     a.x = x; a.packed = packed16; a.bias = bias; a.act = nullptr; a.residual = nullptr; a.out = nullptr; a.ctr = ctr;
     a.npb = images; a.x_mod = 3 * images; a.N = images;
-    if (c16_fill_args(a, p, h, w, C16_FTPT)) return 2;
+    if (c16_fill_args(a, p, h, w, gbk, C16_FTPT)) return 2;
     a.n_gb = (p->ngroup + C16_FGPB - 1) / C16_FGPB;                         // five groups per block (lic360_conv16_pack_tables)
     a.code = code; a.mask = mask; a.pidx = pidx_dev; a.plane_start = plane_start_dev; a.rec = (uint2 *)rec;
     a.list = list; a.cnt = cnt; a.list_cap = cap;
@@ -1141,5 +1143,6 @@ int lic360_cconv16_ec_tables_list(void *stream, const lic360_conv_plan *p, const
 LIC360_API int lic360_cconv16_ec_tables(void *stream, const lic360_conv_plan *p, const float *x, const float *packed16, const float *bias,
                                         const float *code, const float *mask, const int *pidx_dev, const int *plane_start_dev,
                                         void *rec, int images, int h, int w, int *ctr) {
-    return lic360_cconv16_ec_tables_list(stream, p, x, packed16, bias, code, mask, pidx_dev, plane_start_dev, rec, images, h, w, ctr, nullptr, nullptr, 0);
+    return lic360_cconv16_ec_tables_list(stream, p, x, packed16, bias, code, mask, pidx_dev, plane_start_dev, rec, images, h, w, ctr, nullptr, nullptr, 0,
+                                         lic360_process_switches().ec_gbk);
 }

@@ -28,6 +28,7 @@
 
 #include "cconv_tree.h"
 #include "need.h"
+#include "codec_switches.h"
 
 #define C4_COLS 68                       // 64 positions + 2*2 halo
 #define C4_WSLOTS 128                    // weight slots per step (>= 25*cin), 4 floats each
@@ -93,15 +94,17 @@ LIC360_API int lic360_conv4_pack(void *stream, const lic360_conv_plan *p, const 
 // ------------------------------------------------------------------------------------------------ DC4
 #include "cconv4v6_dc.inc"
 
-// mode: bit 1 = no several-samples-per-wave packing, bits 2-3 = task granularity (4: one group per task always, 8: never; 0: by task count),
-// bit 4 = the first layer keeps one net per task.
-// Internal entry (hidden visibility) so that the fused codec passes the switches it read ONCE at create time.
+// sw: the schedule switches dc_pack (several samples per wave), dc_gstep (task granularity: 1 one group per task always, 3 never, 0 by task count) and
+// dc_nets (the first layer's three nets in one task per image); LIC360_NOPACK, LIC360_DC_GSTEP and LIC360_DC_NONETS, read when a codec is created
+// (codec_switches.h).  tests/test_gpu_codec.py runs each of them against the oracle: test_fused_codec_decode_task_granularity the two granularities,
+// test_decode_schedule_switches_where_they_change_the_schedule the other two at shapes where they change the launch.
+// Internal entry (hidden visibility): the fused codec passes its own switches.
 int lic360_cconv4_dc_plane_mode(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
-                                const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod, int mode) {
+                                const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod,
+                                const lic360_switches &sw) {
     ARG_CHECK(p && conv4_ok(p) && x && packed4 && bias && out && n > 0 && nb > 0 && n % nb == 0 && x_mod > 0 && x_mod <= n);
     if (psum < 0 || psum >= h + w + p->ngroup - 2) return 0;
-    return launch_cconv4v6_dc((hipStream_t)stream, p, x, packed4, bias, act, residual, out, n, h, w, nb, psum, x_mod, (mode & 2) != 0,
-                              (mode >> 2) & 3, (mode & 16) != 0);
+    return launch_cconv4v6_dc((hipStream_t)stream, p, x, packed4, bias, act, residual, out, n, h, w, nb, psum, x_mod, !sw.dc_pack, sw.dc_gstep, !sw.dc_nets);
 }
 int lic360_cconv4_dc_plane_list(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
                                 const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod,
@@ -110,16 +113,10 @@ int lic360_cconv4_dc_plane_list(void *stream, const lic360_conv_plan *p, const f
     if (psum < 0 || psum >= h + w + p->ngroup - 2) return 0;
     return launch_cconv4v6_dc_list((hipStream_t)stream, p, x, packed4, bias, act, residual, out, n, h, w, nb, psum, x_mod, (const uint4 *)list, cnt, cap);
 }
-// LIC360_NOPACK / LIC360_DC_GSTEP force the schedule variants (both are tested against the oracle), LIC360_DC_NONETS the first layer's one-net-per-task
-// form (A/B runs); read once per process, not per launch
-int lic360_dc4_env_mode(void) {
-    const char *gsm = getenv("LIC360_DC_GSTEP");                     // "1": one group per task always, "3": never (default: by task count)
-    return (getenv("LIC360_NOPACK") ? 2 : 0) | (gsm && gsm[0] == '1' ? 4 : (gsm && gsm[0] == '3' ? 8 : 0)) | (getenv("LIC360_DC_NONETS") ? 16 : 0);
-}
+// without a codec: the switches of the process, read once (codec_switches.h: lic360_process_switches)
 LIC360_API int lic360_cconv4_dc_plane(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
                                       const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod) {
-    static const int mode = lic360_dc4_env_mode();
-    return lic360_cconv4_dc_plane_mode(stream, p, x, packed4, bias, act, residual, out, n, h, w, nb, psum, x_mod, mode);
+    return lic360_cconv4_dc_plane_mode(stream, p, x, packed4, bias, act, residual, out, n, h, w, nb, psum, x_mod, lic360_process_switches());
 }
 
 // Floats to allocate for `planes` activation planes (samples x channels) of the padded decode-order layout (lic360_dc4_layout): the

@@ -15,6 +15,7 @@
 #include "lic360_exact_math.h"
 #include "gmm_tables.h"
 #include "need.h"
+#include "codec_switches.h"
 #include "rate.h"
 #include <vector>
 #include <cstring>
@@ -133,8 +134,9 @@ struct lic360_codec {
     NetWeights w{"codec", "lic360_codec_set_layer", 3};   // the GMM's weight, delta and mean nets; with use4, xpack[0]: the leaf-resident
                                                // (4x4x1 MFMA) decode-order packing, xpack[1]: the 16x16x4 encode-order one (csrc/cconv16_kernels.hip)
     bool use4;                                 // the nets' shapes fit the specialised kernels (4x4x1 decode order, 16x16x4 encode order with the last layer
-                                               // fused with the CDF tables); otherwise -- or under LIC360_FUSED_CONV=16 -- the generic kernels of cconv_kernels.hip
-    int dc_mode = 0;                           // schedule switches of the decode kernel (LIC360_NOPACK, LIC360_DC_GSTEP), read from the environment once, at create
+                                               // fused with the CDF tables); otherwise -- or under LIC360_FUSED_CONV=16, read when a codec is created
+                                               // (codec_switches.h) -- the generic kernels of cconv_kernels.hip
+    lic360_switches sw;                        // this codec's environment switches, read when it is created (codec_switches.h) and never again
     DevBuf<int> e_ctr;                         // 8 task counters of the encode kernel
     std::vector<int> h_idx, h_pidx, h_plane_start;
     DevBuf<int> d_idx, d_pidx, d_plane_start;
@@ -150,14 +152,14 @@ struct lic360_codec {
     // Dead-cone skip (round 6, need.h): outputs no coded symbol can observe are not computed -- per-layer need maps from the mask, compacted task lists
     // for the encode-order kernels (layers 1..11), per-plane task records for the decode-order kernel (layers 1..11; batches of >= 16 images with
     // 8 | batch on images of at most 128 rows -- below that a list could only drop whole three-group tasks, which almost never happens, and the decode
-    // would have to wait for the whole importance map instead of running behind it).  LIC360_NOSKIP=1 (read at create) turns it off;
-    // LIC360_DC_NOTALL=1 keeps the decode-order lists to images of at most 64 rows.
+    // would have to wait for the whole importance map instead of running behind it).  LIC360_NOSKIP=1 turns it off, LIC360_DC_NOTALL=1 keeps the
+    // decode-order lists to images of at most 64 rows; both read when a codec is created (codec_switches.h).
     bool skip = false;
     // What keeps a skipped cell finite: every encode that skips clears the two ping-pong buffers that layers 1..10 write sparsely, for
     // its 3 B samples, so a stale cell it reads is a zero or a value of THIS call -- at most 11 layers deep.  Without it a dead cell that a live
     // task computes can read, in a tile that this call skips, what a LATER layer of the previous call left there, and the next call reads the
-    // result: a recurrence of about eight layers per call with the weights' gain (tests/skip_age_cases.py).  LIC360_NOCLEAR=1 (read at create)
-    // leaves the clear out, for A/B runs; lic360_codec_debug_fill suppresses it once, so that the next encode sees the fill.
+    // result: a recurrence of about eight layers per call with the weights' gain (tests/skip_age_cases.py).  LIC360_NOCLEAR=1 (read when a codec is
+    // created, codec_switches.h) leaves the clear out, for A/B runs; lic360_codec_debug_fill suppresses it once, so that the next encode sees the fill.
     bool clear = true, filled = false;
     DevBuf<unsigned> dbg;                      // lic360_codec_debug_absmax's 15 maxima (float bits) and 15 counts
     DevBuf<signed char> need, need_d, tmax;
@@ -172,7 +174,7 @@ struct lic360_codec {
     // host thread does 21 / 29 ns per symbol.  With few images per call (<= coder_auto_max = 8) the serial phases therefore run on host threads:
     // encode -- records D2H, one thread per image, bitstreams H2D; decode -- per plane the packed tables go to pinned memory, one persistent thread per
     // image decodes its symbols, a GPU kernel waits for them on polled flags (no API call, no stream synchronisation per plane).
-    int coder_mode = 2;                        // 0 device, 1 host, 2 auto (host when B <= coder_auto_max); LIC360_HOST_CODER=0|1 overrides at create
+    int coder_mode = 2;                        // 0 device, 1 host, 2 auto (host when B <= coder_auto_max); LIC360_HOST_CODER=0|1, read when a codec is created (codec_switches.h), overrides
     int coder_auto_max = 8;                    // (16 images per stream on three streams lose: config 4 as written 52 -> 36 Mpixel/s, config 5 47 -> 18 -- every plane then waits for its slowest host thread while the GPU coder of one stream hides behind the other streams' convolutions)
     // optional per-kernel-class timing (bench.py's instrumented pass; off in the timed region): HIP event pairs around
     // every launch of a class, recorded on the launch stream
@@ -953,9 +955,9 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     ARG_CHECK(out && ngroup > 0 && ngroup < 128 && h > 0 && w > 0 && h < 4096 && w < 4096 && max_batch > 0);
     std::unique_ptr<lic360_codec> c(new lic360_codec());
     c->G = ngroup; c->H = h; c->W = w; c->maxB = max_batch; c->S = h + w - 1; c->P = h + w + ngroup - 2; c->HW = h * w;
+    const lic360_switches &sw = c->sw = lic360_switches_env();        // the only look at the environment in this codec's life
     if (c->w.create(ngroup, ngroup, ngroup * 4, ngroup * 3)) return 1;
-    const char *force = getenv("LIC360_FUSED_CONV");                  // "16" forces the generic 16x16x4 kernels (the fall-back path, kept tested)
-    c->use4 = !(force && force[0] == '1' && force[1] == '6');
+    c->use4 = !sw.conv16;                                             // (the generic 16x16x4 kernels: the fall-back path, kept tested)
     for (const PlanPtr &p : c->w.plan) c->use4 = c->use4 && lic360_conv4_supported(p.get()) && lic360_conv16_supported(p.get());
     if (scan_order(h, w, c->h_idx, c->h_pidx, c->d_idx, c->d_pidx)) return 1;
     c->h_plane_start.resize(c->P + 1);
@@ -974,7 +976,6 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     c->sk = DcLayout::plain(h, w);
     if (c->use4 && lic360_dc4_layout(h, w, &c->sk.rows, &c->sk.pitch, &c->sk.row0, &c->sk.col0)) return 1;
     const size_t B = max_batch, G = ngroup, HW = c->HW, SK = (size_t)c->sk.plane(), TAIL = (size_t)lic360_conv4_buffer_floats(0, 1, h, w) - SK;   // slack for the band fetches of the last plane
-    c->dc_mode = lic360_dc4_env_mode();
     // encode order: 16x16x4 MFMA kernels on zero-haloed NCHW planes, or plain NCHW for the generic kernels
     if (c->use4) { if (lic360_ec16_layout(h, w, &c->e_hp, &c->e_wp)) return 1; c->e_off = 2; }
     else { c->e_hp = h; c->e_wp = w; c->e_off = 0; }
@@ -987,9 +988,10 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
     for (int p = 0; p < c->P; ++p) c->tab_pitch = std::max(c->tab_pitch, c->h_plane_start[p + 1] - c->h_plane_start[p]);
     c->tab_pitch = (c->tab_pitch + 63) / 64 * 64;
     if (c->d_tab.alloc(2 * B * (size_t)c->tab_pitch)) return 1;                 // two uint4 per symbol (dec_pack8)
-    if (const char *hc = getenv("LIC360_HOST_CODER")) c->coder_mode = hc[0] == '0' ? 0 : (hc[0] == '1' ? 1 : 2);
-    c->skip = c->use4 && !getenv("LIC360_NOSKIP");
-    c->clear = !getenv("LIC360_NOCLEAR");
+    if (sw.coder_mode >= 0) c->coder_mode = sw.coder_mode;
+    c->skip = c->use4 && sw.skip;
+    c->clear = sw.clear;
+    c->ecl.gbk = sw.ec_gbk;                                                      // (the encode kernels' task order, with or without lists)
     if (c->skip) {
         const size_t S = c->S, nt = (size_t)((h + 3) / 4) * ((w + 15) / 16);
         if (c->need.alloc(B * NEED_LAYERS * HW) || c->need_d.alloc(B * NEED_LAYERS * S * h) || c->tmax.alloc(B * NEED_LAYERS * nt) ||
@@ -999,24 +1001,19 @@ LIC360_API int lic360_codec_create(int ngroup, int h, int w, int max_batch, lic3
         if ((size_t)c->ecl.cap < cap11) c->ecl.cap = (int)cap11;
         if (c->ecl_list.alloc((size_t)NEED_LAYERS * 8 * c->ecl.cap) || c->ecl_cnt.alloc((size_t)NEED_LAYERS * 8)) return 1;
         c->ecl.list = c->ecl_list; c->ecl.cnt = c->ecl_cnt;
-        // decode-order lists: latents of at most 128 rows (taller than a wave: up to three records per sample, need.h; LIC360_DC_NOTALL=1, read here,
-        // keeps those on the row-segment kernels -- the A/B switch of the tall lists)
-        const int h_max = getenv("LIC360_DC_NOTALL") ? 64 : DCL_MAX_H;
+        // decode-order lists: latents of at most 128 rows (taller than a wave: up to three records per sample, need.h; LIC360_DC_NOTALL=1 keeps those
+        // on the row-segment kernels -- the A/B switch of the tall lists)
+        const int h_max = sw.dc_tall ? DCL_MAX_H : 64;
         if (h <= h_max && max_batch % 8 == 0 && max_batch >= 16 && max_batch <= 512 && ngroup <= 72) {
             c->dcl.P = c->P;
             c->dcl.cap = (int)(((G + 2) / 3) * 3 * (B / 8) * DCL_WAVES_PER_WINDOW(h));
             if (c->dcl_list.alloc((size_t)NEED_LAYERS * c->P * 8 * c->dcl.cap) || c->dcl_cnt.alloc((size_t)NEED_LAYERS * c->P * 8)) return 1;
             c->dcl.list = c->dcl_list; c->dcl.cnt = c->dcl_cnt;
-            // order of the lists (need.h; LIC360_DC_ORDER, read here like the switch above): "1" block major as in round 6, "1p" that order with the
-            // placement pass, "2" / "4" / "8" blocks in groups of that many, placed.  Default 8: the only order whose headline beat the block-major one by
-            // three times the spread of the runs (DESIGN 4.6 "List order")
-            c->dcl.nb = 8; c->dcl.place = true;
-            if (const char *e = getenv("LIC360_DC_ORDER")) {
-                if (!lic360_dc_order_parse(e, &c->dcl.nb, &c->dcl.place)) {
-                    lic360_set_error("LIC360_DC_ORDER=%s: expected 1, 1p, 2, 4 or 8", e);
-                    return 1;
-                }
-            }
+            // order of the lists (need.h; LIC360_DC_ORDER): "1" block major as in round 6, "1p" that order with the placement pass, "2" / "4" / "8" blocks
+            // in groups of that many, placed.  Default 8: the only order whose headline beat the block-major one by three times the spread of the runs
+            // (DESIGN 4.6 "List order").  A value that is no order fails the create here, where the lists it would order exist, and nowhere else.
+            if (sw.dc_order_bad) { lic360_set_error("%s", lic360_dc_order_message(sw).c_str()); return 1; }
+            c->dcl.nb = sw.dc_nb; c->dcl.place = sw.dc_place; c->dcl.balance = sw.balance;
         }
         HIP_TRY(hipMemset(c->stats, 0, 2 * NEED_LAYERS * NEED_STAT_G * sizeof(unsigned long long)));
     }
@@ -1080,17 +1077,16 @@ static int codec_records(void *stream, lic360_codec *c, const float *code, const
         lic360_conv_plan *p = nw.at(layer);
         const int x_mod = layer ? 3 * B : B;
         const bool fused = c->use4 && layer == 11;        // last layer + CDF tables in one kernel: the nets' outputs never reach HBM (no y buffer, no k_enc_tables)
-        if (c->use4 && c->skip && layer > 0) {
-            const int *list = c->ecl.list + (size_t)layer * 8 * c->ecl.cap, *cnt = c->ecl.cnt + layer * 8;
-            if (fused)
-                return lic360_cconv16_ec_tables_list(stream, p, xin, nw.xpack[1][11], nw.bias[11], code, mask, c->d_pidx, c->d_plane_start, c->e_rec, B, H, W,
-                                                     c->e_ctr, list, cnt, c->ecl.cap);
-            return lic360_cconv16_ec_list(stream, p, xin, nw.xpack[1][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, x_mod, c->e_ctr,
-                                          list, cnt, c->ecl.cap);
-        }
-        if (fused) return lic360_cconv16_ec_tables(stream, p, xin, nw.xpack[1][11], nw.bias[11], code, mask, c->d_pidx, c->d_plane_start, c->e_rec, B, H, W, c->e_ctr);
-        if (c->use4) return lic360_cconv16_ec(stream, p, xin, nw.xpack[1][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, x_mod, c->e_ctr);
-        return lic360_cconv_ec_ex(stream, p, xin, nw.packed[layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, x_mod);
+        if (!c->use4) return lic360_cconv_ec_ex(stream, p, xin, nw.packed[layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, x_mod);
+        // the layer's live tasks under the skip, or every task (no list); either way in blocks of this codec's gbk, the one its lists are built with
+        const bool live = c->skip && layer > 0;
+        const int *list = live ? c->ecl.list + (size_t)layer * 8 * c->ecl.cap : nullptr, *cnt = live ? c->ecl.cnt + layer * 8 : nullptr;
+        const int cap = live ? c->ecl.cap : 0;
+        if (fused)
+            return lic360_cconv16_ec_tables_list(stream, p, xin, nw.xpack[1][11], nw.bias[11], code, mask, c->d_pidx, c->d_plane_start, c->e_rec, B, H, W,
+                                                 c->e_ctr, list, cnt, cap, c->ecl.gbk);
+        return lic360_cconv16_ec_list(stream, p, xin, nw.xpack[1][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, x_mod, c->e_ctr,
+                                      list, cnt, cap, c->ecl.gbk);
     };
     auto ec = [&](int layer, const float *xin, const float *res, float *dst) -> int {
         // a skipped (tile, group block) of the fused last layer holds masked symbols only: their records are (0, 0) and nobody writes them
@@ -1214,7 +1210,7 @@ static int codec_decode_impl(void *stream, lic360_codec *c, const uint8_t *bytes
             return lic360_cconv4_dc_plane_list(stream, pl, xin, nw.xpack[0][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, p, x_mod,
                                                c->dcl.list + li * c->dcl.cap, c->dcl.cnt + li, c->dcl.cap);
         }
-        if (c->use4) return lic360_cconv4_dc_plane_mode(stream, pl, xin, nw.xpack[0][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, p, x_mod, c->dc_mode);
+        if (c->use4) return lic360_cconv4_dc_plane_mode(stream, pl, xin, nw.xpack[0][layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3, p, x_mod, c->sw);
         return lic360_cconv_dc_plane_ex(stream, pl, xin, nw.packed[layer], nw.bias[layer], nw.act[layer], res, dst, 3 * B, H, W, 3,
                                         c->d_idx, c->d_pidx, pih, p, x_mod, 1);
     };

@@ -23,9 +23,10 @@ static const int LIC360_REC_PAD = 4;       // records readable past the end (sof
 #define I144_C0 2                               // zero columns before th = 0
 
 // internal entries shared between translation units (hidden visibility; not part of include/lic360_hip.h)
+struct lic360_switches;                         // codec_switches.h
 int lic360_cconv4_dc_plane_mode(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
-                                const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod, int mode);
-int lic360_dc4_env_mode(void);
+                                const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod,
+                                const lic360_switches &sw);
 int lic360_cconv_dc_plane_strided(void *stream, const lic360_conv_plan *p, const float *x, const float *packed, const float *bias,
                                   const float *act, const float *residual, float *out, int n, int h, int w, int nb,
                                   const int *idx_dev, const int *plane_idx_dev, const int *plane_idx_host, int psum, int x_mod,
@@ -34,10 +35,10 @@ int lic360_cconv_dc_plane_strided(void *stream, const lic360_conv_plan *p, const
 // (layer, plane)'s task records
 int lic360_cconv16_ec_list(void *stream, const lic360_conv_plan *p, const float *x, const float *packed16, const float *bias,
                            const float *act, const float *residual, float *out, int n, int h, int w, int nb, int x_mod, int *ctr,
-                           const int *list, const int *cnt, int cap);
+                           const int *list, const int *cnt, int cap, int gbk);
 int lic360_cconv16_ec_tables_list(void *stream, const lic360_conv_plan *p, const float *x, const float *packed16, const float *bias,
                                   const float *code, const float *mask, const int *pidx_dev, const int *plane_start_dev,
-                                  void *rec, int images, int h, int w, int *ctr, const int *list, const int *cnt, int cap);
+                                  void *rec, int images, int h, int w, int *ctr, const int *list, const int *cnt, int cap, int gbk);
 int lic360_cconv4_dc_plane_list(void *stream, const lic360_conv_plan *p, const float *x, const float *packed4, const float *bias,
                                 const float *act, const float *residual, float *out, int n, int h, int w, int nb, int psum, int x_mod,
                                 const void *list, const int *cnt, int cap);

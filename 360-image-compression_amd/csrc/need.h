@@ -114,14 +114,6 @@ __host__ __device__ inline void dcl_place_round(const int *cost, int n, int W, i
 __host__ __device__ inline int dcl_place_order(int it, int n, int W) { return n % W == 0 ? it : (it == 0 ? (n - 1) / W : it - 1); }
 __host__ __device__ inline int dcl_max(const int *v, int n) { int m = 0; for (int i = 0; i < n; ++i) m = v[i] > m ? v[i] : m; return m; }
 
-// units per block of the encode kernels' task order (c16_fill_args and the list builder must agree): 16 measured best without lists (DESIGN 4.1 a);
-// LIC360_EC_GBK overrides it for A/B runs
-#include <cstdlib>
-static inline int lic360_ec_gbk(void) {
-    static const int v = [] { const char *e = getenv("LIC360_EC_GBK"); const int x = e ? atoi(e) : 0; return x > 0 && x <= 4096 ? x : 16; }();
-    return v;
-}
-
 // internal entries (hidden visibility)
 // need [B][12][H][W] and its diagonal-major copy need_d [B][12][H+W-1][H] (cell (y, x) at [(y + x) * H + y]; cells outside the image: -1),
 // tile maxima tmax [B][12][nty][ntx] over the encode kernels' 4 x 16 tiles; all int8
@@ -130,6 +122,8 @@ struct lic360_ec_lists {                   // encode order: compact lists of the
     int *list = nullptr;                   // [12][8][cap] entries u | tile mask << 28 in launch order
     int *cnt = nullptr;                    // [12][8]
     int cap = 0;
+    int gbk = 16;                          // units per block of the encode kernels' task order: the builder numbers the tasks with it and the codec hands the same
+                                           // field to the launchers that decode them (c16_fill_args).  16 measured best without lists (DESIGN 4.1 a)
 };
 int lic360_ec_lists_build(void *stream, const signed char *tmax, int B, int G, int H, int W, const lic360_ec_lists &l, unsigned long long *stats);
 struct lic360_dc_lists {                   // decode order
@@ -138,12 +132,6 @@ struct lic360_dc_lists {                   // decode order
     int cap = 0, P = 0;
     int nb = 1;                            // blocks per emission group (1: block major, the order of round 6)
     bool place = false;                    // the placement pass after the XCD balancing
+    bool balance = true;                   // the XCD balancing pass
 };
-// LIC360_DC_ORDER: "1" (nb 1, no placement), "1p" (nb 1, placed), "2" / "4" / "8" (groups of nb blocks, placed); 0 = not one of these
-static inline int lic360_dc_order_parse(const char *e, int *nb, bool *place) {
-    const int v = e && e[0] >= '1' && e[0] <= '8' ? e[0] - '0' : 0;
-    if (!v || (v & (v - 1)) || (e[1] && !(v == 1 && e[1] == 'p' && !e[2]))) return 0;
-    *nb = v; *place = v > 1 || e[1] == 'p';
-    return 1;
-}
 int lic360_dc_lists_build(void *stream, const signed char *need_d, int B, int G, int H, int W, const lic360_dc_lists &l, unsigned long long *stats);

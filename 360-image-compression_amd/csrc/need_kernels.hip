@@ -183,10 +183,10 @@ __global__ __launch_bounds__(256) void k_ec_tasks(const EcListArgs a) {
 // hidden layers 1..10 (four groups per block, four tiles per task, the 3 B samples of the stacked nets) and the fused last layer (five groups,
 // two tiles, B images); the first layer (cin = 1) has next to nothing to skip and keeps its full task list
 int lic360_ec_lists_build(void *stream, const signed char *tmax, int B, int G, int H, int W, const lic360_ec_lists &l, unsigned long long *stats) {
-    ARG_CHECK(tmax && l.list && l.cnt && B > 0);
+    ARG_CHECK(tmax && l.list && l.cnt && B > 0 && l.gbk > 0);
     const int ntx = (W + 15) / 16, ntiles = ntx * ((H + 3) / 4);
     EcListArgs a;
-    a.tmax = tmax; a.list = l.list; a.cnt = l.cnt; a.stats = stats; a.cap = l.cap; a.npb = B; a.ntiles = ntiles; a.gbk = lic360_ec_gbk();
+    a.tmax = tmax; a.list = l.list; a.cnt = l.cnt; a.stats = stats; a.cap = l.cap; a.npb = B; a.ntiles = ntiles; a.gbk = l.gbk;
     a.l0 = 1; a.N = 3 * B; a.gpb = 4; a.tpt = 4; a.n_chunks = (ntiles + 3) / 4; a.n_gb = (G + 3) / 4;
     ARG_CHECK(((a.N + 7) / 8) * a.n_chunks * a.n_gb <= l.cap && ((a.N + 7) / 8) * a.n_chunks * a.n_gb < (1 << 28));
     hipLaunchKernelGGL(k_ec_tasks, dim3(8, 10), dim3(256), 0, (hipStream_t)stream, a);
@@ -405,8 +405,7 @@ int lic360_dc_lists_build(void *stream, const signed char *need_d, int B, int G,
     ARG_CHECK(l.nb >= 1 && l.nb <= DCL_MAX_NB);
     hipLaunchKernelGGL(k_dc_tasks, dim3(8, l.P, NEED_LAYERS - 1), dim3(128), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK();
-    static const bool balance = !getenv("LIC360_NOBALANCE");                // (A/B switch of the XCD balancing pass)
-    if (balance) {
+    if (l.balance) {
         hipLaunchKernelGGL(k_dc_balance, dim3(l.P, NEED_LAYERS - 1), dim3(64), 0, (hipStream_t)stream, a);
         LAUNCH_CHECK();
     }

@@ -553,7 +553,7 @@ int lic360_impcodec_rate_last(void *stream, lic360_impcodec *codec, int b, unsig
 /* Where the serial arithmetic-coder phases of the fused latent codec run.  The reference runs its coder on the CPU (extension/coder.cpp:70-113, called per
  * plane from test/lic360_demo.py:139-140,234); the fused codec keeps it on the GPU (one wave per image) where many images per call hide it, and hands it
  * to host threads -- records D2H / per-plane tables through pinned memory, polled flags -- when a call holds few images.  mode 0: device, 1: host
- * (<= 64 images per call), 2 (default): host for calls of at most 8 images.  LIC360_HOST_CODER=0|1 sets the mode at create.  Bitstreams are identical. */
+ * (<= 64 images per call), 2 (default): host for calls of at most 8 images.  LIC360_HOST_CODER=0|1, read when a codec is created (codec_switches.h), sets the mode.  Bitstreams are identical. */
 int lic360_codec_set_coder(lic360_codec *codec, int mode);
 
 /* ---- dead-cone skip of the fused latent codec (round 6; csrc/need.h) -------------------------------------------------------------
@@ -578,7 +578,7 @@ int lic360_dcl_order_layout(int n_blocks, const int *g0, const int *nrec, int ng
 /* enable > 0: the following encodes / decodes count what they execute (0: stop; < 0: leave as it is).  out (host, 2 * 12 * 64 values, may be NULL; reading clears):
  * [0][layer][group block] live (tile, group block) pairs of the encode-order launches (64 positions x the block's groups, per sample),
  * [1][layer][group] cells the decode-order launches stored.  *skip_active_out (may be NULL): 0 the codec does not skip (generic kernels or
- * LIC360_NOSKIP), 1 encode order only, 2 both orders (decode order: batches of >= 16 images, 8 | batch, h <= 128; LIC360_DC_NOTALL=1 at create: h <= 64). */
+ * LIC360_NOSKIP), 1 encode order only, 2 both orders (decode order: batches of >= 16 images, 8 | batch, h <= 128; LIC360_DC_NOTALL=1, read when a codec is created (codec_switches.h): h <= 64). */
 int lic360_codec_skip_stats(lic360_codec *codec, int enable, unsigned long long *out, int *skip_active_out);
 /* test hooks: every interior cell of the codec's activation buffers <- value (finite); what the last encode / decode scheduled
  * (which 0: need maps, 1 / 2: encode-order list counts / entries, 3 / 4: decode-order list counts / records; see csrc/codec_fused.hip) */

@@ -1,6 +1,7 @@
 """What the transforms' GPU tests share, each piece once: the `lic` fixture, host <-> device one-liners, the float64 -> fp32 reference with its cache, the
 whole-output and frame comparisons, the sentinel-filled call, the two-stream repeat loop, the past-4 GiB scaffolding, the recorder of lic360.sconv* calls, the
-count-rule switch, the block-parameter jitter and the bf16x1 criteria.  A plain module, imported like util.py and the *_cases.py files; which entry point, pack
+count-rule switch, the block-parameter jitter and the bf16x1 criteria -- and, for the fused latent codec's tests, the one way to create a codec under its
+environment switches (codec_under).  A plain module, imported like util.py and the *_cases.py files; which entry point, pack
 and keywords a form takes stays in the form's own test file, which hands a closure `call(out)` to the helpers here.  tests/test_gpu_support_cpu.py checks the
 checkers on CPU tensors."""
 import functools
@@ -29,6 +30,31 @@ def dev(a):
 
 def host(t):
     return t.detach().cpu().numpy()
+
+
+# ---- the fused latent codec under its environment switches
+# every switch a codec reads when it is created: the names of csrc/codec_switches.h's table, in its order (tests/test_codec_switches_cpu.py compares)
+SWITCH_NAMES = ("LIC360_FUSED_CONV", "LIC360_HOST_CODER", "LIC360_NOSKIP", "LIC360_NOCLEAR", "LIC360_DC_NOTALL", "LIC360_DC_ORDER", "LIC360_NOPACK",
+                "LIC360_DC_GSTEP", "LIC360_DC_NONETS", "LIC360_EC_GBK", "LIC360_NOBALANCE")
+
+
+def codec_under(G, H, W, B, layers, **switches):
+    """a FusedCodec of max_batch B with the layers loaded, created under exactly the given switches (LIC360_NOSKIP=1, LIC360_DC_ORDER="1p"; None: not
+    set) and no other one, whatever the process's environment holds -- which is left as it was"""
+    import os
+    from lic360_fused import FusedCodec
+    assert set(switches) <= set(SWITCH_NAMES), sorted(set(switches) - set(SWITCH_NAMES))
+    old = {k: os.environ.pop(k, None) for k in SWITCH_NAMES}
+    os.environ.update({k: str(v) for k, v in switches.items() if v is not None})
+    try:
+        fc = FusedCodec(G, H, W, max_batch=B)
+    finally:
+        for k in SWITCH_NAMES:
+            os.environ.pop(k, None)
+            if old[k] is not None:
+                os.environ[k] = old[k]
+    fc.load_layers(layers)
+    return fc
 
 
 _REFS = {}                                                                  # key -> fp32 reference, for the callers that asked to keep it

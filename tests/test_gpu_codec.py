@@ -7,7 +7,7 @@ import torch
 
 import ref_codec as rc
 from util import latent
-from gpu_support import dev  # noqa: F401
+from gpu_support import codec_under, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -113,7 +113,7 @@ def test_fused_codec_matches_oracle(G, H, W, B, seed, coder):
 @pytest.mark.parametrize("G,H,W,B,seed", [(6, 8, 12, 2, 21), (4, 66, 10, 1, 22)])
 def test_fused_codec_generic_kernel_fallback(monkeypatch, G, H, W, B, seed):
     """The fall-back path for net shapes the specialised kernels do not cover -- the generic 16x16x4 kernels of cconv_kernels.hip on plain
-    NCHW / diagonal-major planes with the separate table kernel -- forced with LIC360_FUSED_CONV=16 (read once, when a codec is created):
+    NCHW / diagonal-major planes with the separate table kernel -- forced with LIC360_FUSED_CONV=16 (read when a codec is created, csrc/codec_switches.h):
     the same bitstreams, exact decode."""
     from lic360_fused import FusedCodec
     rng = np.random.default_rng(seed)
@@ -130,22 +130,58 @@ def test_fused_codec_generic_kernel_fallback(monkeypatch, G, H, W, B, seed):
     assert np.array_equal(fc.decode(streams, dev(mask)).cpu().numpy(), code * mask)
 
 
-@pytest.mark.parametrize("gstep", ["1", "3"])
+@pytest.mark.parametrize("switch", [("LIC360_DC_GSTEP", "1"), ("LIC360_DC_GSTEP", "3"), ("LIC360_NOPACK", "1"), ("LIC360_DC_NONETS", "1")],
+                         ids=["1", "3", "nopack", "nonets"])
 @pytest.mark.parametrize("G,H,W,B,seed", [(6, 8, 12, 3, 41), (48, 8, 16, 2, 42), (7, 64, 12, 1, 43), (4, 66, 10, 1, 44)])
-def test_fused_codec_decode_task_granularity(monkeypatch, gstep, G, H, W, B, seed):
+def test_fused_codec_decode_task_granularity(switch, G, H, W, B, seed):
     """decode-order conv tasks of three groups (throughput) or of one group (latency mode, picked automatically for few samples):
-    LIC360_DC_GSTEP forces either; both decode the oracle's bitstreams exactly"""
-    from lic360_fused import FusedCodec
+    LIC360_DC_GSTEP forces either and decodes the oracle's bitstreams exactly.  LIC360_NOPACK and LIC360_DC_NONETS decode them too, but these four
+    shapes are too small for either to change a launch (1 to 3 images: latency mode, or two row segments of one image): the test below runs those two
+    where they do"""
+    _decode_of_the_oracles_bytes(G, H, W, B, seed, dict([switch]))
+
+
+def _decode_of_the_oracles_bytes(G, H, W, B, seed, switches):
     rng = np.random.default_rng(seed)
     layers = rc.make_main_params(2000 + seed, G)
     items = [latent(rng, G, H, W) for _ in range(B)]
     code = np.concatenate([it[0] for it in items], 0)
     mask = np.concatenate([it[1] for it in items], 0)
     ref = [rc.encode_main(code[i:i + 1], mask[i:i + 1], layers, G) for i in range(B)]
-    monkeypatch.setenv("LIC360_DC_GSTEP", gstep)
-    fc = FusedCodec(G, H, W, max_batch=B)
-    fc.load_layers(layers)
+    fc = codec_under(G, H, W, B, layers, **switches)
     assert np.array_equal(fc.decode(ref, dev(mask)).cpu().numpy(), code * mask)
+    return fc
+
+
+def _schedule_without_switches(G, H, B, gstep3=False):
+    """what the decode kernel's launcher (csrc/cconv4v6_dc.inc: dc6_schedule, dc6_build_tape, dc6_schedule_nets) decides for a codec's 3 B samples when no
+    list is in play: (three groups per task, row segments, a tape is tried, the last row segment packs two samples, the first layer merges its nets)"""
+    nseg = 1 if H <= 64 else 1 + (H - 62 + 59) // 60
+    three = gstep3 or 3 * B * ((G + 2) // 3) > 128 or nseg > 1
+    c = max([t for t in range(2, 7) if B % 8 == 0 and (B // 8) % t == 0] or [0])
+    tape = three and nseg == 1 and c >= 2 and B % (8 * c) == 0 and (G + 2) // 3 <= 16
+    pack0 = three and nseg > 1 and B % 16 == 0 and H >= 28 and 60 * (nseg - 1) + 2 >= H - 26
+    return three, nseg, tape, pack0, three and nseg == 1
+
+
+@pytest.mark.parametrize("G,H,W,B,seed,switches", [
+    (6, 28, 40, 24, 45, {"LIC360_NOPACK": 1, "LIC360_NOSKIP": 1}),          # 8 | images: tapes of 3 without the switch (every layer: no lists)
+    (4, 66, 10, 16, 46, {"LIC360_NOPACK": 1, "LIC360_NOSKIP": 1}),          # two row segments, the last one packs two samples without the switch
+    (48, 8, 16, 3, 47, {"LIC360_DC_NONETS": 1}),                            # 9 samples x 16 blocks: throughput mode by itself
+    (6, 8, 12, 3, 48, {"LIC360_DC_NONETS": 1, "LIC360_DC_GSTEP": 3}),       # throughput mode forced on a small net
+], ids=["nopack-tape", "nopack-segment", "nonets-g48", "nonets-gstep3"])
+def test_decode_schedule_switches_where_they_change_the_schedule(G, H, W, B, seed, switches):
+    """LIC360_NOPACK and LIC360_DC_NONETS at shapes where the launcher, left alone, packs several samples into a wave (a tape, or the last row segment
+    of a tall image) or runs the first layer's three nets in one task: under the switch the codec takes the other schedule and still decodes the
+    oracle's bitstreams exactly.  The shapes' preconditions are restated from the launcher and asserted, so that a shape at which a switch changes
+    nothing cannot stand here.  (Without lists: LIC360_NOSKIP for batches that would build them; the first layer never runs over a list.)"""
+    three, nseg, tape, pack0, nets = _schedule_without_switches(G, H, B, gstep3="LIC360_DC_GSTEP" in switches)
+    if "LIC360_NOPACK" in switches:
+        assert tape or pack0
+    if "LIC360_DC_NONETS" in switches:
+        assert nets
+    fc = _decode_of_the_oracles_bytes(G, H, W, B, seed, switches)
+    assert fc.skip_active() == (0 if "LIC360_NOSKIP" in switches else 1)
 
 
 @pytest.mark.parametrize("cpg,nsym,H,W,B,seed", [(8, 49, 8, 12, 3, 31), (144, 49, 4, 6, 1, 32), (16, 10, 32, 10, 2, 33)])

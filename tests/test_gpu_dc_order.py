@@ -13,27 +13,11 @@ import pytest
 
 import dc_order_cases as cases
 from util import make_main_params
-from gpu_support import dev  # noqa: F401
+from gpu_support import codec_under, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 POISON = 1.0e10
-
-
-def _codec(G, H, W, B, layers, order):
-    """a FusedCodec created under LIC360_DC_ORDER = order (None: unset), the process's own environment left as it was"""
-    from lic360_fused import FusedCodec
-    old = os.environ.pop("LIC360_DC_ORDER", None)
-    if order is not None:
-        os.environ["LIC360_DC_ORDER"] = order
-    try:
-        fc = FusedCodec(G, H, W, max_batch=B)
-    finally:
-        os.environ.pop("LIC360_DC_ORDER", None)
-        if old is not None:
-            os.environ["LIC360_DC_ORDER"] = old
-    fc.load_layers(layers)
-    return fc
 
 
 def lists_of(fc, shape):
@@ -77,7 +61,7 @@ def order_one(shape):
 def run(shape, order):
     G, H, W, B = shape
     layers = make_main_params(cases.weight_seed(shape), G)
-    fc = _codec(G, H, W, B, layers, order)
+    fc = codec_under(G, H, W, B, layers, LIC360_DC_ORDER=order)
     assert fc.skip_active() == 2
     got = []
     for second in (False, True):
@@ -127,11 +111,41 @@ def test_unset_is_the_default_and_a_wrong_value_is_refused():
     G, H, W, B = shape
     layers = make_main_params(cases.weight_seed(shape), G)
     code, mask = cases.batch(shape)
-    fc = _codec(G, H, W, B, layers, None)
+    fc = codec_under(G, H, W, B, layers)
     fc.decode(fc.encode(dev(code), dev(mask)), dev(mask))
-    fd = _codec(G, H, W, B, layers, cases.DEFAULT_ORDER)
+    fd = codec_under(G, H, W, B, layers, LIC360_DC_ORDER=cases.DEFAULT_ORDER)
     fd.decode(fd.encode(dev(code), dev(mask)), dev(mask))
     assert digest(*lists_of(fc, shape)) == digest(*lists_of(fd, shape))
     for bad in ("3", "0", "16", "4p", "p", ""):
         with pytest.raises(Lic360Error):
-            _codec(G, H, W, B, layers, bad)
+            codec_under(G, H, W, B, layers, LIC360_DC_ORDER=bad)
+
+
+def test_the_balancing_pass_belongs_to_the_codec():
+    """LIC360_NOBALANCE is read when a codec is created and is that codec's: a default codec and then, in the same process, one under LIC360_NOBALANCE=1, both
+    at order 1 (no placement).  Images 3 and 11 -- the home list of XCD 3 -- are fully masked, so that list starts empty and the balancing pass fills it
+    from the others: the default codec holds records away from their home list n % 8, the other codec none; the records are the same multisets and both
+    decode the first codec's streams exactly."""
+    shape = cases.GPU_SHAPES[0]
+    G, H, W, B = shape
+    layers = make_main_params(cases.weight_seed(shape), G)
+    code, mask = cases.batch(shape)
+    mask = mask.copy()
+    mask[3] = mask[11] = 0.0
+    got = []
+    streams = None
+    for switches in ({}, {"LIC360_NOBALANCE": 1}):
+        fc = codec_under(G, H, W, B, layers, LIC360_DC_ORDER="1", **switches)
+        assert fc.skip_active() == 2
+        if streams is None:
+            streams = fc.encode(dev(code), dev(mask))
+        out = fc.decode(streams, dev(mask)).cpu().numpy()                   # (raises unless err is 0 for every image)
+        assert int(fc.err[:B].abs().sum().item()) == 0
+        assert np.array_equal(out, code * mask)
+        cnt, rec = lists_of(fc, shape)
+        away = sum(int(((rec[l, p, x, :cnt[l, p, x], 0] >> 10) % 8 != x).sum()) for l in range(1, 12) for p in range(cnt.shape[1]) for x in range(8))
+        got.append((multisets(cnt, rec), away, int(cnt[1:].sum())))
+    (balanced, moved, n), (plain, stayed, m) = got
+    assert moved > 0, "the masks load the XCDs unevenly: the balancing pass of the default codec moves records"
+    assert stayed == 0, "without the balancing pass every record is in its home list"
+    assert n == m > 0 and balanced == plain

@@ -19,28 +19,11 @@ import pytest
 
 import dc_tall_cases as cases
 from util import latent_smooth, make_main_params
-from gpu_support import dev  # noqa: F401
+from gpu_support import codec_under, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 POISON = 1.0e10
-
-
-def _codec(G, H, W, B, layers, **env):
-    """a FusedCodec created under the given LIC360_* switches (they are read at create), the process's own environment left as it was"""
-    from lic360_fused import FusedCodec
-    names = ("LIC360_NOSKIP", "LIC360_DC_NOTALL")
-    old = {k: os.environ.pop(k, None) for k in names}
-    os.environ.update({k: "1" for k in env if env[k]})
-    try:
-        fc = FusedCodec(G, H, W, max_batch=B)
-    finally:
-        for k in names:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-    fc.load_layers(layers)
-    return fc
 
 
 class Run(object):
@@ -61,13 +44,13 @@ def run_of(shape):
     r.want = cases.golden_streams(shape, r.code, r.mask)                    # the CPU oracle's bytes (tools/gen_golden_dc_tall.py)
     n_or = len(r.want)
     if n_or < B:                                                            # the other images: today's row-segment kernels, which existing tests pin to the oracle
-        ref = _codec(G, H, W, B, layers, LIC360_NOSKIP=1)
+        ref = codec_under(G, H, W, B, layers, LIC360_NOSKIP=1)
         assert ref.skip_active() == 0
         rest = ref.encode(dev(r.code), dev(r.mask))
         assert rest[:n_or] == r.want
         r.want = r.want + rest[n_or:]
         del ref
-    fc = _codec(G, H, W, B, layers)
+    fc = codec_under(G, H, W, B, layers)
     r.active = fc.skip_active()
     fc.debug_fill(POISON)
     r.streams = fc.encode(dev(r.code), dev(r.mask))
@@ -184,7 +167,7 @@ def test_full_size_tall_golden_with_poisoned_buffers():
     c14, m14 = cases.batch(G, H, W, 14, 555)
     code16 = np.concatenate([code, c14[:8], code, c14[8:]], 0)
     mask16 = np.concatenate([mask, m14[:8], mask, m14[8:]], 0)
-    fc = _codec(G, H, W, 16, layers)
+    fc = codec_under(G, H, W, 16, layers)
     assert fc.skip_active() == 2
     fc.debug_fill(POISON)
     t0 = time.time()
@@ -202,10 +185,10 @@ def test_the_switch_keeps_tall_latents_on_the_row_segment_kernels():
     G, H, W, B = shape
     r = run_of(shape)
     layers = make_main_params(cases.weight_seed(shape), G)
-    fc = _codec(G, H, W, B, layers, LIC360_DC_NOTALL=1)
+    fc = codec_under(G, H, W, B, layers, LIC360_DC_NOTALL=1)
     assert fc.skip_active() == 1
     assert fc.encode(dev(r.code), dev(r.mask)) == r.want
     assert np.array_equal(fc.decode(r.want, dev(r.mask)).cpu().numpy(), r.code * r.mask)
-    short = _codec(G, 64, W, B, layers, LIC360_DC_NOTALL=1)
+    short = codec_under(G, 64, W, B, layers, LIC360_DC_NOTALL=1)
     assert short.skip_active() == 2, "the switch is about latents taller than 64 rows only"
-    assert _codec(G, 130, W, B, layers).skip_active() == 1, "past 128 rows: row segments, as before"
+    assert codec_under(G, 130, W, B, layers).skip_active() == 1, "past 128 rows: row segments, as before"

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from util import latent, latent_smooth, make_main_params
-from gpu_support import dev  # noqa: F401
+from gpu_support import codec_under, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -76,21 +76,6 @@ def test_need_maps_match_reachability(G, H, W, kind):
     assert np.array_equal(out.cpu().numpy()[0].astype(np.int64), brute_need(mask[0] > 0.5))
 
 
-def _codec(G, H, W, B, layers, skip=True):
-    from lic360_fused import FusedCodec
-    old = os.environ.pop("LIC360_NOSKIP", None)
-    if not skip:
-        os.environ["LIC360_NOSKIP"] = "1"
-    try:
-        fc = FusedCodec(G, H, W, max_batch=B)
-    finally:
-        os.environ.pop("LIC360_NOSKIP", None)
-        if old is not None:
-            os.environ["LIC360_NOSKIP"] = old
-    fc.load_layers(layers)
-    return fc
-
-
 def _batch(G, H, W, B, seed, n_iid=2):
     cs, ms = [], []
     for i in range(B):
@@ -111,7 +96,7 @@ def test_full_size_smooth_goldens_with_poisoned_buffers():
         layers = make_main_params(int(g["weight_seed"]), G)
         c15, m15 = _batch(G, H, W, 15, 777)
         code16, mask16 = np.concatenate([code, c15], 0), np.concatenate([mask, m15], 0)
-        fc = _codec(G, H, W, 16, layers)
+        fc = codec_under(G, H, W, 16, layers)
         assert fc.skip_active() == 2
         fc.debug_fill(POISON)
         streams = fc.encode(dev(code16), dev(mask16))
@@ -125,10 +110,10 @@ def test_full_size_smooth_goldens_with_poisoned_buffers():
 def test_skip_changes_no_byte(G, H, W, B):
     code, mask = _batch(G, H, W, B, 4242 + H)
     layers = make_main_params(99 + G, G)
-    ref = _codec(G, H, W, B, layers, skip=False)
+    ref = codec_under(G, H, W, B, layers, LIC360_NOSKIP=1)
     assert ref.skip_active() == 0
     want = ref.encode(dev(code), dev(mask))
-    fc = _codec(G, H, W, B, layers)
+    fc = codec_under(G, H, W, B, layers)
     assert fc.skip_active() == 2
     fc.debug_fill(POISON)
     fc.skip_stats(True)
@@ -155,7 +140,7 @@ def _need_of(mask):
 def test_task_lists_cover_the_live_cells_exactly_once(G, H, W, B):
     code, mask = _batch(G, H, W, B, 31337)
     layers = make_main_params(5, G)
-    fc = _codec(G, H, W, B, layers)
+    fc = codec_under(G, H, W, B, layers)
     streams = fc.encode(dev(code), dev(mask))
     fc.decode(streams, dev(mask))
     need, _ = fc.debug_lists(0)
@@ -206,7 +191,12 @@ def test_task_lists_cover_the_live_cells_exactly_once(G, H, W, B):
     live = np.arange(G)[None, None, :, None, None] <= need.transpose(1, 0, 2, 3)[:, :, None]      # [12, B, G, H, W]
     for net in range(3):
         assert not (live[1:] & (stored[1:, net * B:(net + 1) * B] == 0)).any()
-    # ---- encode order: hidden layers (4 groups x 4 tiles) and the fused last layer (5 groups x 2 tiles)
+    _encode_lists_cover_the_live_tasks(fc, need, G, H, W, B, gbk=16)
+
+
+def _encode_lists_cover_the_live_tasks(fc, need, G, H, W, B, gbk):
+    """encode order, hidden layers (4 groups x 4 tiles) and the fused last layer (5 groups x 2 tiles): the codec's lists, decoded as the kernels decode a
+    task number under blocks of gbk units, hold exactly the live (sample, tile, group block) set of the need maps, each once and in launch order"""
     ecnt, ecap = fc.debug_lists(1)
     elist, _ = fc.debug_lists(2)
     ecnt, elist = ecnt.reshape(12, 8), elist.reshape(12, 8, ecap)
@@ -217,7 +207,7 @@ def test_task_lists_cover_the_live_cells_exactly_once(G, H, W, B):
     tmax = tmax.reshape(B, 12, nty, 4, ntx, 16).max((3, 5)).reshape(B, 12, ntiles)
     for l in range(1, 12):
         gpb, tpt, N = (5, 2, B) if l == 11 else (4, 4, 3 * B)
-        n_gb, n_chunks, gbk = (G + gpb - 1) // gpb, (ntiles + tpt - 1) // tpt, 16
+        n_gb, n_chunks = (G + gpb - 1) // gpb, (ntiles + tpt - 1) // tpt
         seen = np.zeros((N, ntiles, n_gb), np.int32)
         for x in range(8):
             ns_x = (N - x + 7) >> 3
@@ -239,3 +229,22 @@ def test_task_lists_cover_the_live_cells_exactly_once(G, H, W, B):
                         seen[n, tile0 + t, gb] += 1
         want = tmax[np.arange(N) % B, l][:, :, None] >= (np.arange(n_gb) * gpb)[None, None, :]
         assert np.array_equal(seen, want.astype(np.int32))
+
+
+def test_the_encode_block_size_belongs_to_the_codec():
+    """LIC360_EC_GBK is read when a codec is created and is that codec's: a default codec and then, in the same process, one under LIC360_EC_GBK=4.  A hidden
+    layer's list of one XCD has 12 units of 3 group blocks here, so blocks of 16 and of 4 number its tasks differently.  Same bytes (the default codec's, which
+    the test above pins to the need maps and others to the oracle); the first codec's lists are the live set under blocks of 16, the second's under blocks of 4."""
+    G, H, W, B = 12, 16, 24, 16
+    code, mask = _batch(G, H, W, B, 31337)
+    layers = make_main_params(5, G)
+    need = _need_of(mask)
+    first = codec_under(G, H, W, B, layers)
+    want = first.encode(dev(code), dev(mask))
+    second = codec_under(G, H, W, B, layers, LIC360_EC_GBK=4)
+    got = second.encode(dev(code), dev(mask))
+    assert first.encode(dev(code), dev(mask)) == want and got == want
+    for fc, gbk in ((first, 16), (second, 4)):
+        assert np.array_equal(fc.debug_lists(0)[0].reshape(B, 12, H, W).astype(np.int64), need)
+        _encode_lists_cover_the_live_tasks(fc, need, G, H, W, B, gbk)
+    assert not np.array_equal(first.debug_lists(2)[0], second.debug_lists(2)[0]), "blocks of 4 are another task order at this shape"
