@@ -24,7 +24,9 @@ The first stage's stride-2 layers (3 input channels: no 16-channel chunk, and bo
 shapes, small maps and every recording (training) pass are library work (torch -> MIOpen); native around them:
 sphere pad / trim / cut-edge / pixel-shuffle / importance map / quantiser kernels and the one-pass GDN (csrc/gdn_kernels.hip).
 EntropyNet2 is the reference's training-time entropy model of the latent (train/EntropyNet2.py:8-74) on MaskConv2, DropGrad and GmmRateLoss: its
-`rate(x, mask)` is the rate term of the training loss, on the fused GMM rate loss with head="fused"."""
+`rate(x, mask)` is the rate term of the training loss, on the fused GMM rate loss with head="fused".
+EntropyNet3 is the reference's training-time entropy model of the importance map (test/model_zoo.py:275-300) on MaskConv2, DropGrad and CeRateLoss: its
+`rate(x)` is the importance map's rate term, on the fused cross-entropy rate loss with head="fused"."""
 import collections
 import functools
 import types
@@ -572,6 +574,36 @@ class EntropyNet2(nn.Module):
     def rate(self, x, mask=None):
         logit, sigma, mean, tx = self._nets(x)
         return self.head(logit, sigma, mean, tx, mask)
+
+
+class EntropyNet3(nn.Module):
+    """The training-time entropy model of the importance map (reference test/model_zoo.py:275-300): one group-causal net gives every symbol
+    nvalue + 1 logits.  Same submodule and parameter names (`net.N...`), so lic360_codec.cast_imp_entropy_parameter maps its state_dict (under
+    `imp_ent.`) onto the importance-map drivers; the gradient stops at the input (DropGrad(True)), which the net sees as x / ((nvalue - 1) / 2) - 1.
+    The parameter-free tail of the reference's net (ContextReshape) and its CrossEntropyLoss live in CeRateLoss.
+    forward(x) -> the reference's per-symbol loss_vec [n * ngroups * h * w], always on the library composition.
+    rate(x) -> CeRateLoss's (nats [n] float64, symbols [n] int64) on the route `head` names ("library" or "fused")."""
+    def __init__(self, ngroups, cpn, nvalue=48, device_id=0, head="library"):
+        super().__init__()
+        from lic360_operator import MaskConv2, DropGrad, CeRateLoss
+        self.drop = DropGrad(True)
+        self.net = nn.Sequential(MaskConv2(ngroups, 1, cpn, 5, False, device_id), nn.PReLU(ngroups * cpn),
+                                 *[EntropyResidualBlock(ngroups, cpn, device_id) for _ in range(5)],
+                                 MaskConv2(ngroups, cpn, nvalue + 1, 5, True, device_id))
+        self.scale = (nvalue - 1.) / 2.
+        self.head = CeRateLoss(ngroups, nvalue + 1, head, device_id)
+
+    def _net(self, x):
+        x = self.drop(x)
+        return self.net(x / self.scale - 1.), x
+
+    def forward(self, x):
+        logit, label = self._net(x)
+        return self.head.loss_vec(logit, label)
+
+    def rate(self, x):
+        logit, label = self._net(x)
+        return self.head(logit, label)
 
 
 def transform_gflops(channels=192, code_channels=192, h=512, w=1024):

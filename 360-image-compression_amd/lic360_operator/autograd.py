@@ -132,3 +132,22 @@ class GmmRateFn(torch.autograd.Function):
         logit, sigma, mean, label, mask = ctx.saved_tensors
         d = lic360.gmm_rate_backward(logit, sigma, mean, label, mask, _c(g_nats.to(torch.float32)), need_label=ctx.need_label)
         return d[0], d[1], d[2], d[3], None
+
+
+class CeRateFn(torch.autograd.Function):
+    """(logit, label) -> (nats [n] float64, symbols [n] int64, invalid [n] int64) of lic360.ce_rate; saves the inputs only.  backward:
+    lic360.ce_rate_backward recomputes every symbol from them; the label never gets a gradient."""
+    @staticmethod
+    def forward(ctx, logit, label):
+        import lic360
+        nats, symbols, invalid = lic360.ce_rate(logit, label)
+        ctx.save_for_backward(logit, label)
+        ctx.mark_non_differentiable(symbols, invalid)
+        return nats, symbols, invalid
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_nats, g_symbols, g_invalid):
+        import lic360
+        logit, label = ctx.saved_tensors
+        return lic360.ce_rate_backward(logit, label, _c(g_nats.to(torch.float32))), None

@@ -13,6 +13,8 @@ metric / bookkeeping utilities, and two wrappers of out-of-scope native ops) and
                  not a name of the reference
   GmmRateLoss    the rate term of the training loss from the three entropy nets' raw outputs: one fused native pass each way (lic360.gmm_rate,
                  autograd.GmmRateFn), or ContextReshape + softmax + ReLU + EntropyGmm + mask + sum; not a name of the reference
+  CeRateLoss     the rate term of the importance map's entropy model from its net's raw output: one fused native pass each way (lic360.ce_rate,
+                 autograd.CeRateFn), or ContextReshape + cross_entropy + sum; not a name of the reference
   MaskConv2      torch conv2d over a weight masked by lic360.MaskConstrainOp (the training-time form of the context conv)
 """
 import math
@@ -327,6 +329,73 @@ class GmmRateLoss(nn.Module):
             from .autograd import GmmRateFn
             return GmmRateFn.apply(logit, sigma, mean, label, mask)
         return self._library(logit, sigma, mean, label, mask, return_map)
+
+
+class CeRateLoss(nn.Module):
+    """The rate term of the importance map's entropy model from the raw output of its net (reference test/model_zoo.py:275-300: ContextReshape,
+    then CrossEntropyLoss over nclass classes): forward(logit, label, return_map=False) -> (nats [n] float64, symbols [n] int64), plus the
+    per-symbol loss [n, g, h, w] with return_map.  logit [n, ngroup * nclass, h, w]; label [n, ngroup, h, w] holding class indices; symbol
+    (n, g, y, x) reads channel g * nclass + i; its class is the label truncated, as the reference's `.type(torch.LongTensor)` does.
+    route "library": the composition the reference trains with on this package's modules -- ContextReshape,
+    torch.nn.functional.cross_entropy(..., reduction="none") (`loss_vec`), a per-image sum in float64; symbols counts every symbol.  It takes
+    tensors of any placement and dtype (they are computed in fp32 on `device_id`, the results come back to the inputs' device); a label outside
+    0 .. nclass - 1 raises through torch.
+    route "fused": fp32 contiguous device tensors take one native pass -- lic360.ce_rate without a recording pass, autograd.CeRateFn (which saves
+    the inputs only and runs lic360.ce_rate_backward) with one.  A label outside (-1, nclass), NaN included, costs nothing, gets a zero gradient
+    and is counted out of symbols; with check_labels (the default) the call then raises IndexError, which costs one synchronisation;
+    check_labels=False skips the check.  CPU tensors, other dtypes, strided tensors and a recording call with return_map=True take the library
+    route.  The attribute can be switched between calls.
+    The default is "library": measured at 1 x 64 x 128, 49 classes (tools/ce_rate_probe.py), the fused route's medians are 1.1 - 1.2 x lower at batch 8
+    and batch 1, forward and forward + backward, but only two of the four differences exceed the two min - max spreads added -- both routes are bound
+    by the host at 0.05 - 0.25 ms per call, the fused entries alone take at most 0.016 + 0.017 ms of it -- so the rule that made "fused" GmmRateLoss's
+    default does not."""
+    ROUTES = ("library", "fused")
+
+    def __init__(self, ngroup, nclass, route="library", device_id=0, check_labels=True):
+        super().__init__()
+        from .quantize import ContextReshape
+        from .autograd import recording
+        self.ngroup, self.nclass, self.route, self.check_labels = int(ngroup), int(nclass), self._route(route), bool(check_labels)
+        self.device_id = device_id if isinstance(device_id, int) else list(device_id)[0]
+        self._recording = recording
+        self.reshape = ContextReshape(self.ngroup, device_id)
+
+    @classmethod
+    def _route(cls, route):
+        if route not in cls.ROUTES:
+            raise ValueError("CeRateLoss: route must be one of %s, got %r" % (", ".join(repr(r) for r in cls.ROUTES), route))
+        return route
+
+    def loss_vec(self, logit, label):
+        """the reference's per-symbol loss_vec [n * ngroup * h * w] of fp32 device tensors (the library composition)"""
+        return F.cross_entropy(self.reshape(logit), label.reshape(-1).to(torch.int64), reduction="none")
+
+    def _library(self, logit, label, return_map):
+        dev = logit.device if logit.is_cuda else torch.device("cuda:%d" % self.device_id)
+        f = lambda t: t.to(device=dev, dtype=torch.float32)
+        vec = self.loss_vec(f(logit), f(label))
+        n = label.shape[0]
+        symbols = torch.full((n,), label[0].numel() if n else 0, dtype=torch.int64, device=logit.device)
+        nats = vec.view(n, -1).double().sum(1).to(logit.device)
+        return (nats, symbols, vec.view(label.shape).to(logit.device)) if return_map else (nats, symbols)
+
+    def forward(self, logit, label, return_map=False):
+        if label.dim() != 4 or label.shape[1] != self.ngroup or logit.dim() != 4 or logit.shape[1] != self.ngroup * self.nclass or \
+                (logit.shape[0],) + tuple(logit.shape[2:]) != (label.shape[0],) + tuple(label.shape[2:]):
+            raise ValueError("CeRateLoss takes logit [n, %d, h, w] and label [n, %d, h, w]" % (self.ngroup * self.nclass, self.ngroup))
+        native = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == logit.device for t in (logit, label)) and label.numel() > 0
+        recording = self._recording(logit)
+        if self._route(getattr(self, "route", "library")) == "fused" and native and not (recording and return_map):
+            import lic360
+            if not recording:
+                out = lic360.ce_rate(logit, label, self.nclass, self.ngroup, return_map=return_map)
+            else:
+                from .autograd import CeRateFn
+                out = CeRateFn.apply(logit, label)
+            if getattr(self, "check_labels", True) and int(out[2].sum()):
+                raise IndexError("CeRateLoss: %d labels lie outside 0 .. %d" % (int(out[2].sum()), self.nclass - 1))
+            return (out[0], out[1]) + tuple(out[3:])
+        return self._library(logit, label, return_map)
 
 
 class _MaskConstrainFn(torch.autograd.Function):

@@ -360,6 +360,29 @@ int lic360_gmm_rate_backward(void *stream, const float *logit, const float *sigm
                              const float *grad_nats, int n, int g, int h, int w, int ng, float *d_logit, float *d_sigma, float *d_mean,
                              float *d_label);
 
+/* Fused cross-entropy rate loss (no reference kernel: the importance map's entropy model, test/model_zoo.py:275-300, runs ContextReshape and
+ * CrossEntropyLoss over nvalue + 1 classes).  logit [n][g*k][h][w] fp32: the net's raw output; label [n][g][h][w] fp32 holding class indices.
+ * Symbol (n, g, y, x) reads channel g*k + i, i < k (1 <= k <= 64), and is valid iff label > -1.0f && label < (float)k (so NaN is invalid); its
+ * class is c = (int)label, truncated (-0.5 -> 0, 3.7 -> 3).  A valid symbol, every operation rounded once in fp32 and nothing contracted:
+ *   m = l_0; for i = 1..k-1: if (m < l_i) m = l_i;   e_i = lic360_expf(l_i - m);   s = 0.0f; s = s + e_i in index order;
+ *   loss = lic360_logf(s) - (l_c - m).
+ * An invalid symbol costs 0, is counted in invalid[n] and not in symbols[n], and gets exact zeros in d_logit whatever its logits hold.
+ * nats [n] double (device): the valid symbols' fp32 losses added in double in a fixed order (no atomics: the same bits on every call); symbols,
+ * invalid [n] int64 (device): the counts; map: NULL or [n][g][h][w] fp32, the per-symbol loss, 0 where invalid.  scratch:
+ * lic360_ce_rate_scratch_bytes(n, g, h, w) bytes of device memory, 8-byte aligned, fully written before it is read (the query returns 0 for
+ * arguments the launch refuses or that hold no symbol; it does not know k and answers for k = 64, so for n*g*h*w above 2^60 / 64 elements it
+ * returns 0 where a launch with a smaller k would still be accepted).
+ * lic360_ce_rate_backward: with t = grad_nats[n] (device, fp32), d_logit [n][g*k][h][w] recomputed from the inputs: p_i = e_i / s,
+ * d_logit_i = (i == c ? p_i - 1.0f : p_i) * t.  Every element of d_logit is written by every call.
+ * Nothing written may overlap anything read.  Both refuse (2) before anything is launched: a negative dimension, k outside 1..64, a null
+ * pointer, a product of the dimensions that leaves the kernels' index types.  n*g*h*w == 0 is no error and launches nothing (pointers may then
+ * be NULL; with n > 0, nats, symbols and invalid are zeroed in the stream). */
+long lic360_ce_rate_scratch_bytes(int n, int g, int h, int w);
+int lic360_ce_rate(void *stream, const float *logit, const float *label, int n, int g, int h, int w, int k, double *nats, long long *symbols,
+                   long long *invalid, float *map, void *scratch);
+int lic360_ce_rate_backward(void *stream, const float *logit, const float *label, const float *grad_nats, int n, int g, int h, int w, int k,
+                            float *d_logit);
+
 /* CppOp: ERP -> Craster parabolic projection.  lic360_cpp_rows fills the per-row column window ws [h][2] = (first column, count) and the
  * row angle theta [h] (host computes, device write); lic360_cpp_forward resamples x [nc][h][w] row by row, zero outside the window; mask
  * (may be NULL) gets 1 inside / 0 outside     extension/CPP.hpp:6-11, CPP_cuda.cu:11-22,46-122 */

@@ -1,0 +1,210 @@
+"""The cases of the fused cross-entropy rate loss (tests/ce_rate_cases.py) without a GPU: the case list reaches every path of the restated launch
+geometry, the restated constants are the source's, the built kernels use no scratch memory, the numpy lic360_logf is the header's bit for bit,
+the reference agrees with the float64 statement of the head within the recorded figures, and every model of a broken kernel changes the
+reference on some case.
+
+The library composition of lic360_operator.CeRateLoss is NOT testable here: `lic360` (and with it lic360_operator) computes nothing without the
+device library's kernels; tests/test_gpu_ce_rate.py holds it against the same float64 statement on the GPU."""
+import os
+import re
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import ce_rate_cases as cc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "360-image-compression_amd")
+SOURCE = os.path.join(PKG, "csrc", "ce_rate_kernels.hip")
+LIB = os.path.join(PKG, "liblic360_hip.so")
+READELF = shutil.which("llvm-readelf") or "/opt/rocm/lib/llvm/bin/llvm-readelf"
+F = np.float32
+
+
+def test_restated_constants_are_the_source_s():
+    text = open(SOURCE).read()
+    m = re.search(r"constexpr int CE_THREADS = (\d+), CE_PER_THREAD = (\d+), CE_CHUNK = CE_THREADS \* CE_PER_THREAD, CE_MAX_K = (\d+), CE_STATIC_K = (\d+);", text)
+    assert m, "the kernel's constants are no longer stated as the cases file restates them"
+    assert tuple(int(v) for v in m.groups()) == (cc.THREADS, cc.PER_THREAD, cc.MAX_K, cc.STATIC_K) and cc.CHUNK == cc.THREADS * cc.PER_THREAD
+    assert "if (k == CE_STATIC_K && vec)" in text                            # the one class count with an instantiation of its own
+    assert text.count("const bool vec = w % 2 == 0 && aligned8(logit) && aligned8(label) && aligned8(") == 2     # the vector form's condition, as form() restates it
+    assert "return ((uintptr_t)p & 7) == 0;" in text and cc.VEC_BYTES == 8 == 4 * cc.PER_THREAD
+    assert "lab[k] > -1.0f && lab[k] < top" in text and "(int)lab[k]" in text   # validity and truncation, as valid_of and reference restate them
+    makefile = open(os.path.join(PKG, "csrc", "Makefile")).read()
+    assert "ce_rate_kernels.hip" in makefile and "-ffp-contract=off" in makefile  # nothing contracted outside the lic360_* functions' own fmaf
+
+
+def test_case_ids_are_unique_and_cases_reach_every_path():
+    assert len(cc.BY_ID) == len(cc.CASES)
+    reached = set()
+    for case in cc.CASES:
+        reached |= cc.reach(case)
+    assert set(cc.REACH) <= reached, sorted(set(cc.REACH) - reached)
+    for family in (cc.REGULAR, cc.EDGE):                                     # both instantiations and both forms in either family
+        assert {(cc.form(c), cc.instantiation(c)) for c in family} == {(f, i) for f in ("vec", "scalar") for i in ("static", "generic")}
+    assert {c.K for c in cc.CASES} == {1, 2, 3, 48, 49, 50, 64}
+    assert {c.G for c in cc.CASES if c.K == cc.STATIC_K} >= {1, 2, 3}
+    assert any(c.N == c.G == c.H == c.W == 1 for c in cc.CASES)
+    assert any(c.offset % 4 and c.W % 4 == 0 and cc.form(c) == "scalar" for c in cc.CASES)
+    for f in ("vec", "scalar"):                                              # a ragged last chunk in each access form, and multi-chunk planes
+        assert any(cc.form(c) == f and cc.chunks(c) > 1 and (c.H * c.W) % cc.CHUNK for c in cc.CASES), f
+    assert max(c.H * c.W for c in cc.CASES) == 2 * cc.CHUNK                  # the largest plane is the two-chunk one
+    for case in cc.EDGE:
+        assert set(cc.inputs(case)["edges"]) == set(cc.EDGE_KINDS), case.id
+
+
+def test_edge_cases_hold_the_values_they_are_for():
+    for case in cc.EDGE:
+        d, ref = cc.inputs(case), cc.reference(case)
+        K, valid = case.K, ref["valid"]
+        L = cc.rows(d["logit"], case)[valid.reshape(-1)]
+        assert np.isfinite(d["logit"]).all(), case.id                                         # no infinities or NaN among the logits
+        assert (L == L[:, :1]).all(1).any(), case.id                                         # equal values
+        top = L.max(1, keepdims=True)
+        assert ((L[:, 0] == top[:, 0]) & ((L == top).sum(1) == 1)).any() and ((L[:, K - 1] == top[:, 0]) & ((L == top).sum(1) == 1)).any(), case.id
+        assert ((L == top).sum(1) == 2).any(), case.id                                       # the maximum tied
+        spread = (top[:, 0] - L.min(1))
+        assert ((spread > 104) & (spread < 1e3)).any() and (np.abs(L) >= 1e29).any(), case.id
+        assert ((spread > 0) & (spread < 1e-44)).any(), case.id                              # a subnormal spread
+        for k in ("map", "d_logit"):
+            assert np.isfinite(ref[k]).all(), (case.id, k)
+        assert not ref["d_logit"][~np.repeat(valid, K, 1)].any() and not ref["map"][~valid].any(), case.id   # exact zeros where invalid
+        assert (np.abs(d["logit"][~np.repeat(valid, K, 1)]) >= 1e30).any(), case.id          # whatever the logits hold there
+    grads = np.concatenate([cc.inputs(c)["grad"] for c in cc.EDGE])
+    assert (grads == 0).any() and (grads < 0).any() and (grads > 0).any()
+
+
+def test_labels_are_counted_as_the_contract_says():
+    for case in cc.CASES:
+        d, ref = cc.inputs(case), cc.reference(case)
+        per = case.G * case.H * case.W
+        assert (ref["symbols"] + ref["invalid"] == per).all(), case.id
+        if case.labels == "classes":
+            assert not ref["invalid"].any(), case.id
+        if case.labels == "image":
+            assert ref["symbols"][1] == 0 and ref["nats"][1] == 0 and not ref["d_logit"][1].any() and ref["symbols"][0] > 0, case.id
+        lab = d["label"]
+        if (lab == F(-0.5)).any():                                            # -0.5 is class 0: its gradient carries the - 1 on channel g K + 0
+            n, g, y, x = np.argwhere(lab == F(-0.5))[0]
+            row = ref["d_logit"][n, g * case.K:(g + 1) * case.K, y, x].astype(np.float64) / float(d["grad"][n]) if d["grad"][n] else None
+            assert row is None or (row[0] <= 0 and (row[1:] >= 0).all()), case.id
+
+
+def test_numpy_logf_is_the_header_s_bit_for_bit(tmp_path):
+    """cc.logf against lic360_logf compiled on the host (tests/ce_logf_host_main.cpp, built with -fsanitize=address,undefined and run as a child
+    process): normal and subnormal inputs, around powers of two and around sqrt 2, and what the kernels feed it -- sums of up to 64 terms"""
+    if shutil.which("g++") is None:
+        pytest.skip("needs g++")
+    rng = np.random.default_rng(11)
+    parts = [np.exp(rng.uniform(-87, 88, 2000)).astype(F), rng.uniform(1, 64, 2000).astype(F),
+             rng.integers(1, 0x00800000, 1000).astype(np.uint32).view(F),                                             # subnormal
+             np.array([0x00000001, 0x007fffff, 0x00800000, 0x7f7fffff, 0x3f800000, 0, 0x80000000, 0xbf800000, 0x7fc00000], np.uint32).view(F)]
+    for e in range(-126, 128, 9):                                                                                    # around powers of two ...
+        base = np.array([np.ldexp(1.0, e)], F).view(np.uint32)[0]
+        parts.append((base + np.arange(-8, 9)).astype(np.uint32).view(F))
+        root = np.array([np.ldexp(float(cc.SQRT2), e)], F).view(np.uint32)[0]                                        # ... and around sqrt 2
+        parts.append((root + np.arange(-8, 9)).astype(np.uint32).view(F))
+    x = np.concatenate(parts)
+    assert len(x) > 5000
+    inp, outp, exe = tmp_path / "in.bin", tmp_path / "out.bin", str(tmp_path / "ce_logf_host_main")
+    x.view("<u4").tofile(str(inp))
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        "-fno-omit-frame-pointer", "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "ce_logf_host_main.cpp"), "-o", exe],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe, str(inp), str(outp)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-500:] + r.stderr[-3000:])
+    want = np.fromfile(str(outp), "<u4")
+    got = cc.logf(x).view(np.uint32)
+    nan = np.isnan(x)
+    assert len(want) == len(got) and np.array_equal(want[~nan], got[~nan]), "%d of %d differ" % (int((want != got)[~nan].sum()), len(x))
+    assert (got[nan] == np.array([-np.inf], F).view(np.uint32)[0]).all() and (want[nan] == got[nan]).all()
+    fin = np.isfinite(cc.logf(x))
+    assert np.allclose(cc.logf(x)[fin], np.log(x[fin].astype(np.float64)), rtol=1e-6, atol=1e-7)                      # and it is a logarithm
+
+
+@pytest.mark.parametrize("case", cc.REGULAR + cc.VALID, ids=lambda c: c.id)
+def test_reference_against_float64(case):
+    """the restatement against the float64 statement, on the regular cases and on their valid-only variants; prints the measurement, holds the
+    recorded tolerances (elements, nats) and holds each within a factor 2 of the measurement"""
+    ref = cc.reference(case)
+    worst, dn = cc.f64_distance(case, ref)
+    print("%s: gradients / loss %.3g, nats %.3g" % (case.id, worst, dn))
+    tol, tol_n = cc.F64_TOL[case.id]
+    assert worst <= tol and dn <= tol_n
+    assert tol <= 2 * worst or worst == 0 == tol
+    assert tol_n <= 2 * dn or dn == 0 == tol_n
+
+
+def test_valid_variants_are_the_cases_with_their_invalid_labels_at_class_0():
+    assert set(cc.F64_TOL) == {c.id for c in cc.REGULAR + cc.VALID} and set(cc.LIBRARY_NATS_TOL) == {c.id for c in cc.VALID}
+    for var in cc.VALID:
+        base = cc.BASE_OF[var.id]
+        d, b = cc.inputs(var), cc.inputs(base)
+        bad = ~cc.valid_of(b["label"], base.K)
+        assert d["logit"] is b["logit"] and d["grad"] is b["grad"] and not d["label"][bad].any() and np.array_equal(d["label"][~bad], b["label"][~bad])
+        ref = cc.reference(var)
+        assert not ref["invalid"].any() and (ref["symbols"] == var.G * var.H * var.W).all()
+        keep = ~np.repeat(bad, var.K, 1)
+        assert np.array_equal(ref["d_logit"][keep], cc.reference(base)["d_logit"][keep])          # the valid symbols are untouched
+
+
+@pytest.mark.parametrize("broken", cc.BROKEN)
+def test_every_broken_model_changes_the_reference(broken):
+    changed = []
+    for case in cc.CASES:
+        ref, bad = cc.reference(case), cc.reference(case, broken)
+        if any(ref[k].tobytes() != bad[k].tobytes() for k in ("map", "symbols", "invalid", "nats", "d_logit")):
+            changed.append(case.id)
+    print(broken, "changes", len(changed), "cases")
+    assert changed, "no case would notice a kernel that is broken this way"
+
+
+# ---- resources of the built kernels (the method of tests/test_kernarg_bytes.py: the gfx950 code objects' notes, read with llvm-readelf)
+KERNELS = ("k_ce_rateILi49ELb1EE", "k_ce_rateILi49ELb0EE", "k_ce_rateILi0ELb1EE", "k_ce_rateILi0ELb0EE", "k_ce_rate_backwardILi49ELb1EE",
+           "k_ce_rate_backwardILi49ELb0EE", "k_ce_rate_backwardILi0ELb1EE", "k_ce_rate_backwardILi0ELb0EE", "k_ce_rate_finish")
+
+
+def _kernel_notes():
+    blob = open(LIB, "rb").read()
+    out = {}
+    for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob):
+        p = m.start()
+        (nent,) = struct.unpack_from("<Q", blob, p + 24)
+        off = p + 32
+        for _ in range(nent):
+            eo, es, ts = struct.unpack_from("<QQQ", blob, off)
+            off += 24
+            triple = blob[off:off + ts].decode()
+            off += ts
+            if "gfx950" not in triple or not es:
+                continue
+            path = "/tmp/lic360_ce_co_%d.elf" % os.getpid()
+            with open(path, "wb") as f:
+                f.write(blob[p + eo:p + eo + es])
+            notes = subprocess.run([READELF, "--notes", path], capture_output=True, text=True, check=True).stdout
+            os.unlink(path)
+            for block in notes.split("  - .agpr_count:")[1:]:
+                name = re.search(r"\.name:\s+(\S+)", block)
+                if name:
+                    out[name.group(1)] = "  - .agpr_count:" + block
+    return out
+
+
+def test_kernels_use_no_scratch_memory_and_do_not_spill():
+    assert os.path.exists(LIB), "the library is not built: the requirement cannot be read, which is a failure, not a skip"
+    assert os.path.exists(READELF), "llvm-readelf (part of the ROCm toolchain that builds the library) is missing"
+    notes = _kernel_notes()
+    for pat in KERNELS:
+        hits = [n for n in notes if pat in n]
+        assert len(hits) == 1, (pat, hits)
+        block = notes[hits[0]]
+        field = lambda key: int(re.search(r"\.%s:\s+(\d+)" % key, block).group(1))
+        print(pat, "vgpr", field("vgpr_count"), "agpr", field("agpr_count"), "sgpr", field("sgpr_count"), "kernarg", field("kernarg_segment_size"))
+        assert field("private_segment_fixed_size") == 0, pat + ": scratch memory"
+        assert field("vgpr_spill_count") == 0 and field("sgpr_spill_count") == 0, pat + ": spills"
+        assert field("vgpr_count") + field("agpr_count") <= 256, pat + ": two waves per SIMD have 256 registers each"
+        assert field("kernarg_segment_size") <= 72 and "hidden_" not in block, pat + ": one struct by value, no implicit arguments"
