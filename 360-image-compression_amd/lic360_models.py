@@ -532,12 +532,12 @@ class CMP_Decoder(nn.Module):
 
 
 class EntropyResidualBlock(nn.Module):
-    """two hidden group-causal 5x5 convolutions with PReLU around a skip (train/EntropyNet2.py:8-21)"""
-    def __init__(self, ngroups, cpn, device_id=0):
+    """two hidden group-causal 5x5 convolutions with PReLU around a skip (train/EntropyNet2.py:8-21); conv: the route of both MaskConv2"""
+    def __init__(self, ngroups, cpn, device_id=0, conv="library"):
         super().__init__()
         from lic360_operator import MaskConv2
-        self.net = nn.Sequential(MaskConv2(ngroups, cpn, cpn, 5, True, device_id), nn.PReLU(ngroups * cpn),
-                                 MaskConv2(ngroups, cpn, cpn, 5, True, device_id), nn.PReLU(ngroups * cpn))
+        self.net = nn.Sequential(MaskConv2(ngroups, cpn, cpn, 5, True, device_id, route=conv), nn.PReLU(ngroups * cpn),
+                                 MaskConv2(ngroups, cpn, cpn, 5, True, device_id, route=conv), nn.PReLU(ngroups * cpn))
 
     def forward(self, x):
         return self.net(x) + x
@@ -549,16 +549,17 @@ class EntropyNet2(nn.Module):
     `mean_net.N...`), so lic360_codec.cast_entropy_parameter maps its state_dict (under `ent.`) onto the codec drivers; the last sigma layer's
     bias starts at 2.  The parameter-free tail of the reference's nets (ContextReshape, Softmax, ReLU) lives in GmmRateLoss.
     forward(x) -> the reference's per-symbol loss_vec [n * ngroups * h * w], always on the library composition.
-    rate(x, mask=None) -> GmmRateLoss's (nats [n] float64, symbols [n] int64) on the route `head` names ("library" or "fused")."""
-    def __init__(self, ngroups, cpn=4, num_gaussian=3, device_id=0, drop_flag=False, head="library"):
+    rate(x, mask=None) -> GmmRateLoss's (nats [n] float64, symbols [n] int64) on the route `head` names ("library" or "fused").
+    conv: the route of every MaskConv2 ("library" or "fused": the native forward and backward of the group-causal convolution)."""
+    def __init__(self, ngroups, cpn=4, num_gaussian=3, device_id=0, drop_flag=False, head="library", conv="library"):
         super().__init__()
         from lic360_operator import MaskConv2, DropGrad, GmmRateLoss
         self.drop = DropGrad(drop_flag)
 
         def net():
-            return nn.Sequential(MaskConv2(ngroups, 1, cpn, 5, False, device_id), nn.PReLU(ngroups * cpn),
-                                 *[EntropyResidualBlock(ngroups, cpn, device_id) for _ in range(5)],
-                                 MaskConv2(ngroups, cpn, num_gaussian, 5, True, device_id))
+            return nn.Sequential(MaskConv2(ngroups, 1, cpn, 5, False, device_id, route=conv), nn.PReLU(ngroups * cpn),
+                                 *[EntropyResidualBlock(ngroups, cpn, device_id, conv) for _ in range(5)],
+                                 MaskConv2(ngroups, cpn, num_gaussian, 5, True, device_id, route=conv))
         self.weight_net, self.mean_net, self.delta_net = net(), net(), net()
         self.delta_net[7].bias.data.fill_(2)
         self.head = GmmRateLoss(ngroups, num_gaussian, head, device_id)
@@ -582,14 +583,15 @@ class EntropyNet3(nn.Module):
     `imp_ent.`) onto the importance-map drivers; the gradient stops at the input (DropGrad(True)), which the net sees as x / ((nvalue - 1) / 2) - 1.
     The parameter-free tail of the reference's net (ContextReshape) and its CrossEntropyLoss live in CeRateLoss.
     forward(x) -> the reference's per-symbol loss_vec [n * ngroups * h * w], always on the library composition.
-    rate(x) -> CeRateLoss's (nats [n] float64, symbols [n] int64) on the route `head` names ("library" or "fused")."""
-    def __init__(self, ngroups, cpn, nvalue=48, device_id=0, head="library"):
+    rate(x) -> CeRateLoss's (nats [n] float64, symbols [n] int64) on the route `head` names ("library" or "fused").
+    conv: the route of every MaskConv2 ("library" or "fused"); under "fused" the first layer's data gradient is never computed (its input needs none)."""
+    def __init__(self, ngroups, cpn, nvalue=48, device_id=0, head="library", conv="library"):
         super().__init__()
         from lic360_operator import MaskConv2, DropGrad, CeRateLoss
         self.drop = DropGrad(True)
-        self.net = nn.Sequential(MaskConv2(ngroups, 1, cpn, 5, False, device_id), nn.PReLU(ngroups * cpn),
-                                 *[EntropyResidualBlock(ngroups, cpn, device_id) for _ in range(5)],
-                                 MaskConv2(ngroups, cpn, nvalue + 1, 5, True, device_id))
+        self.net = nn.Sequential(MaskConv2(ngroups, 1, cpn, 5, False, device_id, route=conv), nn.PReLU(ngroups * cpn),
+                                 *[EntropyResidualBlock(ngroups, cpn, device_id, conv) for _ in range(5)],
+                                 MaskConv2(ngroups, cpn, nvalue + 1, 5, True, device_id, route=conv))
         self.scale = (nvalue - 1.) / 2.
         self.head = CeRateLoss(ngroups, nvalue + 1, head, device_id)
 

@@ -151,3 +151,33 @@ class CeRateFn(torch.autograd.Function):
         import lic360
         logit, label = ctx.saved_tensors
         return lic360.ce_rate_backward(logit, label, _c(g_nats.to(torch.float32))), None
+
+
+class MaskConvFn(torch.autograd.Function):
+    """(x, weight, bias) -> lic360.cconv_forward: the group-causal 5x5 convolution over an already masked weight, bias added, no activation; saves
+    x and the weight.  backward: dx = lic360.cconv_dgrad (the forward kernel on transformed operands; torch's conv2d_input when `dgrad_native` is
+    false), only when x needs it; dw = lic360.cconv_wgrad, exact zeros at masked taps; db = the sum of g over n, h, w."""
+    @staticmethod
+    def forward(ctx, x, weight, bias, ngroup, constrain, dgrad_native):
+        import lic360
+        ctx.ngroup, ctx.constrain, ctx.dgrad_native = ngroup, constrain, dgrad_native
+        ctx.save_for_backward(x, weight)
+        return lic360.cconv_forward(x, weight.detach(), bias.detach(), ngroup, constrain)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        import lic360
+        x, weight = ctx.saved_tensors
+        g = _c(g)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            if ctx.dgrad_native:
+                dx = lic360.cconv_dgrad(g, weight, ctx.ngroup, ctx.constrain)
+            else:
+                dx = torch.nn.grad.conv2d_input(x.shape, weight, g, padding=2)
+        if ctx.needs_input_grad[1]:
+            dw = lic360.cconv_wgrad(x, g, ctx.ngroup, ctx.constrain)
+        if ctx.needs_input_grad[2]:
+            db = g.sum((0, 2, 3))
+        return dx, dw, db, None, None, None

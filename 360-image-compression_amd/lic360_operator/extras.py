@@ -416,17 +416,52 @@ class MaskConv2(nn.Module):
     """The training-time form of the group-causal context convolution (reference lic360_operator/MaskConstrain.py:24-39): a dense
     `conv2d` whose weight is masked by lic360.MaskConstrainOp before every forward.  Same constructor, same parameter names
     (`weight` [c_out*ngroup, c_in*ngroup, k, k], `bias`), so checkpoints interchange; the inference path evaluates the same
-    function with CconvEc / CconvDc."""
-    def __init__(self, ngroup, c_in, c_out, kernel_size, hidden=False, device=0, time_it=False):
+    function with CconvEc / CconvDc.
+    route: "library" (the default) is that dense conv2d, forward and backward.  "fused" masks `weight.data` in place in the same way, then runs
+    autograd.MaskConvFn: the forward is lic360_cconv_ec (the bits CconvEc returns for the same weights), the data gradient the same kernel on
+    transformed operands, the weight gradient lic360_cconv_wgrad, the bias gradient a library sum.  It takes fp32 CUDA tensors, kernel_size 5 and at
+    most 249 channels on either side; anything else runs on the library.  When no plan can be created for the transposed shape, only the data
+    gradient runs on the library (conv2d_input); forward and weight gradient stay native.
+    One visible difference: under "library" `weight.grad` carries the dense gradient at masked taps (the mask is applied to `.data` and never
+    recorded); under "fused" those entries are zero.  A per-element optimiser follows the same trajectory, since masked taps are zeroed again
+    before every forward; a global gradient-norm clip sees a different norm."""
+    ROUTES = ("library", "fused")
+    FUSED_MAX_CHANNELS = 249
+
+    def __init__(self, ngroup, c_in, c_out, kernel_size, hidden=False, device=0, time_it=False, route="library"):
         super().__init__()
         import lic360
+        if route not in self.ROUTES:
+            raise ValueError("MaskConv2: unknown route %r; the routes are %s" % (route, ", ".join(repr(r) for r in self.ROUTES)))
         devs = [device] if isinstance(device, int) else list(device)
-        self.op = {gid: lic360.MaskConstrainOp(6 if hidden else 5, ngroup, gid, time_it) for gid in devs}
+        self.ngroup, self.constrain, self.route = int(ngroup), 6 if hidden else 5, route
+        self.op = {gid: lic360.MaskConstrainOp(self.constrain, ngroup, gid, time_it) for gid in devs}
         self.weight = nn.Parameter(torch.empty((c_out * ngroup, c_in * ngroup, kernel_size, kernel_size), dtype=torch.float32))
         nn.init.kaiming_normal_(self.weight)
         self.bias = nn.Parameter(torch.zeros(c_out * ngroup, dtype=torch.float32))
         self.pad = kernel_size // 2
+        self._dgrad_native = None                                           # decided at the first fused forward
+
+    def _fused(self, x):
+        nout, channel, k, _ = self.weight.shape
+        return self.route == "fused" and k == 5 and max(nout, channel) <= self.FUSED_MAX_CHANNELS and x.dim() == 4 and \
+            all(t.is_cuda and t.dtype == torch.float32 and t.device == x.device for t in (x, self.weight, self.bias))
+
+    def _transposed_plan(self, device):
+        """is there a plan for the data gradient's shape (c_out * ngroup -> c_in * ngroup channels)?"""
+        if self._dgrad_native is None:
+            import lic360
+            try:
+                lic360._cconv_op(self.weight.shape[0], self.ngroup, self.weight.shape[1], self.constrain, device.index)
+                self._dgrad_native = True
+            except lic360.Lic360Error:
+                self._dgrad_native = False
+        return self._dgrad_native
 
     def forward(self, x):
         self.weight.data = _MaskConstrainFn.apply(self.weight.data, self.op)
+        if getattr(self, "route", "library") == "fused" and self._fused(x):
+            from .autograd import MaskConvFn
+            x = x if x.is_contiguous() else x.contiguous()
+            return MaskConvFn.apply(x, self.weight, self.bias, self.ngroup, self.constrain, self._transposed_plan(x.device))
         return nn.functional.conv2d(x, self.weight, self.bias, padding=self.pad)
