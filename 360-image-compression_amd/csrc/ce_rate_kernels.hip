@@ -9,8 +9,8 @@
 //     t + 128 with 4-byte accesses.  KS > 0 (49 in production) keeps a symbol's logits in registers and reads them once: 2 x 49 live values per
 //     thread; KS == 0 takes K (1..64) at run time and streams over the classes in passes that read them again (L1/L2 hits), so no array is indexed
 //     at run time and nothing goes to scratch memory.  A symbol is valid iff label > -1 && label < K (NaN is not), its class (int)label.  Each valid
-//     symbol's fp32 loss is added in double: a thread's cells in index order, the wave by a butterfly, the two waves in index order; total, count and
-//     the count of invalid symbols go to the workgroup's scratch slot.  k_ce_rate_finish adds an image's slots in index order.  No atomics: the same
+//     symbol's fp32 loss is added in double: a thread's cells in index order, then plane_walk.h's workgroup sum (total, count and the count of
+//     invalid symbols to the workgroup's scratch slot) and its finish kernel, which adds an image's slots in index order.  No atomics: the same
 //     bits on every call.
 //   * k_ce_rate_backward<KS, VEC>: the same walk; recomputes the symbol from the inputs and writes d_logit in place of the reads, exact zeros for
 //     invalid symbols.
@@ -19,6 +19,7 @@
 //     loss = lic360_logf(s) - (l_c - m);   backward, t = grad_nats[n]:  p_i = e_i / s,  d_logit_i = (i == c ? p_i - 1 : p_i) * t
 #include "common.h"
 #include "lic360_exact_math.h"
+#include "plane_walk.h"
 
 namespace {
 constexpr int CE_THREADS = 128, CE_PER_THREAD = 2, CE_CHUNK = CE_THREADS * CE_PER_THREAD, CE_MAX_K = 64, CE_STATIC_K = 49;
@@ -28,55 +29,18 @@ struct CeRateArgs {
     const float *logit, *label;
     const float *grad;                                  // backward: grad_nats [N]
     float *out;                                         // forward: the map (or null); backward: d_logit
-    double *slot_nats;                                  // forward: one slot per workgroup
-    long long *slot_sym, *slot_inv;
+    PlaneSlots<2> slots;                                // forward: one slot per workgroup (total, valid symbols, invalid symbols)
     int G, K, HW, chunks;                               // chunks: workgroups per plane
 };
-struct CeFinishArgs {
-    const double *slot_nats;
-    const long long *slot_sym, *slot_inv;
-    double *nats;
-    long long *symbols, *invalid;
-    int per_image;
-};
 
-// this thread's two cells of a plane: which they are, and moving them
+// the plane walk of this loss, which of the thread's cells hold a valid label and its class
 template <bool VEC>
-struct CeCells {
-    int first;                 // VEC: the first of two consecutive cells; else the first of two CE_THREADS apart
-    int hw;
-    __device__ __forceinline__ CeCells(int chunk, int tid, int hw_) : first(chunk * CE_CHUNK + (VEC ? CE_PER_THREAD * tid : tid)), hw(hw_) {}
-    __device__ __forceinline__ bool inside(int k) const { return VEC ? first < hw : first + k * CE_THREADS < hw; }     // (VEC: hw % 2 == 0)
-    __device__ __forceinline__ void load(const float *plane, float (&v)[CE_PER_THREAD]) const {
-        if (VEC) {
-            float2 q = make_float2(0.0f, 0.0f);
-            if (first < hw) q = *(const float2 *)(plane + first);
-            v[0] = q.x; v[1] = q.y;
-        } else {
-#pragma unroll
-            for (int k = 0; k < CE_PER_THREAD; ++k) v[k] = inside(k) ? plane[first + k * CE_THREADS] : 0.0f;
-        }
-    }
-    __device__ __forceinline__ void store(float *plane, const float (&v)[CE_PER_THREAD]) const {
-        if (VEC) {
-            if (first < hw) *(float2 *)(plane + first) = make_float2(v[0], v[1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < CE_PER_THREAD; ++k)
-                if (inside(k)) plane[first + k * CE_THREADS] = v[k];
-        }
-    }
-};
-
-// what a workgroup is: (image, plane, chunk) of its index, the cells of this thread, which of them hold a valid label and its class
-template <bool VEC>
-struct CeWalk {
-    long plane;                // n * G + g
-    int n;
-    CeCells<VEC> cells;
+struct CeWalk : PlaneWalk<CE_THREADS, CE_PER_THREAD, VEC> {
+    using PlaneWalk<CE_THREADS, CE_PER_THREAD, VEC>::plane;
+    using PlaneWalk<CE_THREADS, CE_PER_THREAD, VEC>::cells;
     bool valid[CE_PER_THREAD];
     int cls[CE_PER_THREAD];    // -1 where invalid
-    __device__ __forceinline__ CeWalk(const CeRateArgs &a) : plane(blockIdx.x / a.chunks), n((int)(plane / a.G)), cells(blockIdx.x % a.chunks, threadIdx.x, a.HW) {
+    __device__ __forceinline__ CeWalk(const CeRateArgs &a) : PlaneWalk<CE_THREADS, CE_PER_THREAD, VEC>(a.chunks, a.G, a.HW) {
         float lab[CE_PER_THREAD];
         cells.load(a.label + plane * a.HW, lab);
         const float top = (float)a.K;
@@ -167,8 +131,6 @@ __device__ __forceinline__ void ce_cells_stream(const CeRateArgs &a, const CeWal
 
 template <int KS, bool VEC>
 __global__ __launch_bounds__(CE_THREADS) void k_ce_rate(const CeRateArgs a) {
-    __shared__ double s_nats[CE_THREADS / 64];
-    __shared__ int s_sym[CE_THREADS / 64], s_inv[CE_THREADS / 64];
     const CeWalk<VEC> wk(a);
     const long HW = a.HW;
     float loss[CE_PER_THREAD];
@@ -183,51 +145,13 @@ __global__ __launch_bounds__(CE_THREADS) void k_ce_rate(const CeRateArgs a) {
     }
     if (a.out) wk.cells.store(a.out + wk.plane * HW, loss);                  // the map: 0 where invalid
     double acc = 0.0;
-    int cnt = 0, inv = 0;
+    int cnt[2] = {0, 0};                                                     // valid, invalid
 #pragma unroll
     for (int k = 0; k < CE_PER_THREAD; ++k) {
-        if (wk.valid[k]) { acc += (double)loss[k]; ++cnt; }
-        else if (wk.cells.inside(k)) ++inv;
+        if (wk.valid[k]) { acc += (double)loss[k]; ++cnt[0]; }
+        else if (wk.cells.inside(k)) ++cnt[1];
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_xor(acc, off);
-        cnt += __shfl_xor(cnt, off);
-        inv += __shfl_xor(inv, off);
-    }
-    const int tid = threadIdx.x;
-    if ((tid & 63) == 0) { s_nats[tid >> 6] = acc; s_sym[tid >> 6] = cnt; s_inv[tid >> 6] = inv; }
-    __syncthreads();
-    if (tid == 0) {
-        double tot = s_nats[0];
-        int c = s_sym[0], v = s_inv[0];
-        for (int wv = 1; wv < CE_THREADS / 64; ++wv) { tot += s_nats[wv]; c += s_sym[wv]; v += s_inv[wv]; }
-        a.slot_nats[blockIdx.x] = tot;
-        a.slot_sym[blockIdx.x] = c;
-        a.slot_inv[blockIdx.x] = v;
-    }
-}
-
-__global__ __launch_bounds__(CE_THREADS) void k_ce_rate_finish(const CeFinishArgs a) {
-    __shared__ double s_nats[CE_THREADS];
-    __shared__ long long s_sym[CE_THREADS], s_inv[CE_THREADS];
-    const int tid = threadIdx.x;
-    const long first = (long)blockIdx.x * a.per_image;
-    double tot = 0.0;
-    long long sym = 0, inv = 0;
-    for (int lo = 0; lo < a.per_image; lo += CE_THREADS) {
-        const int j = lo + tid;
-        s_nats[tid] = j < a.per_image ? a.slot_nats[first + j] : 0.0;
-        s_sym[tid] = j < a.per_image ? a.slot_sym[first + j] : 0;
-        s_inv[tid] = j < a.per_image ? a.slot_inv[first + j] : 0;
-        __syncthreads();
-        if (tid == 0) {
-            const int cnt = a.per_image - lo < CE_THREADS ? a.per_image - lo : CE_THREADS;
-#pragma unroll 8
-            for (int q = 0; q < cnt; ++q) { tot += s_nats[q]; sym += s_sym[q]; inv += s_inv[q]; }   // index order; the unrolled reads overlap
-        }
-        __syncthreads();
-    }
-    if (tid == 0) { a.nats[blockIdx.x] = tot; a.symbols[blockIdx.x] = sym; a.invalid[blockIdx.x] = inv; }
+    block_sum_to_slot<CE_THREADS, 2>(acc, cnt, a.slots);
 }
 
 template <int KS, bool VEC>
@@ -249,28 +173,15 @@ __global__ __launch_bounds__(CE_THREADS) void k_ce_rate_backward(const CeRateArg
     }
 }
 
-// geometry shared by the three entry points: 0 on success with *chunks / *groups filled, 1 when a product leaves the index types
-// (cells of a plane and workgroups are ints, element offsets are longs)
-int ce_rate_geometry(int n, int g, int h, int w, int k, int *chunks, long *groups) {
-    long hw, planes, elems, wg;
-    if (__builtin_mul_overflow((long)h, (long)w, &hw) || hw > 0x7fffffffL - CE_CHUNK) return 1;
-    if (__builtin_mul_overflow((long)n, (long)g, &planes)) return 1;
-    if (__builtin_mul_overflow(planes, hw, &elems) || __builtin_mul_overflow(elems, (long)k, &elems) || elems > (1L << 60)) return 1;
-    const long per_plane = (hw + CE_CHUNK - 1) / CE_CHUNK;
-    if (__builtin_mul_overflow(planes, per_plane, &wg) || wg > 0x7fffffffL) return 1;
-    if ((long)g * per_plane > 0x7fffffffL) return 1;                         // the finish kernel's slots per image
-    *chunks = (int)per_plane;
-    *groups = wg;
-    return 0;
-}
-bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
+int ce_rate_geometry(int n, int g, int h, int w, int k, int *chunks, long *groups) { return plane_walk_geometry(n, g, h, w, k, CE_CHUNK, chunks, groups); }
+bool aligned8(const void *p) { return plane_walk_aligned(p, 4 * CE_PER_THREAD); }
 }  // namespace
 
 LIC360_API long lic360_ce_rate_scratch_bytes(int n, int g, int h, int w) {
     int chunks;
     long groups;
     if (n <= 0 || g <= 0 || h <= 0 || w <= 0 || ce_rate_geometry(n, g, h, w, CE_MAX_K, &chunks, &groups)) return 0;
-    return groups * (long)(sizeof(double) + 2 * sizeof(long long));
+    return plane_slots_bytes<2>(groups);
 }
 
 LIC360_API int lic360_ce_rate(void *stream, const float *logit, const float *label, int n, int g, int h, int w, int k, double *nats,
@@ -278,23 +189,14 @@ LIC360_API int lic360_ce_rate(void *stream, const float *logit, const float *lab
     ARG_CHECK(n >= 0 && g >= 0 && h >= 0 && w >= 0);
     ARG_CHECK(k >= 1 && k <= CE_MAX_K);
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0 || g == 0 || h == 0 || w == 0) {                              // no symbol: nothing is launched; an image's totals are still written
-        if (n > 0) {
-            ARG_CHECK(nats && symbols && invalid);
-            HIP_TRY(hipMemsetAsync(nats, 0, (size_t)n * sizeof(double), s));
-            HIP_TRY(hipMemsetAsync(symbols, 0, (size_t)n * sizeof(long long), s));
-            HIP_TRY(hipMemsetAsync(invalid, 0, (size_t)n * sizeof(long long), s));
-        }
-        return 0;
-    }
+    long long *const totals[2] = {symbols, invalid};
+    if (n == 0 || g == 0 || h == 0 || w == 0) return plane_walk_no_symbol(s, n, nats, totals);
     ARG_CHECK(logit && label && nats && symbols && invalid && scratch);
     int chunks;
     long groups;
     ARG_CHECK(!ce_rate_geometry(n, g, h, w, k, &chunks, &groups));
     ARG_CHECK(((uintptr_t)scratch & 7) == 0);
-    double *slot_nats = (double *)scratch;
-    long long *slot_sym = (long long *)(slot_nats + groups), *slot_inv = slot_sym + groups;
-    const CeRateArgs a{logit, label, nullptr, map, slot_nats, slot_sym, slot_inv, g, k, h * w, chunks};
+    const CeRateArgs a{logit, label, nullptr, map, plane_slots_carve<2>(scratch, groups), g, k, h * w, chunks};
     const bool vec = w % 2 == 0 && aligned8(logit) && aligned8(label) && aligned8(map);
     const dim3 grid((unsigned)groups), block(CE_THREADS);
     if (k == CE_STATIC_K && vec) hipLaunchKernelGGL((k_ce_rate<CE_STATIC_K, true>), grid, block, 0, s, a);
@@ -302,8 +204,7 @@ LIC360_API int lic360_ce_rate(void *stream, const float *logit, const float *lab
     else if (vec) hipLaunchKernelGGL((k_ce_rate<0, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((k_ce_rate<0, false>), grid, block, 0, s, a);
     LAUNCH_CHECK();
-    const CeFinishArgs f{slot_nats, slot_sym, slot_inv, nats, symbols, invalid, g * chunks};
-    hipLaunchKernelGGL(k_ce_rate_finish, dim3((unsigned)n), block, 0, s, f);
+    plane_sum_finish_launch<CE_THREADS, 2>(s, n, g * chunks, a.slots, nats, totals);
     LAUNCH_CHECK();
     return 0;
 }
@@ -317,7 +218,7 @@ LIC360_API int lic360_ce_rate_backward(void *stream, const float *logit, const f
     int chunks;
     long groups;
     ARG_CHECK(!ce_rate_geometry(n, g, h, w, k, &chunks, &groups));
-    const CeRateArgs a{logit, label, grad_nats, d_logit, nullptr, nullptr, nullptr, g, k, h * w, chunks};
+    const CeRateArgs a{logit, label, grad_nats, d_logit, {}, g, k, h * w, chunks};
     const bool vec = w % 2 == 0 && aligned8(logit) && aligned8(label) && aligned8(d_logit);
     const dim3 grid((unsigned)groups), block(CE_THREADS);
     hipStream_t s = (hipStream_t)stream;

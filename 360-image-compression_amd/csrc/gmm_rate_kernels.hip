@@ -8,8 +8,8 @@
 //     cells t, t + 256, t + 512, t + 768 with 4-byte accesses.  The mask is read first; a wave none of whose cells is coded (mask >= 0.5, the coder's
 //     rule) reads no parameter and does no arithmetic.  NG > 0 (3 in production) keeps a symbol's parameters in registers; NG == 0 takes ng (1..16) at
 //     run time and streams over the components in passes that read them again (L1/L2 hits), so no array is indexed at run time and nothing goes
-//     to scratch memory.  Each coded symbol's fp32 loss is added in double: a thread's cells in index order, the wave by a butterfly, the four waves in
-//     index order; total and count go to the workgroup's scratch slot.  k_gmm_rate_finish adds an image's slots in index order.  No atomics: the same
+//     to scratch memory.  Each coded symbol's fp32 loss is added in double: a thread's cells in index order, then plane_walk.h's workgroup sum
+//     (total and count to the workgroup's scratch slot) and its finish kernel, which adds an image's slots in index order.  No atomics: the same
 //     bits on every call.
 //   * k_gmm_rate_backward<NG, VEC, LABEL>: the same walk; recomputes the symbol from the inputs and writes d_logit, d_sigma, d_mean (and d_label)
 //     in place of the reads, exact zeros for uncoded cells.
@@ -17,6 +17,7 @@
 // per-component body (csrc/tile_table_kernels.hip) stated a second time in gmm_component below -- that kernel is untouched.
 #include "common.h"
 #include "lic360_exact_math.h"
+#include "plane_walk.h"
 
 namespace {
 constexpr int GR_THREADS = 256, GR_PER_THREAD = 4, GR_CHUNK = GR_THREADS * GR_PER_THREAD, GR_MAX_NG = 16;
@@ -27,16 +28,8 @@ struct GmmRateArgs {
     const float *logit, *sigma, *mean, *label, *mask;   // mask: null = every symbol coded
     const float *grad;                                  // backward: grad_nats [N]
     float *o_logit, *o_sigma, *o_mean, *o_label;        // backward: the gradients; forward: o_label is the map (or null)
-    double *slot_nats;                                  // forward: one slot per workgroup
-    long long *slot_sym;
+    PlaneSlots<1> slots;                                // forward: one slot per workgroup (total, coded symbols)
     int G, ng, HW, chunks;                              // chunks: workgroups per plane
-};
-struct GmmFinishArgs {
-    const double *slot_nats;
-    const long long *slot_sym;
-    double *nats;
-    long long *symbols;
-    int per_image;
 };
 
 struct GmmComp { float p, lw, dd, md; };
@@ -61,43 +54,14 @@ LIC360_HD float gmm_sigma(float raw) { return raw > 0.0f ? raw + GR_SIGMA_FLOOR 
 LIC360_HD float gmm_loss(float sum_p) { return -lic360_logf((float)((double)sum_p + 0.0000001)); }
 LIC360_HD float gmm_inv_p(float sum_p) { return (float)(-1.0 / ((double)sum_p + 0.0000001)); }
 
-// this thread's four cells of a plane: which they are, and moving them
+// the plane walk of this loss, and which of the thread's cells are coded
 template <bool VEC>
-struct Cells {
-    int first;                 // VEC: the first of four consecutive cells; else the first of four GR_THREADS apart
-    int hw;
-    __device__ __forceinline__ Cells(int chunk, int tid, int hw_) : first(chunk * GR_CHUNK + (VEC ? GR_PER_THREAD * tid : tid)), hw(hw_) {}
-    __device__ __forceinline__ bool inside(int k) const { return VEC ? first < hw : first + k * GR_THREADS < hw; }     // (VEC: hw % 4 == 0)
-    __device__ __forceinline__ void load(const float *plane, float (&v)[GR_PER_THREAD]) const {
-        if (VEC) {
-            float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (first < hw) q = *(const float4 *)(plane + first);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < GR_PER_THREAD; ++k) v[k] = inside(k) ? plane[first + k * GR_THREADS] : 0.0f;
-        }
-    }
-    __device__ __forceinline__ void store(float *plane, const float (&v)[GR_PER_THREAD]) const {
-        if (VEC) {
-            if (first < hw) *(float4 *)(plane + first) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < GR_PER_THREAD; ++k)
-                if (inside(k)) plane[first + k * GR_THREADS] = v[k];
-        }
-    }
-};
-
-// what a workgroup is: (image, plane, chunk) of its index, the cells of this thread and which of them are coded
-template <bool VEC>
-struct Walk {
-    long plane;                // n * G + g
-    int n;
-    Cells<VEC> cells;
+struct Walk : PlaneWalk<GR_THREADS, GR_PER_THREAD, VEC> {
+    using PlaneWalk<GR_THREADS, GR_PER_THREAD, VEC>::plane;
+    using PlaneWalk<GR_THREADS, GR_PER_THREAD, VEC>::cells;
     bool coded[GR_PER_THREAD];
     bool any;                  // a cell of this WAVE is coded
-    __device__ __forceinline__ Walk(const GmmRateArgs &a) : plane(blockIdx.x / a.chunks), n((int)(plane / a.G)), cells(blockIdx.x % a.chunks, threadIdx.x, a.HW) {
+    __device__ __forceinline__ Walk(const GmmRateArgs &a) : PlaneWalk<GR_THREADS, GR_PER_THREAD, VEC>(a.chunks, a.G, a.HW) {
         float m[GR_PER_THREAD];
         if (a.mask) cells.load(a.mask + plane * a.HW, m);
         bool mine = false;
@@ -239,8 +203,6 @@ __device__ __forceinline__ void gmm_cells_stream(const GmmRateArgs &a, const Wal
 
 template <int NG, bool VEC>
 __global__ __launch_bounds__(GR_THREADS) void k_gmm_rate(const GmmRateArgs a) {
-    __shared__ double s_nats[GR_THREADS / 64];
-    __shared__ int s_sym[GR_THREADS / 64];
     const Walk<VEC> wk(a);
     const long HW = a.HW;
     float loss[GR_PER_THREAD] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -263,46 +225,11 @@ __global__ __launch_bounds__(GR_THREADS) void k_gmm_rate(const GmmRateArgs a) {
     }
     if (a.o_label) wk.cells.store(a.o_label + wk.plane * HW, loss);          // the map: 0 where uncoded
     double acc = 0.0;
-    int cnt = 0;
+    int cnt[1] = {0};
 #pragma unroll
     for (int k = 0; k < GR_PER_THREAD; ++k)
-        if (wk.coded[k]) { acc += (double)loss[k]; ++cnt; }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_xor(acc, off);
-        cnt += __shfl_xor(cnt, off);
-    }
-    const int tid = threadIdx.x;
-    if ((tid & 63) == 0) { s_nats[tid >> 6] = acc; s_sym[tid >> 6] = cnt; }
-    __syncthreads();
-    if (tid == 0) {
-        double tot = s_nats[0];
-        int c = s_sym[0];
-        for (int wv = 1; wv < GR_THREADS / 64; ++wv) { tot += s_nats[wv]; c += s_sym[wv]; }
-        a.slot_nats[blockIdx.x] = tot;
-        a.slot_sym[blockIdx.x] = c;
-    }
-}
-
-__global__ __launch_bounds__(GR_THREADS) void k_gmm_rate_finish(const GmmFinishArgs a) {
-    __shared__ double s_nats[GR_THREADS];
-    __shared__ long long s_sym[GR_THREADS];
-    const int tid = threadIdx.x;
-    const long first = (long)blockIdx.x * a.per_image;
-    double tot = 0.0;
-    long long sym = 0;
-    for (int lo = 0; lo < a.per_image; lo += GR_THREADS) {
-        const int j = lo + tid;
-        s_nats[tid] = j < a.per_image ? a.slot_nats[first + j] : 0.0;
-        s_sym[tid] = j < a.per_image ? a.slot_sym[first + j] : 0;
-        __syncthreads();
-        if (tid == 0) {
-            const int cnt = a.per_image - lo < GR_THREADS ? a.per_image - lo : GR_THREADS;
-#pragma unroll 8
-            for (int q = 0; q < cnt; ++q) { tot += s_nats[q]; sym += s_sym[q]; }               // index order; the unrolled reads overlap
-        }
-        __syncthreads();
-    }
-    if (tid == 0) { a.nats[blockIdx.x] = tot; a.symbols[blockIdx.x] = sym; }
+        if (wk.coded[k]) { acc += (double)loss[k]; ++cnt[0]; }
+    block_sum_to_slot<GR_THREADS, 1>(acc, cnt, a.slots);
 }
 
 template <int NG, bool VEC, bool LABEL>
@@ -348,27 +275,15 @@ __global__ __launch_bounds__(GR_THREADS) void k_gmm_rate_backward(const GmmRateA
     if (LABEL) wk.cells.store(a.o_label + wk.plane * HW, zero);
 }
 
-// geometry shared by the three entry points: 0 on success with *chunks / *groups filled, 1 when a product leaves the index types
-// (cells of a plane and workgroups are ints, element offsets are longs)
-int gmm_rate_geometry(int n, int g, int h, int w, int ng, int *chunks, long *groups) {
-    long hw, planes, elems, wg;
-    if (__builtin_mul_overflow((long)h, (long)w, &hw) || hw > 0x7fffffffL - GR_CHUNK) return 1;
-    if (__builtin_mul_overflow((long)n, (long)g, &planes)) return 1;
-    if (__builtin_mul_overflow(planes, hw, &elems) || __builtin_mul_overflow(elems, (long)ng, &elems) || elems > (1L << 60)) return 1;
-    const long per_plane = (hw + GR_CHUNK - 1) / GR_CHUNK;
-    if (__builtin_mul_overflow(planes, per_plane, &wg) || wg > 0x7fffffffL) return 1;
-    *chunks = (int)per_plane;
-    *groups = wg;
-    return 0;
-}
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+int gmm_rate_geometry(int n, int g, int h, int w, int ng, int *chunks, long *groups) { return plane_walk_geometry(n, g, h, w, ng, GR_CHUNK, chunks, groups); }
+bool aligned16(const void *p) { return plane_walk_aligned(p, 4 * GR_PER_THREAD); }
 }  // namespace
 
 LIC360_API long lic360_gmm_rate_scratch_bytes(int n, int g, int h, int w) {
     int chunks;
     long groups;
     if (n <= 0 || g <= 0 || h <= 0 || w <= 0 || gmm_rate_geometry(n, g, h, w, GR_MAX_NG, &chunks, &groups)) return 0;
-    return groups * (long)(sizeof(double) + sizeof(long long));
+    return plane_slots_bytes<1>(groups);
 }
 
 LIC360_API int lic360_gmm_rate(void *stream, const float *logit, const float *sigma, const float *mean, const float *label, const float *mask,
@@ -376,22 +291,14 @@ LIC360_API int lic360_gmm_rate(void *stream, const float *logit, const float *si
     ARG_CHECK(n >= 0 && g >= 0 && h >= 0 && w >= 0);
     ARG_CHECK(ng >= 1 && ng <= GR_MAX_NG);
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0 || g == 0 || h == 0 || w == 0) {                              // no symbol: nothing is launched; an image's totals are still written
-        if (n > 0) {
-            ARG_CHECK(nats && symbols);
-            HIP_TRY(hipMemsetAsync(nats, 0, (size_t)n * sizeof(double), s));
-            HIP_TRY(hipMemsetAsync(symbols, 0, (size_t)n * sizeof(long long), s));
-        }
-        return 0;
-    }
+    long long *const totals[1] = {symbols};
+    if (n == 0 || g == 0 || h == 0 || w == 0) return plane_walk_no_symbol(s, n, nats, totals);
     ARG_CHECK(logit && sigma && mean && label && nats && symbols && scratch);
     int chunks;
     long groups;
     ARG_CHECK(!gmm_rate_geometry(n, g, h, w, ng, &chunks, &groups));
     ARG_CHECK(((uintptr_t)scratch & 7) == 0);
-    double *slot_nats = (double *)scratch;
-    long long *slot_sym = (long long *)(slot_nats + groups);
-    const GmmRateArgs a{logit, sigma, mean, label, mask, nullptr, nullptr, nullptr, nullptr, map, slot_nats, slot_sym, g, ng, h * w, chunks};
+    const GmmRateArgs a{logit, sigma, mean, label, mask, nullptr, nullptr, nullptr, nullptr, map, plane_slots_carve<1>(scratch, groups), g, ng, h * w, chunks};
     const bool vec = w % 4 == 0 && aligned16(logit) && aligned16(sigma) && aligned16(mean) && aligned16(label) && aligned16(mask) && aligned16(map);
     const dim3 grid((unsigned)groups), block(GR_THREADS);
     if (ng == 3 && vec) hipLaunchKernelGGL((k_gmm_rate<3, true>), grid, block, 0, s, a);
@@ -399,8 +306,7 @@ LIC360_API int lic360_gmm_rate(void *stream, const float *logit, const float *si
     else if (vec) hipLaunchKernelGGL((k_gmm_rate<0, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((k_gmm_rate<0, false>), grid, block, 0, s, a);
     LAUNCH_CHECK();
-    const GmmFinishArgs f{slot_nats, slot_sym, nats, symbols, g * chunks};
-    hipLaunchKernelGGL(k_gmm_rate_finish, dim3((unsigned)n), block, 0, s, f);
+    plane_sum_finish_launch<GR_THREADS, 1>(s, n, g * chunks, a.slots, nats, totals);
     LAUNCH_CHECK();
     return 0;
 }
@@ -415,7 +321,7 @@ LIC360_API int lic360_gmm_rate_backward(void *stream, const float *logit, const 
     int chunks;
     long groups;
     ARG_CHECK(!gmm_rate_geometry(n, g, h, w, ng, &chunks, &groups));
-    const GmmRateArgs a{logit, sigma, mean, label, mask, grad_nats, d_logit, d_sigma, d_mean, d_label, nullptr, nullptr, g, ng, h * w, chunks};
+    const GmmRateArgs a{logit, sigma, mean, label, mask, grad_nats, d_logit, d_sigma, d_mean, d_label, {}, g, ng, h * w, chunks};
     const bool vec = w % 4 == 0 && aligned16(logit) && aligned16(sigma) && aligned16(mean) && aligned16(label) && aligned16(mask) &&
                      aligned16(d_logit) && aligned16(d_sigma) && aligned16(d_mean) && aligned16(d_label);
     const dim3 grid((unsigned)groups), block(GR_THREADS);

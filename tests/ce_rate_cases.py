@@ -67,9 +67,12 @@ CASES = (
     _c(3, 5, 3, 5, 49, "image", "edge"),
     _c(2, 2, 6, 8, 3, "mixed", "edge"),
     _c(2, 1, 15, 19, 50, "mixed", "edge"),
+    _c(2, 129, 2, 4, 3, "mixed", "slots"),     # 129 slots per image: the finish kernel's second pass (THREADS + 1), vector form, generic K
+    _c(2, 129, 3, 5, 49, "mixed", "slots"),    # the same in the scalar form, K = 49
 )
 REGULAR = tuple(c for c in CASES if c.family == "regular")
 EDGE = tuple(c for c in CASES if c.family == "edge")
+SLOTS = tuple(c for c in CASES if c.family == "slots")       # kernels only: bit for bit and within nats_bound, no recorded float64 figures
 BY_ID = {c.id: c for c in CASES}
 
 
@@ -137,12 +140,14 @@ def reach(case):
     if case.N > 1 and (~per_image.any(1)).any() and per_image.any():
         names.add("invalid_image_among_valid")
     names |= {"edge_" + k for k in d["edges"]}
+    if case.G * chunks(case) > THREADS:                                 # slots per image: the finish kernel adds them in passes of THREADS
+        names.add("finish_second_pass")
     return names
 
 
 REACH = ("vec_static", "vec_generic", "scalar_static", "scalar_generic", "multi_chunk", "exactly_two_chunks", "ragged_chunk_vec", "ragged_chunk_scalar",
          "misaligned_w4_scalar", "misaligned_w4_vec", "plane_base_4_byte", "K49_G2", "K49_G3", "every_class", "label_minus_half", "label_fractional",
-         "label_minus_1", "label_K", "label_1e9", "label_nan", "invalid_image_among_valid", "family_regular", "family_edge") + \
+         "label_minus_1", "label_K", "label_1e9", "label_nan", "invalid_image_among_valid", "family_regular", "family_edge", "finish_second_pass") + \
     tuple("K%d" % k for k in (1, 2, 3, 48, 49, 50, 64)) + tuple("labels_" + k for k in LABEL_KINDS) + tuple("edge_" + k for k in EDGE_KINDS)
 
 # MEASURED here on the CPU: the reference's own distance from the float64 statement -- max |reference - float64 autograd| over the elements of d_logit
@@ -322,7 +327,7 @@ def logf(x):
 
 
 BROKEN = ("no_max_subtraction", "sum_reversed", "label_rounded", "invalid_clamped", "minus_one_on_wrong_class", "gk_taken_as_g", "ragged_tail_written",
-          "t_of_image_0")
+          "t_of_image_0", "finish_first_pass_only")
 UNWRITTEN = F(7.7701e33)
 
 
@@ -373,7 +378,14 @@ def reference(case, broken=None):
     out["map"] = mp.reshape(N, G, H, W)
     out["symbols"] = valid.reshape(N, -1).sum(1).astype(np.int64)
     out["invalid"] = (~valid).reshape(N, -1).sum(1).astype(np.int64)
-    per = [list(map(float, mp.reshape(N, -1)[n][valid.reshape(N, -1)[n]])) for n in range(N)]
+    summed = valid.reshape(N, -1)
+    if broken == "finish_first_pass_only":
+        # slot j = g * chunks + chunk of an image; the slots past the first THREADS never reach nats and the counts
+        slot = (np.arange(G)[:, None] * chunks(case) + np.arange(H * W)[None, :] // CHUNK).reshape(-1)
+        summed = summed & (slot < THREADS)
+        out["symbols"] = summed.sum(1).astype(np.int64)
+        out["invalid"] = (~valid.reshape(N, -1) & (slot < THREADS)).sum(1).astype(np.int64)
+    per = [list(map(float, mp.reshape(N, -1)[n][summed[n]])) for n in range(N)]
     if broken == "ragged_tail_written" and (H * W) % CHUNK:
         # the cells past the plane's end in its last chunk load zeros: label 0, K equal logits -- valid symbols of class 0 that cost log K
         tail = chunks(case) * CHUNK - H * W

@@ -71,9 +71,12 @@ CASES = (
     _c(2, 4, 6, 8, 1, "stair", "edge"),
     _c(3, 2, 25, 45, 3, "runs64", "edge"),
     _c(1, 2, 32, 64, 5, "runs256", "edge"),
+    _c(2, 257, 2, 4, 3, "stair", "slots"),   # 257 slots per image: the finish kernel's second pass (THREADS + 1), vector form, ng = 3
+    _c(2, 257, 3, 5, 5, "stair", "slots"),   # the same in the scalar form, ng at run time
 )
 REGULAR = tuple(c for c in CASES if c.family == "regular")
 EDGE = tuple(c for c in CASES if c.family == "edge")
+SLOTS = tuple(c for c in CASES if c.family == "slots")       # kernels only: bit for bit and within nats_bound, no recorded float64 figures
 BY_ID = {c.id: c for c in CASES}
 
 
@@ -118,11 +121,13 @@ def reach(case):
         names.add("dead_wave_beside_live_" + form(case))
     if case.N > 1 and any(not coded.reshape(case.N, -1)[n].any() for n in range(case.N)) and coded.any():
         names.add("dead_image_among_live")
+    if case.G * chunks(case) > THREADS:                                  # slots per image: the finish kernel adds them in passes of THREADS
+        names.add("finish_second_pass")
     return names
 
 
 REACH = ("vec_static", "vec_generic", "scalar_static", "scalar_generic", "multi_chunk", "ragged_chunk_vec", "ragged_chunk_scalar", "misaligned_w4",
-         "plane_base_4_byte", "dead_wave_beside_live_vec", "dead_wave_beside_live_scalar", "dead_image_among_live", "family_regular", "family_edge") + \
+         "plane_base_4_byte", "dead_wave_beside_live_vec", "dead_wave_beside_live_scalar", "dead_image_among_live", "family_regular", "family_edge", "finish_second_pass") + \
     tuple("mask_" + k for k in MASK_KINDS)
 
 # MEASURED: max |reference - float64 autograd| on the rows with p >= GMM_MIN_P, (over the four gradients and the loss, of nats[n]); gradient scales
@@ -279,7 +284,7 @@ def softmax_rows(l, no_max=False):
 
 
 BROKEN = ("channel_i_major", "mask_rule_gt", "relu_gradient_kept", "floor_before_sign", "softmax_without_max", "dot_reversed", "uncoded_unwritten",
-          "last_chunk_dropped", "d_label_scaled_twice")
+          "last_chunk_dropped", "d_label_scaled_twice", "finish_first_pass_only")
 UNWRITTEN = F(7.7701e33)
 
 
@@ -335,7 +340,13 @@ def reference(case, broken=None):
     m[sel] = loss
     out["map"] = m.reshape(N, G, H, W)
     out["symbols"] = coded.reshape(N, -1).sum(1).astype(np.int64)
-    per = [m.reshape(N, -1)[n][coded.reshape(N, -1)[n]] for n in range(N)]
+    summed = coded.reshape(N, -1)
+    if broken == "finish_first_pass_only":
+        # slot j = g * chunks + chunk of an image; the slots past the first THREADS never reach nats and the count
+        slot = (np.arange(G)[:, None] * chunks(case) + np.arange(H * W)[None, :] // CHUNK).reshape(-1)
+        summed = summed & (slot < THREADS)
+        out["symbols"] = summed.sum(1).astype(np.int64)
+    per = [m.reshape(N, -1)[n][summed[n]] for n in range(N)]
     out["nats"] = np.array([math.fsum(float(v) for v in p) for p in per], np.float64)
     out["abs"] = np.array([math.fsum(abs(float(v)) for v in p) for p in per], np.float64)
     for v in out.values():

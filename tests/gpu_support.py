@@ -1,6 +1,6 @@
 """What the transforms' GPU tests share, each piece once: the `lic` fixture, host <-> device one-liners, the float64 -> fp32 reference with its cache, the
 whole-output and frame comparisons, the sentinel-filled call, the two-stream repeat loop, the past-4 GiB scaffolding, the recorder of lic360.sconv* calls, the
-count-rule switch, the block-parameter jitter and the bf16x1 criteria -- and, for the fused latent codec's tests, the one way to create a codec under its
+count-rule switch, the block-parameter jitter, the bf16x1 criteria and the canaried allocations (Arena) -- and, for the fused latent codec's tests, the one way to create a codec under its
 environment switches (codec_under).  A plain module, imported like util.py and the *_cases.py files; which entry point, pack
 and keywords a form takes stays in the form's own test file, which hands a closure `call(out)` to the helpers here.  tests/test_gpu_support_cpu.py checks the
 checkers on CPU tensors."""
@@ -55,6 +55,53 @@ def codec_under(G, H, W, B, layers, **switches):
                 os.environ[k] = old[k]
     fc.load_layers(layers)
     return fc
+
+
+# ---- canaried, sentinel-filled, deliberately misaligned allocations (the pointwise / table ops and the fused rate losses)
+GUARD_BYTES = 256                # of canary on either side: the carved view keeps the allocation's 256-byte alignment
+CANARY = {torch.float32: float(np.float32(-6.0221e23)), torch.float64: -6.0221e23, torch.int64: -0x5A5A5A5A5A5A5A5A, torch.uint8: 0x5A}
+# what a call leaves unwritten still holds; fp32: the *_cases.py files' UNWRITTEN
+SENTINEL = {torch.float32: float(np.float32(7.7701e33)), torch.float64: 7.7701e33, torch.int64: 0x7777777777777777, torch.uint8: 0xA5}
+
+
+class Arena(object):
+    """tensors carved out of canaried allocations; `offset` elements past the aligned start give a 4-byte (odd offset) or 8-byte (offset 2)
+    aligned fp32 view that is not 16-byte aligned"""
+
+    def __init__(self, device="cuda:0"):
+        self.device = torch.device(device)
+        self.bufs = []
+
+    def new(self, shape, offset=0, dtype=torch.float32):
+        n = int(np.prod(shape))
+        guard = GUARD_BYTES // torch.empty((), dtype=dtype).element_size()
+        buf = torch.full((guard + offset + n + guard,), CANARY[dtype], dtype=dtype, device=self.device)
+        view = buf[guard + offset:guard + offset + n].view(*shape)
+        view.fill_(SENTINEL[dtype])
+        assert view.data_ptr() % 16 == (view.element_size() * offset) % 16 and view.is_contiguous()
+        self.bufs.append((buf, guard + offset, n, dtype))
+        return view
+
+    def put(self, a, offset=0):
+        view = self.new(a.shape, offset)
+        view.copy_(torch.from_numpy(np.array(a, copy=True)))
+        return view
+
+    def check(self):
+        if self.device.type == "cuda":
+            torch.cuda.synchronize()
+        for k, (buf, lo, n, dtype) in enumerate(self.bufs):
+            front, back = int((buf[:lo] != CANARY[dtype]).sum()), int((buf[lo + n:] != CANARY[dtype]).sum())
+            assert front == 0 and back == 0, "allocation %d: %d canaries overwritten in front, %d behind" % (k, front, back)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def differing(a, b):
+    """how many fp32 elements of two arrays of one shape differ in their bits"""
+    return int((a.view(np.uint32) != b.view(np.uint32)).sum())
 
 
 _REFS = {}                                                                  # key -> fp32 reference, for the callers that asked to keep it

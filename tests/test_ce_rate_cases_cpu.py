@@ -1,5 +1,6 @@
 """The cases of the fused cross-entropy rate loss (tests/ce_rate_cases.py) without a GPU: the case list reaches every path of the restated launch
-geometry, the restated constants are the source's, the built kernels use no scratch memory, the numpy lic360_logf is the header's bit for bit,
+geometry, the restated constants are the source's, the built kernels (and the GMM rate loss's, which share csrc/plane_walk.h with them) use no
+scratch memory, the numpy lic360_logf is the header's bit for bit,
 the reference agrees with the float64 statement of the head within the recorded figures, and every model of a broken kernel changes the
 reference on some case.
 
@@ -19,6 +20,7 @@ import ce_rate_cases as cc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "360-image-compression_amd")
 SOURCE = os.path.join(PKG, "csrc", "ce_rate_kernels.hip")
+SHARED = os.path.join(PKG, "csrc", "plane_walk.h")
 LIB = os.path.join(PKG, "liblic360_hip.so")
 READELF = shutil.which("llvm-readelf") or "/opt/rocm/lib/llvm/bin/llvm-readelf"
 F = np.float32
@@ -31,7 +33,8 @@ def test_restated_constants_are_the_source_s():
     assert tuple(int(v) for v in m.groups()) == (cc.THREADS, cc.PER_THREAD, cc.MAX_K, cc.STATIC_K) and cc.CHUNK == cc.THREADS * cc.PER_THREAD
     assert "if (k == CE_STATIC_K && vec)" in text                            # the one class count with an instantiation of its own
     assert text.count("const bool vec = w % 2 == 0 && aligned8(logit) && aligned8(label) && aligned8(") == 2     # the vector form's condition, as form() restates it
-    assert "return ((uintptr_t)p & 7) == 0;" in text and cc.VEC_BYTES == 8 == 4 * cc.PER_THREAD
+    assert "bool aligned8(const void *p) { return plane_walk_aligned(p, 4 * CE_PER_THREAD); }" in text and cc.VEC_BYTES == 8 == 4 * cc.PER_THREAD
+    assert "return ((uintptr_t)p & (bytes - 1)) == 0;" in open(SHARED).read()  # ... the alignment of every base, in bytes, stated beside the walk
     assert "lab[k] > -1.0f && lab[k] < top" in text and "(int)lab[k]" in text   # validity and truncation, as valid_of and reference restate them
     makefile = open(os.path.join(PKG, "csrc", "Makefile")).read()
     assert "ce_rate_kernels.hip" in makefile and "-ffp-contract=off" in makefile  # nothing contracted outside the lic360_* functions' own fmaf
@@ -161,11 +164,16 @@ def test_every_broken_model_changes_the_reference(broken):
             changed.append(case.id)
     print(broken, "changes", len(changed), "cases")
     assert changed, "no case would notice a kernel that is broken this way"
+    if broken == "finish_first_pass_only":                                   # only an image of more than THREADS slots can show it
+        assert changed == [c.id for c in cc.SLOTS] and len(changed) == 2
 
 
 # ---- resources of the built kernels (the method of tests/test_kernarg_bytes.py: the gfx950 code objects' notes, read with llvm-readelf)
 KERNELS = ("k_ce_rateILi49ELb1EE", "k_ce_rateILi49ELb0EE", "k_ce_rateILi0ELb1EE", "k_ce_rateILi0ELb0EE", "k_ce_rate_backwardILi49ELb1EE",
-           "k_ce_rate_backwardILi49ELb0EE", "k_ce_rate_backwardILi0ELb1EE", "k_ce_rate_backwardILi0ELb0EE", "k_ce_rate_finish")
+           "k_ce_rate_backwardILi49ELb0EE", "k_ce_rate_backwardILi0ELb1EE", "k_ce_rate_backwardILi0ELb0EE", "k_plane_sum_finishILi128ELi2EE")
+# the GMM rate loss's twelve kernels and its instantiation of the finish kernel: the same three conditions (their one struct is 112 bytes)
+GMM_KERNELS = tuple("k_gmm_rateILi%dELb%dEE" % (ng, v) for ng in (3, 0) for v in (1, 0)) + \
+    tuple("k_gmm_rate_backwardILi%dELb%dELb%dEE" % (ng, v, lab) for ng in (3, 0) for v in (1, 0) for lab in (1, 0)) + ("k_plane_sum_finishILi256ELi1EE",)
 
 
 def _kernel_notes():
@@ -198,7 +206,8 @@ def test_kernels_use_no_scratch_memory_and_do_not_spill():
     assert os.path.exists(LIB), "the library is not built: the requirement cannot be read, which is a failure, not a skip"
     assert os.path.exists(READELF), "llvm-readelf (part of the ROCm toolchain that builds the library) is missing"
     notes = _kernel_notes()
-    for pat in KERNELS:
+    assert len(GMM_KERNELS) == 13
+    for pat in KERNELS + GMM_KERNELS:
         hits = [n for n in notes if pat in n]
         assert len(hits) == 1, (pat, hits)
         block = notes[hits[0]]
@@ -207,4 +216,4 @@ def test_kernels_use_no_scratch_memory_and_do_not_spill():
         assert field("private_segment_fixed_size") == 0, pat + ": scratch memory"
         assert field("vgpr_spill_count") == 0 and field("sgpr_spill_count") == 0, pat + ": spills"
         assert field("vgpr_count") + field("agpr_count") <= 256, pat + ": two waves per SIMD have 256 registers each"
-        assert field("kernarg_segment_size") <= 72 and "hidden_" not in block, pat + ": one struct by value, no implicit arguments"
+        assert field("kernarg_segment_size") <= (72 if pat in KERNELS else 112) and "hidden_" not in block, pat + ": one struct by value, no implicit arguments"

@@ -24,6 +24,7 @@ def test_restated_constants_are_the_source_s():
     assert re.search(r"constexpr float GR_SIGMA_FLOOR = 0\.00001f;", text) and gc.SIGMA_FLOOR == np.float32(0.00001)
     assert "if (ng == %d && vec)" % gc.STATIC_NG in text                    # the one mixture size with an instantiation of its own
     assert "w % 4 == 0 && aligned16(logit)" in text                        # the vector form's condition starts as restated in form()
+    assert "bool aligned16(const void *p) { return plane_walk_aligned(p, 4 * GR_PER_THREAD); }" in text and 4 * gc.PER_THREAD == 16
 
 
 def test_case_ids_are_unique_and_cases_reach_every_path():
@@ -115,3 +116,5 @@ def test_every_broken_model_changes_the_reference(broken):
             changed.append(case.id)
     print(broken, "changes", len(changed), "cases")
     assert changed, "no case would notice a kernel that is broken this way"
+    if broken == "finish_first_pass_only":                                   # only an image of more than THREADS slots can show it
+        assert changed == [c.id for c in gc.SLOTS] and len(changed) == 2

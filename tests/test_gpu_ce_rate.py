@@ -1,7 +1,7 @@
 """The fused cross-entropy rate loss on the GPU (csrc/ce_rate_kernels.hip; cases, reference and tolerances in tests/ce_rate_cases.py, their CPU side
 in tests/test_ce_rate_cases_cpu.py).  Kernels: map and d_logit bit for bit the reference's, symbols and invalid equal, nats within the bound of a
 double sum in any fixed order and the same bits on every call; every output carved from a canary-guarded, sentinel-filled allocation
-(test_gpu_gmm_rate.py's pattern), the scratch poisoned.  Modules: CeRateLoss's two routes against the float64 statement of the head, the label
+(gpu_support.Arena), the scratch poisoned.  Modules: CeRateLoss's two routes against the float64 statement of the head, the label
 check, the fallbacks, and lic360_models.EntropyNet3 under both heads and beside the coder's own estimate."""
 import math
 
@@ -10,57 +10,17 @@ import pytest
 import torch
 
 import ce_rate_cases as cc
-from gpu_support import host, lic  # noqa: F401
+from gpu_support import SENTINEL, Arena, differing, host, lic, same_bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-GUARD_BYTES = 256                # of canary on either side: the carved view keeps the allocation's 256-byte alignment
-CANARY = {torch.float32: float(F(-6.0221e23)), torch.float64: -6.0221e23, torch.int64: -0x5A5A5A5A5A5A5A5A, torch.uint8: 0x5A}
-SENTINEL = {torch.float32: float(cc.UNWRITTEN), torch.float64: 7.7701e33, torch.int64: 0x7777777777777777, torch.uint8: 0xA5}
-
-
-class Arena(object):
-    """tensors carved out of canaried allocations; `offset` elements past the aligned start give a 4-byte (odd offset) or 8-byte (offset 2)
-    aligned fp32 view that is not 16-byte aligned"""
-
-    def __init__(self):
-        self.bufs = []
-
-    def new(self, shape, offset=0, dtype=torch.float32):
-        n = int(np.prod(shape))
-        guard = GUARD_BYTES // torch.empty((), dtype=dtype).element_size()
-        buf = torch.full((guard + offset + n + guard,), CANARY[dtype], dtype=dtype, device="cuda:0")
-        view = buf[guard + offset:guard + offset + n].view(*shape)
-        view.fill_(SENTINEL[dtype])
-        assert view.data_ptr() % 16 == (view.element_size() * offset) % 16 and view.is_contiguous()
-        self.bufs.append((buf, guard + offset, n, dtype))
-        return view
-
-    def put(self, a, offset=0):
-        view = self.new(a.shape, offset)
-        view.copy_(torch.from_numpy(np.array(a, copy=True)))
-        return view
-
-    def check(self):
-        torch.cuda.synchronize()
-        for k, (buf, lo, n, dtype) in enumerate(self.bufs):
-            front, back = buf[:lo], buf[lo + n:]
-            bad = int((front != CANARY[dtype]).sum()) + int((back != CANARY[dtype]).sum())
-            assert bad == 0, "allocation %d: %d canaries overwritten" % (k, bad)
+assert SENTINEL[torch.float32] == float(cc.UNWRITTEN)
 
 
 def operands(ar, case):
     d = cc.inputs(case)
     return dict(logit=ar.put(d["logit"], case.offset), label=ar.put(d["label"], case.offset), grad=ar.put(d["grad"]))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def differing(a, b):
-    return int((a.view(np.uint32) != b.view(np.uint32)).sum())
 
 
 CASE_ID = lambda c: "%s-%s_%s" % (c.id, cc.form(c), cc.instantiation(c))

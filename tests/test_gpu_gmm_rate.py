@@ -1,50 +1,19 @@
 """The fused GMM rate loss on the GPU (csrc/gmm_rate_kernels.hip; cases, reference and tolerances in tests/gmm_rate_cases.py, their CPU side in
 tests/test_gmm_rate_cases_cpu.py).  Kernels: map and the gradients bit for bit the reference's, symbols equal, nats within the bound of a double
 sum in any fixed order and the same bits on every call; every output carved from a canary-guarded, sentinel-filled allocation
-(test_gpu_ops_edges.py's pattern), the scratch poisoned.  Modules: GmmRateLoss's two routes against the float64 statement of the head, the
+(gpu_support.Arena), the scratch poisoned.  Modules: GmmRateLoss's two routes against the float64 statement of the head, the
 fallbacks, and lic360_models.EntropyNet2 under both heads."""
 import numpy as np
 import pytest
 import torch
 
 import gmm_rate_cases as gc
-from gpu_support import host, lic  # noqa: F401
+from gpu_support import SENTINEL, Arena, differing, host, lic, same_bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-GUARD_BYTES = 256                # of canary on either side: the carved view keeps the allocation's 256-byte alignment
-CANARY = {torch.float32: float(F(-6.0221e23)), torch.float64: -6.0221e23, torch.int64: -0x5A5A5A5A5A5A5A5A, torch.uint8: 0x5A}
-SENTINEL = {torch.float32: float(gc.UNWRITTEN), torch.float64: 7.7701e33, torch.int64: 0x7777777777777777, torch.uint8: 0xA5}
-
-
-class Arena(object):
-    """tensors carved out of canaried allocations; `offset` elements past the aligned start give a 4-byte aligned, not 16-byte aligned, fp32 view"""
-
-    def __init__(self):
-        self.bufs = []
-
-    def new(self, shape, offset=0, dtype=torch.float32):
-        n = int(np.prod(shape))
-        guard = GUARD_BYTES // torch.empty((), dtype=dtype).element_size()
-        buf = torch.full((guard + offset + n + guard,), CANARY[dtype], dtype=dtype, device="cuda:0")
-        view = buf[guard + offset:guard + offset + n].view(*shape)
-        view.fill_(SENTINEL[dtype])
-        assert view.data_ptr() % 16 == (view.element_size() * offset) % 16 and view.is_contiguous()
-        self.bufs.append((buf, guard + offset, n, dtype))
-        return view
-
-    def put(self, a, offset=0):
-        view = self.new(a.shape, offset)
-        view.copy_(torch.from_numpy(np.array(a, copy=True)))
-        return view
-
-    def check(self):
-        torch.cuda.synchronize()
-        for k, (buf, lo, n, dtype) in enumerate(self.bufs):
-            front, back = buf[:lo], buf[lo + n:]
-            bad = int((front != CANARY[dtype]).sum()) + int((back != CANARY[dtype]).sum())
-            assert bad == 0, "allocation %d: %d canaries overwritten" % (k, bad)
+assert SENTINEL[torch.float32] == float(gc.UNWRITTEN)
 
 
 def operands(ar, case):
@@ -53,10 +22,6 @@ def operands(ar, case):
     t["mask"] = None if d["mask"] is None else ar.put(d["mask"], case.offset)
     t["grad"] = ar.put(d["grad"])
     return t
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 # ---------------------------------------------------------------------------------------------------- kernels
@@ -76,7 +41,7 @@ def test_forward(lic, case):
         ar.check()
         runs.append((host(nats), host(symbols), None if mp is None else host(mp)))
     nats, symbols, mp = runs[0]
-    assert same_bits(mp, ref["map"]), "%d of %d map cells differ" % (int((mp.view(np.uint32) != ref["map"].view(np.uint32)).sum()), mp.size)
+    assert same_bits(mp, ref["map"]), "%d of %d map cells differ" % (differing(mp, ref["map"]), mp.size)
     assert np.array_equal(symbols, ref["symbols"]) and np.array_equal(runs[1][1], ref["symbols"])
     err, bound = np.abs(nats - ref["nats"]), gc.nats_bound(ref)
     print("%s: |nats - fsum| %s, bound %s" % (case.id, err.tolist(), bound.tolist()))
@@ -103,7 +68,7 @@ def test_backward(lic, case):
                 continue
             g = host(g)
             assert same_bits(g, ref[k]), "%s (d_label %s): %d of %d elements differ, %d left unwritten" % (
-                k, need_label, int((g.view(np.uint32) != ref[k].view(np.uint32)).sum()), g.size, int((g == gc.UNWRITTEN).sum()))
+                k, need_label, differing(g, ref[k]), g.size, int((g == gc.UNWRITTEN).sum()))
         assert (host(spare) == gc.UNWRITTEN).all()
 
 

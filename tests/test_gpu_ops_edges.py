@@ -1,6 +1,6 @@
 """The pointwise, table and projection ops on every dispatch path of their launchers (tests/ops_edge_cases.py; the CPU side of the
 cases is tests/test_ops_edge_cases_cpu.py).  Each case runs through the drop-in ops of `lic360`.  Every buffer an op writes is carved
-from a larger allocation with canary floats on both sides and pre-filled with a sentinel: the canaries must be intact after the launch,
+from a larger allocation with canary floats on both sides and pre-filled with a sentinel (gpu_support.Arena): the canaries must be intact after the launch,
 and whatever an op leaves unwritten shows as the sentinel.  Equality with the CPU oracle wherever tests/test_gpu_ops.py demands it;
 the float64 statements at the bounds derived or measured in ops_edge_cases.py."""
 import numpy as np
@@ -9,46 +9,16 @@ import torch
 
 import oracle as orc
 import ops_edge_cases as oe
-from gpu_support import host, lic  # noqa: F401
+from gpu_support import SENTINEL as _SENTINEL, Arena, host, lic  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-GUARD = 64                       # floats (256 bytes) of canary on either side: the carved view keeps the allocation's 256-byte alignment
-CANARY = float(F(-6.0221e23))
-SENTINEL = float(F(7.7701e33))
+SENTINEL = _SENTINEL[torch.float32]
 
 
 def dev(a):
     return torch.from_numpy(np.array(a, copy=True)).to("cuda:0")          # a copy: the cached case arrays are read-only
-
-
-class Arena(object):
-    """tensors carved out of canaried allocations; `offset` floats past the aligned start give a 4-byte aligned, not 16-byte aligned, view"""
-
-    def __init__(self):
-        self.bufs = []
-
-    def new(self, shape, offset=0, fill=SENTINEL):
-        n = int(np.prod(shape))
-        buf = torch.full((GUARD + offset + n + GUARD,), CANARY, dtype=torch.float32, device="cuda:0")
-        view = buf[GUARD + offset:GUARD + offset + n].view(*shape)
-        view.fill_(fill)
-        assert view.data_ptr() % 16 == (4 * offset) % 16 and view.is_contiguous()
-        self.bufs.append((buf, GUARD + offset, n))
-        return view
-
-    def put(self, a, offset=0):
-        view = self.new(a.shape, offset)
-        view.copy_(torch.from_numpy(np.array(a, copy=True)))
-        return view
-
-    def check(self):
-        torch.cuda.synchronize()
-        for k, (buf, lo, n) in enumerate(self.bufs):
-            front, back = host(buf[:lo]), host(buf[lo + n:])
-            assert (front == F(CANARY)).all() and (back == F(CANARY)).all(), "allocation %d: %d canaries overwritten in front, %d behind" % (
-                k, int((front != F(CANARY)).sum()), int((back != F(CANARY)).sum()))
 
 
 def written(a):

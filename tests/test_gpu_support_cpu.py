@@ -52,6 +52,38 @@ def test_fp32_reference_refuses_what_is_not_an_fp32_number():
     assert gs.fp32_reference(lambda: (calls.append(1), exact)[1], key=("self-test", 1)) is first and calls == [1]     # kept per key
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.int64, torch.uint8], ids=str)
+def test_arena_catches_an_overwritten_canary_on_either_side(dtype):
+    ar = gs.Arena(device="cpu")
+    first, view = ar.new((2, 3), dtype=dtype), ar.new((3, 5), offset=1, dtype=dtype)
+    assert (view == gs.SENTINEL[dtype]).all() and view.device.type == "cpu" and view.data_ptr() % 16 == view.element_size() % 16
+    view.zero_()                                                            # a call that writes its whole output and nothing else
+    first[0, 0] = 1
+    ar.check()
+    buf, lo, n, _ = ar.bufs[1]
+    assert buf[lo:lo + n].data_ptr() == view.data_ptr() and lo * view.element_size() == gs.GUARD_BYTES + view.element_size()
+    for where, said in ((lo - 1, "allocation 1: 1 canaries overwritten in front, 0 behind"), (lo + n, "allocation 1: 0 canaries overwritten in front, 1 behind")):
+        kept = buf[where].clone()
+        buf[where] = 0
+        with pytest.raises(AssertionError, match=said):
+            ar.check()
+        buf[where] = kept
+    ar.check()
+    if dtype == torch.float32:
+        put = ar.put(np.arange(6, dtype=np.float32).reshape(2, 3), offset=2)
+        assert put.tolist() == [[0.0, 1.0, 2.0], [3.0, 4.0, 5.0]] and put.data_ptr() % 16 == 8
+        ar.check()
+
+
+def test_same_bits_and_differing_compare_bits_not_values():
+    a = np.array([0.0, 1.0, np.nan], np.float32)
+    assert gs.same_bits(a, a.copy()) and gs.differing(a, a.copy()) == 0     # a NaN equals itself bit for bit
+    b = a.copy()
+    b[0] = -0.0                                                             # equal as a value, another bit pattern
+    assert not gs.same_bits(a, b) and gs.differing(a, b) == 1
+    assert not gs.same_bits(a, a.reshape(3, 1))
+
+
 def test_bf16x1_criterion():
     win = (slice(None), slice(None), slice(2, 4), slice(2, 6))
     ref16 = _out().astype(np.float64)

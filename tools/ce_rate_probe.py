@@ -2,7 +2,7 @@
 512 x 1024 ERP image), K = 49 classes, at batch 8 and batch 1, on one stream:
   library  lic360_operator.CeRateLoss(route="library"): ContextReshape, torch.nn.functional.cross_entropy(reduction="none"), a per-image float64
            sum, and their autograd;
-  fused    CeRateLoss(route="fused"): lic360.ce_rate (k_ce_rate, k_ce_rate_finish) and, recording, autograd.CeRateFn with lic360.ce_rate_backward
+  fused    CeRateLoss(route="fused"): lic360.ce_rate (k_ce_rate, k_plane_sum_finish) and, recording, autograd.CeRateFn with lic360.ce_rate_backward
            (k_ce_rate_backward).  The module's label check is on, as by default (one synchronisation per call).
 The two alternate in one process: --repeats (20) timed windows of --calls (50) calls each, each after 5 warm-up calls, timed with device events
 around the window -- a window of a few milliseconds, so that the events' resolution and one scheduling hiccup do not make the figure; median

@@ -2,7 +2,7 @@
 components, at batch 8 and batch 1, with SURVEY.md 8d's smooth masks (tests/util.py:latent_smooth) and with every symbol coded:
   library  lic360_operator.GmmRateLoss(route="library"): ContextReshape x 3, torch.softmax, relu, + 1e-5, EntropyGmm, the product with the mask
            and a per-image float64 sum, and their autograd;
-  fused    GmmRateLoss(route="fused"): lic360.gmm_rate (k_gmm_rate, k_gmm_rate_finish) and, recording, autograd.GmmRateFn with
+  fused    GmmRateLoss(route="fused"): lic360.gmm_rate (k_gmm_rate, k_plane_sum_finish) and, recording, autograd.GmmRateFn with
            lic360.gmm_rate_backward (k_gmm_rate_backward).
 The two alternate in one process: --repeats (20) repeats of 5 calls each, each after 2 warm-up calls, timed with device events; median
 (min - max) ms per call, for the forward alone (no gradient recorded) and for forward + backward of sum(g * nats) with the three nets'
