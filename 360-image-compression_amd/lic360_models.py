@@ -111,6 +111,16 @@ def set_conv_precision(module, precision, stride2="fp32", gdn="fp32", gate="libr
     return module
 
 
+def set_gdn_grad(module, grad):
+    """where the recording passes of every lic360_operator.GDN under `module` go: "library" (the composition and autograd's chain, the default) or "fused"
+    (autograd.GdnFn: the one-pass forward and lic360.gdn_backward, which keeps nothing but x).  Returns how many GDNs were set."""
+    grad = GDN._grad(grad)
+    gdns = [m for m in module.modules() if isinstance(m, GDN)]
+    for m in gdns:
+        m.grad = grad
+    return len(gdns)
+
+
 def _records_grad(x, conv, mod=None):
     """is a gradient recorded here?  (The kernels have no backward: with gradients enabled a fused path is taken only if neither x, the layer's weight nor ANY parameter
     of the block `mod` that the path pushes through them -- the 1x1 layers, shortcuts, PReLU slopes, biases: all of the block -- requires one)"""

@@ -181,3 +181,24 @@ class MaskConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             db = g.sum((0, 2, 3))
         return dx, dw, db, None, None, None
+
+
+class GdnFn(torch.autograd.Function):
+    """(x, gamma, beta) -> lic360.gdn_forward on the effective parameters (the bits of the inference forward); saves x, gamma and beta only.
+    backward: lic360.gdn_backward recomputes the norm from x and returns what needs_input_grad asks for; the bound / square / pedestal
+    reparametrisation in front of gamma and beta stays torch work and carries these gradients on to the raw parameters."""
+    @staticmethod
+    def forward(ctx, x, gamma, beta, inverse):
+        import lic360
+        ctx.inverse = bool(inverse)
+        ctx.save_for_backward(x, gamma, beta)
+        return lic360.gdn_forward(x, gamma.detach(), beta.detach(), ctx.inverse)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        import lic360
+        x, gamma, beta = ctx.saved_tensors
+        need_params = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        gx, gg, gb = lic360.gdn_backward(x, _c(g), gamma, beta, ctx.inverse, need_x=ctx.needs_input_grad[0], need_params=need_params)
+        return gx, gg if ctx.needs_input_grad[1] else None, gb if ctx.needs_input_grad[2] else None, None

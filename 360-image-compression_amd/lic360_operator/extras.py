@@ -42,8 +42,20 @@ class _FloorSTE(torch.autograd.Function):
 
 
 class GDN(nn.Module):
-    def __init__(self, ch, device=0, inverse=False, beta_min=1e-6, gamma_init=.1, reparam_offset=2 ** -18):
+    """grad: where a pass that records gradients goes.  "library" (the default): the reference's composition -- x * x, a 1x1 conv2d, sqrt and a
+    division or product -- and autograd's chain through it, which keeps x^2 and the norm for the backward.  "fused" (opt-in): an fp32 CUDA tensor of
+    a channel count the one-pass kernel takes goes through autograd.GdnFn -- lic360.gdn_forward, then lic360.gdn_backward, which recomputes the
+    norm and keeps nothing but x; CPU tensors, other dtypes and other channel counts still take the composition.  Under "fused" the recording
+    forward is the fp32 kernel whatever `_gdn_precision` says (the backward's recomputed sum is then the forward's, bit for bit), and it returns
+    the bits the fp32 inference forward returns.  The reparametrisation of beta and gamma is torch work on both routes; state dict, parameter names
+    and shapes do not depend on the route.  The attribute can be switched between calls (lic360_models.set_gdn_grad does it for a whole model).
+    Measured (tools/gdn_grad_probe.py, DESIGN.md "Native backward of the one-pass GDN"): the table there says what the fused route buys and why
+    "library" stays the default."""
+    GRADS = ("library", "fused")
+
+    def __init__(self, ch, device=0, inverse=False, beta_min=1e-6, gamma_init=.1, reparam_offset=2 ** -18, grad="library"):
         super().__init__()
+        self.grad = self._grad(grad)
         self.inverse = bool(inverse)
         dev = torch.device("cuda:%d" % (device if isinstance(device, int) else device[0])) if torch.cuda.is_available() else torch.device("cpu")
         ped = float(reparam_offset) ** 2
@@ -53,7 +65,27 @@ class GDN(nn.Module):
         self.beta = nn.Parameter(torch.sqrt(torch.ones(ch) + ped).to(dev))
         self.gamma = nn.Parameter(torch.sqrt(float(gamma_init) * torch.eye(ch) + ped).to(dev))
 
+    @classmethod
+    def _grad(cls, grad):
+        if grad not in cls.GRADS:
+            raise ValueError("GDN: grad must be one of %s, got %r" % (", ".join(repr(g) for g in cls.GRADS), grad))
+        return grad
+
+    def _fused_backward(self, x):
+        """does this call record gradients on a tensor the native forward and backward take?"""
+        if not (torch.is_grad_enabled() and (x.requires_grad or self.beta.requires_grad or self.gamma.requires_grad)):
+            return False
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3 and x.numel() > 0):
+            return False
+        import lic360
+        return lic360.gdn_supported(x.shape[1])
+
     def forward(self, x):
+        if getattr(self, "grad", "library") == "fused" and self._fused_backward(x):
+            from .autograd import GdnFn
+            beta = _FloorSTE.apply(self.beta.to(x.device), self.beta_bound) ** 2 - self.pedestal
+            gamma = _FloorSTE.apply(self.gamma.to(x.device), self.gamma_bound) ** 2 - self.pedestal
+            return GdnFn.apply(x.contiguous(), gamma, beta, self.inverse)
         shape = x.shape
         if x.dim() == 5:
             x = x.reshape(shape[0], shape[1], shape[2] * shape[3], shape[4])
